@@ -4,12 +4,16 @@
                                                              ranks itself, one process per GPU, like the reference's
                                                              mp.spawn in espnet2/tasks/abs_task.py:1026-1045)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py --full                                  (+ roofline / kernel profile, comm, vocoder + infill,
+                                                             configs[3], collate and CPU-baseline legs)
+    python bench.py --dump-outputs DIR                      (+ what the last timed step computed, as DIR/*.npy)
 
 A step = forward + loss + full backward + (RCCL gradient all-reduce if N>1) + grad-norm/clip/Adam
 of one synthetic batch that is already resident in HBM when the timed region
 starts.  Workload = BASELINE.json configs[1]: 6 enc + 6 dec Conformer blocks ("12L"), d=384,
 B=32/GPU, T_mel=1000, T_phn=120, bf16 MFMA compute with fp32 accumulation/master weights.
-Prints ONE JSON line on rank 0.  The CPU oracle is imported only for the cpu_baseline leg.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0; every other
+figure is measured only with --full.  The CPU oracle is imported only for the --full legs.
 """
 import argparse
 import json
@@ -93,6 +97,34 @@ def build_trainer(cfg, device, compute, world, dropout=True, comm_dtype=torch.fl
     xavier_init_(store, seed=0, bn_gamma=1.0)
     return A3TTrainer(cfg, store, compute=compute, lr=1.0, warmup_steps=4000, grad_clip=1.0, dropout=dropout,
                       comm_dtype=comm_dtype)
+
+
+# --dump-outputs: largest number of elements written per array; a larger tensor is written as a fixed, seeded sample of its
+# elements.  Two mel outputs + four flat buffers stay under 2 x 16 + 4 x 4 = 48 MB of float32 whatever the arguments.
+DUMP_MEL_MAX = 4 << 20
+DUMP_FLAT_MAX = 1 << 20
+
+
+def dump_outputs(out_dir, tr, loss):
+    """What the timed step computed in its last call, as float32 .npy files: the loss it returns, the forward's mel outputs
+    (before / after the postnet, [B, T_mel, odim] when whole), and the parameters, gradient and Adam moments it leaves in
+    the trainer.  A tensor above its cap is flattened and sampled at indices drawn from a fixed seed, so two runs with the
+    same arguments write the same elements."""
+    import numpy as np
+    _hs, before, after, _db, _da = tr.engine.sv["head"]
+    B, Tm = tr.engine.dims[:2]
+    arrays = dict(loss=(loss, 1), mel_before=(before, DUMP_MEL_MAX), mel_after=(before if after is None else after, DUMP_MEL_MAX),
+                  params=(tr.store.flat, DUMP_FLAT_MAX), grad=(tr.store.grad, DUMP_FLAT_MAX), adam_m=(tr.m, DUMP_FLAT_MAX),
+                  adam_v=(tr.v, DUMP_FLAT_MAX))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (t, cap) in arrays.items():
+        t = t.detach().float()
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        elif name.startswith("mel_"):
+            t = t.reshape(B, Tm, -1)
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def c4_leg(dev, compute, steps=8, warmup=3):
@@ -411,7 +443,16 @@ def main():
                     help="do not measure roofline.traffic with two rocprofv3 --pmc passes of a child process (the tracked file is used)")
     ap.add_argument("--threads", type=int, default=32)
     ap.add_argument("--budget", type=float, default=20.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline / kernel profile, the gradient exchange (N>1), the vocoder + "
+                         "infill, configs[3], collate and CPU-baseline legs (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, < 64 MB in all; rank 0)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:       # a plain run measures the headline step and nothing else
+        a.no_kernel_profile = a.no_vocoder = a.no_c4 = a.no_collate = a.no_cpu_baseline = True
     if a.cpu_baseline_worker:
         cpu_baseline_worker(a.blocks, a.tmel, a.tphn, a.threads, a.budget)
         return
@@ -486,9 +527,12 @@ def main():
     step_flops = 3.0 * fwd_flops_per_step(cfg, B, Tm, Tp)
     final_loss = float(loss)
     log(f"{ms:.1f} ms/step, {value:.0f} frames/s, loss {final_loss:.4f}")
+    if a.dump_outputs and rank == 0:      # before anything else runs a step
+        dump_outputs(a.dump_outputs, tr, loss)
+        log(f"outputs of the last timed step written to {a.dump_outputs}")
 
     comm = None
-    if world > 1:
+    if world > 1 and a.full:
         # the gradient exchange alone: the flat buffer in the trainer's buckets, 3 repetitions; bus bandwidth as
         # RCCL defines it for all-reduce: 2 (N-1)/N x bytes / time (what each xGMI link pair has to carry)
         gbuf = torch.zeros_like(tr.store.grad) if tr.comm_dtype == torch.float32 else \

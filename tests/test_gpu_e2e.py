@@ -696,3 +696,29 @@ def test_speech_editor_end_to_end_against_oracle(kind):
     assert np.array_equal(got["orgin_replaced"][:h * ob[0]], wav[:h * ob[0]])
     if h * ob[1] < len(wav):
         assert np.array_equal(got["orgin_replaced"][h * nb[1]:], wav[h * ob[1]:])
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """`bench.py` without --full times the step and reports nothing else; --dump-outputs writes what the last timed step
+    computed (loss, mel outputs, sampled parameter / gradient / Adam buffers) as float32 .npy files under 64 MB."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--blocks", "1", "--batch", "4", "--tmel",
+                        "200", "--tphn", "24", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["roofline"] is None
+    assert not {"comm", "vocoder", "c4", "collate", "cpu_baseline"} & set(out)
+    got = {p.stem: np.load(p) for p in d.glob("*.npy")}
+    assert set(got) == {"loss", "mel_before", "mel_after", "params", "grad", "adam_m", "adam_v"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(p.stat().st_size for p in d.glob("*.npy")) < 64 << 20
+    assert float(got["loss"][0]) == out["config"]["final_loss"]
+    assert got["mel_before"].shape == got["mel_after"].shape == (4, 200, 80)
+    assert got["params"].shape == got["grad"].shape == (1 << 20,) and np.abs(got["grad"]).max() > 0

@@ -175,7 +175,7 @@ def test_bench_n_rank_path_dry_run_on_one_gpu_over_gloo():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--one-gpu-gloo", "--blocks", "1", "--batch", "4",
-                        "--tmel", "200", "--tphn", "24", "--steps", "2", "--warmup", "1"],
+                        "--tmel", "200", "--tphn", "24", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]

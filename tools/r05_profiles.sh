@@ -7,7 +7,8 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 export A3T_ROUND=r05 PYTHONPATH=$R
 cd $R; mkdir -p gpurun_out
-python bench.py > gpurun_out/r05_bench_n1.json 2> gpurun_out/r05_bench_n1.log
+OUT=${OUT:-$R/out}; mkdir -p "$OUT"      # the bench line (all legs) and the step A/B table
+python bench.py --full > "$OUT/r05_bench_n1.json" 2> "$OUT/r05_bench_n1.log"
 cd /tmp && export TMPDIR=/tmp
 for mode in 1 0; do
   rm -rf $R/gpurun_out/r05_prof_s$mode
@@ -76,6 +77,6 @@ python tools/attn_bench.py > gpurun_out/r05_attn_bench.txt 2>&1
 TRAIN=1 python tools/attn_fwd_time.py >> gpurun_out/r05_attn_bench.txt 2>&1
 python tools/attn_ds_time.py >> gpurun_out/r05_attn_bench.txt 2>&1
 python tools/collate_time.py > gpurun_out/r05_collate_time.txt 2>&1
-bash tools/step_ab.sh "default:A3T_X=0" "weight_gradients_on_the_128x128_kernel:A3T_GEMM_8P_TN3=0" "no_grouped_linear_weight_gradients:A3T_WGRAD_GROUP=0" "materialised_score_gradients:A3T_ATTN_BWD_DS=0" "materialised_attention_forward:A3T_FUSED_ATTN_TRAIN=0" "one_stream:A3T_SIDE_STREAM=0" "round4_equivalent:A3T_GEMM_8P_TN3=0 A3T_WGRAD_GROUP=0 A3T_ATTN_BWD_DS=0" "default_again:A3T_X=0" > gpurun_out/r05_step_ab.txt 2>&1
+bash tools/step_ab.sh "default:A3T_X=0" "weight_gradients_on_the_128x128_kernel:A3T_GEMM_8P_TN3=0" "no_grouped_linear_weight_gradients:A3T_WGRAD_GROUP=0" "materialised_score_gradients:A3T_ATTN_BWD_DS=0" "materialised_attention_forward:A3T_FUSED_ATTN_TRAIN=0" "one_stream:A3T_SIDE_STREAM=0" "round4_equivalent:A3T_GEMM_8P_TN3=0 A3T_WGRAD_GROUP=0 A3T_ATTN_BWD_DS=0" "default_again:A3T_X=0" > "$OUT/r05_step_ab.txt" 2>&1
 bash tools/c4_ab.sh "default:A3T_X=0" "score_gradients_in_one_launch:A3T_ATTN_BWD_DS=1" "128x384_tiles_everywhere:A3T_GEMM_8P_TN3=1" "atomic_epilogue:A3T_GEMM_8P_TN_SLAB=0" "default_again:A3T_X=0" > gpurun_out/r05_c4_ab.txt 2>&1
-tail -c 400 gpurun_out/r05_bench_n1.json; cat gpurun_out/r05_step_ab.txt
+tail -c 400 "$OUT/r05_bench_n1.json"; cat "$OUT/r05_step_ab.txt"

@@ -7,7 +7,8 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 export A3T_ROUND=r06 PYTHONPATH=$R
 cd $R; mkdir -p gpurun_out
-python bench.py > gpurun_out/r06_bench_n1.json 2> gpurun_out/r06_bench_n1.log
+OUT=${OUT:-$R/out}; mkdir -p "$OUT"      # the bench line (all legs) and the step A/B table
+python bench.py --full > "$OUT/r06_bench_n1.json" 2> "$OUT/r06_bench_n1.log"
 cd /tmp && export TMPDIR=/tmp
 for mode in 1 0; do
   rm -rf $R/gpurun_out/r06_prof_s$mode
@@ -77,11 +78,11 @@ TRAIN=2 python tools/attn_fwd_time.py >> gpurun_out/r06_attn_bench.txt 2>&1
 python tools/ffn_dgrad2_time.py >> gpurun_out/r06_attn_bench.txt 2>&1
 python tools/attn_ds_time.py >> gpurun_out/r06_attn_bench.txt 2>&1
 python tools/collate_time.py > gpurun_out/r06_collate_time.txt 2>&1
-bash tools/step_ab.sh "default:A3T_X=0" "weight_gradients_on_the_128x128_kernel:A3T_GEMM_8P_TN3=0" "no_grouped_linear_weight_gradients:A3T_WGRAD_GROUP=0" "attention_products_on_the_128_row_kernel:A3T_GEMM_TT=0" "two_saved_probability_tensors:A3T_ATTN_SIGNED=0" "stored_dbd_matrix:A3T_ATTN_DBD_VIEW=0" "dk_on_the_second_side_queue:A3T_ATTN_DK_MAIN=0" "dq_as_two_launches:A3T_ATTN_DQ_DUAL=0" "ffn_mask_from_the_saved_activation:A3T_FFN_KEEP4=0" "both:A3T_ATTN_SIGNED=0 A3T_FFN_KEEP4=0" "materialised_score_gradients:A3T_ATTN_BWD_DS=0" "materialised_attention_forward:A3T_FUSED_ATTN_TRAIN=0" "one_stream:A3T_SIDE_STREAM=0" "default_again:A3T_X=0" > gpurun_out/r06_step_ab.txt 2>&1
+bash tools/step_ab.sh "default:A3T_X=0" "weight_gradients_on_the_128x128_kernel:A3T_GEMM_8P_TN3=0" "no_grouped_linear_weight_gradients:A3T_WGRAD_GROUP=0" "attention_products_on_the_128_row_kernel:A3T_GEMM_TT=0" "two_saved_probability_tensors:A3T_ATTN_SIGNED=0" "stored_dbd_matrix:A3T_ATTN_DBD_VIEW=0" "dk_on_the_second_side_queue:A3T_ATTN_DK_MAIN=0" "dq_as_two_launches:A3T_ATTN_DQ_DUAL=0" "ffn_mask_from_the_saved_activation:A3T_FFN_KEEP4=0" "both:A3T_ATTN_SIGNED=0 A3T_FFN_KEEP4=0" "materialised_score_gradients:A3T_ATTN_BWD_DS=0" "materialised_attention_forward:A3T_FUSED_ATTN_TRAIN=0" "one_stream:A3T_SIDE_STREAM=0" "default_again:A3T_X=0" > "$OUT/r06_step_ab.txt" 2>&1
 bash tools/c4_ab.sh "default:A3T_X=0" "stored_dbd_matrix:A3T_ATTN_DBD_VIEW=0" "two_saved_probability_tensors:A3T_ATTN_SIGNED=0" "materialised_score_gradients:A3T_ATTN_BWD_DS=0" "attention_products_on_the_128_row_kernel:A3T_GEMM_TT=0" "128x384_tiles_everywhere:A3T_GEMM_8P_TN3=1" "default_again:A3T_X=0" > gpurun_out/r06_c4_ab_final.txt 2>&1
 bash tools/trace_step.sh > gpurun_out/r06_trace.log 2>&1
 python tools/trace_analyse.py gpurun_out/trace_step.csv > gpurun_out/r06_trace_analysis.txt 2>&1
 rm -f gpurun_out/trace_step.csv
 python tools/gemm_shapes.py > gpurun_out/r06_gemm_shapes.txt 2>&1
 python tools/hbm_bound_table.py r06 gpurun_out > gpurun_out/r06_hbm_bound_kernels.txt 2>&1
-tail -c 400 gpurun_out/r06_bench_n1.json; cat gpurun_out/r06_step_ab.txt
+tail -c 400 "$OUT/r06_bench_n1.json"; cat "$OUT/r06_step_ab.txt"
