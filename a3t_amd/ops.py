@@ -536,6 +536,18 @@ def bias_act(x, bias, act, scale_=1.0):
     L.check(L.load().a3t_bias_act(_ptr(x), _ptr(bias), M, C, act, scale_, _stream()), "bias_act")
 
 
+def duration_head(z, g, b, w, bias, logd, frames, eps=1e-12, offset=1.0):
+    """logd[m] = LayerNorm(z[m]) . w + bias, frames[m] = clamp(round(exp(logd[m]) - offset), min=0) (int64)."""
+    M, C = z.shape
+    L.check(L.load().a3t_duration_head(_ptr(z), _ptr(g), _ptr(b), _ptr(w), _ptr(bias), _ptr(logd), _ptr(frames), M, C, eps,
+                                       offset, _stream()), "duration_head")
+
+
+def l2_normalize(x, y, eps=1e-12):
+    B, n = x.shape
+    L.check(L.load().a3t_l2_normalize(_ptr(x), _ptr(y), B, n, eps, _stream()), "l2_normalize")
+
+
 def dropout(x, y, p, key, scale=1.0):
     L.check(L.load().a3t_dropout(_ptr(x), _dt(x), _ptr(y), _dt(y), x.numel(), p, key, scale, _stream()), "dropout")
 

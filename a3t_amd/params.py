@@ -156,10 +156,12 @@ def reference_shape(kind: str, store_shape: tuple, key: str) -> tuple:
 class ParamStore:
     """Flat fp32 parameter / gradient / Adam-moment buffers with named views."""
 
-    def __init__(self, cfg: A3TConfig, device):
+    def __init__(self, cfg: A3TConfig, device, layout=None, buffers=None, keymap=None):
+        """layout / buffers / keymap: another model's parameter layout, buffer layout and reference key map (the duration
+        model of a3t_amd/duration.py); default: the masked-mel model's."""
         self.cfg = cfg
         self.device = torch.device(device)
-        self.layout = param_layout(cfg)
+        self.layout = param_layout(cfg) if layout is None else layout
         self.offsets: Dict[str, Tuple[int, tuple]] = {}
         off = 0
         for name, shp in self.layout.items():
@@ -173,11 +175,11 @@ class ParamStore:
         self.p = {k: self.flat[o:o + int(np.prod(s))].view(s) for k, (o, s) in self.offsets.items()}
         self.g = {k: self.grad[o:o + int(np.prod(s))].view(s) for k, (o, s) in self.offsets.items()}
         self.buf = {}
-        for k, s in buffer_layout(cfg).items():
+        for k, s in (buffer_layout(cfg) if buffers is None else buffers).items():
             self.buf[k] = (torch.ones if k.endswith(".rv") else torch.zeros)(s, dtype=torch.float32,
                                                                              device=self.device)
         self.nbt = {}  # num_batches_tracked counters (host ints)
-        self.keymap = reference_key_map(cfg)
+        self.keymap = reference_key_map(cfg) if keymap is None else keymap
 
     # ---- reference checkpoint format ---------------------------------------------------------
     def _view(self, name, rows, kind, grads=False):

@@ -366,6 +366,16 @@ int a3t_pwg_upsample(const float* c, const float* w, float* out, int64_t B, int6
 int a3t_replicate_pad(const float* x, float* y, int64_t B, int64_t T, int C, int pad, void* stream);
 int a3t_bias_act(float* x, const float* bias, int64_t M, int C, int act, float scale, void* stream);
 
+/* FastSpeech2 duration head (fastspeech/duration_predictor.py:77-95, inference): per row of z [M][C] -- the last predictor
+ * conv after its bias and ReLU -- LayerNorm over C (eps, biased variance), x = LN(z) . w + bias[0] (Linear(C -> 1); bias
+ * on the device), logd[m] = x (fp32, log domain), frames[m] = max(round_half_even(exp(x) - offset), 0) (int64).  One wave
+ * per row; C <= 512, A3T_EINVAL otherwise. */
+int a3t_duration_head(const float* z, const float* gamma, const float* beta, const float* w, const float* bias,
+                      float* logd, int64_t* frames, int M, int C, float eps, float offset, void* stream);
+/* y[b] = x[b] / max(||x[b]||_2, eps) over rows of x [B][n] (torch.nn.functional.normalize: the x-vector of
+ * fastspeech2.py:797-805). */
+int a3t_l2_normalize(const float* x, float* y, int B, int n, float eps, void* stream);
+
 /* Dropout (torch.nn.Dropout sites of the path).  Counter-based: keep = f(key, element index), so the
  * same key reproduces the mask in the backward pass and inside GEMM epilogues; no mask tensors.
  * y = scale * x * keep/(1-p); in place allowed; x / y may be fp32 or bf16. */
