@@ -44,6 +44,7 @@ class GemmDesc(ctypes.Structure):
 _P = c_void_p
 _SIGS = {
     "a3t_gemm": [POINTER(GemmDesc), _P],
+    "a3t_gemm_plan": [POINTER(GemmDesc), c_char_p, c_int],
     "a3t_layernorm_fwd": [_P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_float, _P],
     "a3t_layernorm_bwd": [_P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_int, c_int, c_float,
                           ctypes.c_uint32, _P],

@@ -19,17 +19,10 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #include "gemm_common.h"
 
-int a3t_gemm_bf16_glds(const GP& p, int batch, bool AK, bool BKC, hipStream_t stream);
-
-#include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 static thread_local char g_last_kernel[128] = "";
-void a3t_note_kernel(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_last_kernel, sizeof(g_last_kernel), fmt, ap);
-    va_end(ap);
-}
+void a3t_note_kernel(const char* name) { snprintf(g_last_kernel, sizeof(g_last_kernel), "%s", name); }
 extern "C" const char* a3t_gemm_last_kernel(void) { return g_last_kernel; }
 
 // =============================================================================================
@@ -429,15 +422,112 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GP p) {
 }
 
 // =============================================================================================
-// host dispatch
+// host: what the GEMM files share (CU count, switches), the plan (route table) and the launch
 // =============================================================================================
+int gemm_cus() {          // per device (a process may drive several GPUs)
+    static int n[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (!n[dev]) {
+        hipDeviceProp_t pr;
+        if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
+        n[dev] = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
+    }
+    return n[dev];
+}
+
+// Kernel-selection switches, read from the environment on first use.  8P / PN / TT / 8P_TN / 8P_TN3: 0 never, 1 whenever legal,
+// 2 (default) the kernel's cost model (PN 3: the cost model for N = 384 only).  STAGES: LDS stages of the 128-row kernel, 1 / 2
+// forced (unset: by grid size).  WN3: its 192-column tiles, 0 never, 2 always (unset: where they waste fewer padded columns).
+static int sw_mode(const char* e) { return e ? atoi(e) : 2; }
+static int sw_stages(const char* e) { return e ? (e[0] == '1' ? 1 : 2) : 0; }
+static int sw_wn3(const char* e) { return e ? (e[0] == '0' ? 0 : 2) : 1; }
+static const struct {
+    const char* env;
+    int (*read)(const char*);
+} k_switch[] = {{"A3T_GEMM_8P", sw_mode},     {"A3T_GEMM_PN", sw_mode},         {"A3T_GEMM_TT", sw_mode}, {"A3T_GEMM_8P_TN", sw_mode},
+                {"A3T_GEMM_8P_TN3", sw_mode}, {"A3T_GEMM_STAGES", sw_stages}, {"A3T_GEMM_WN3", sw_wn3}};
+static int g_switch[] = {-1, -1, -1, -1, -1, -1, -1};
+int gemm_switch(int s) {
+    if (g_switch[s] < 0) g_switch[s] = k_switch[s].read(getenv(k_switch[s].env));
+    return g_switch[s];
+}
+int gemm_switch_set(int s, int v) {
+    const int old = gemm_switch(s);
+    g_switch[s] = v;
+    return old;
+}
+extern "C" int a3t_gemm_8p_mode(int mode) { return gemm_switch_set(SW_8P, mode); }
+extern "C" int a3t_gemm_pn_mode(int mode) { return gemm_switch_set(SW_PN, mode); }
+extern "C" int a3t_gemm_tt_mode(int mode) { return gemm_switch_set(SW_TT, mode); }
+extern "C" int a3t_gemm_tn3_mode(int mode) { return gemm_switch_set(SW_8P_TN3, mode); }
+
+GP gemm_rep(int M, int N, int K, int taps, int flags, int keep_layout) {
+    static float dummy[4] __attribute__((aligned(16)));
+    GP p = {};
+    p.M = M, p.N = N, p.K = K, p.taps = taps < 1 ? 1 : taps, p.Kc = K / p.taps, p.b_ts = p.Kc;
+    p.a_rs = p.Kc, p.a_cs = 1, p.b_rs = K, p.b_cs = 1, p.c_rs = N, p.splitk = 1, p.accumulate = A3T_ACC_STORE;
+    p.Tseq = 1, p.colsum_slots = 1, p.c_dtype = (flags & 16) ? A3T_F32 : A3T_BF16;
+    if (flags & 1) p.bias = dummy, p.act = A3T_ACT_RELU;
+    if (flags & 2) p.drop_inv = 1.25f;
+    if (flags & 4) p.keep_out = (unsigned char*)dummy;
+    if (flags & 8) p.keep_in = (const unsigned char*)dummy, p.keep_layout = keep_layout;
+    if (flags & 32) p.colsum = dummy;
+    if (flags & 64) p.S = dummy, p.s_dtype = A3T_BF16;
+    return p;
+}
+
 static inline bool al(const void* p, int b) { return ((uintptr_t)p % b) == 0; }
 static inline bool m4(int64_t v, int m) { return (v % m) == 0; }
 
-extern "C" int a3t_gemm(const a3t_gemm_desc* d, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+// The direct-to-LDS bf16 kernels: their alignment contract, then the routes in order -- 384-column panel, 8-phase (TN: 128 x 384
+// or 256 x 256 tiles), streaming, 128-row.  false: none of them takes the descriptor.
+static bool glds_routes(GP& p, int batch, bool AK, bool BKC, GemmPlan* pl) {
+    const bool aview = (p.a_unaligned & 1) != 0;     // A: a 2-byte aligned strided view (the loaders only do pointer arithmetic)
+    bool ok = (aview || al(p.A, 16)) && al(p.B, 16) && m4(p.a_bs0, 8) && m4(p.a_bs1, 8) && m4(p.b_bs0, 8) && m4(p.b_bs1, 8);
+    if (AK || BKC) ok = ok && m4(p.Kc, 8);      // (16-byte granules run along k only for k-contiguous operands)
+    if (AK)
+        ok = ok && (aview || m4(p.a_rs, 8)) && m4(p.K, 8);
+    else
+        ok = ok && (aview || m4(p.a_cs, 8)) && m4(p.M, 8);
+    if (BKC)
+        ok = ok && m4(p.b_rs, 8) && m4(p.K, 8) && m4(p.b_ts, 8);
+    else
+        ok = ok && m4(p.b_cs, 8) && m4(p.b_ts, 8) && m4(p.N, 8);
+    if (!AK && p.taps > 1) ok = ok && ((p.N / p.taps) % 128 == 0) && (p.N % p.taps == 0) && p.Tseq > 0;
+    if (!ok || (p.colsum && p.accumulate == A3T_ACC_ATOMIC)) return false;
+    // vector epilogue contract: 4-column groups never straddle N and every C/R/S/bias access is aligned
+    const int epi_vec = (p.N % 4 == 0) && (p.c_rs % 4 == 0) && (p.c_bs0 % 4 == 0) && (p.c_bs1 % 4 == 0) && al(p.C, 16) &&
+                        (!p.R || al(p.R, 16)) && (!p.S || al(p.S, 8)) && (!p.bias || al(p.bias, 16));
+    if (p.colsum && !epi_vec) return false;
+    const bool keep = p.keep_in || p.keep_out;
+    const bool keep_rm = p.keep_layout == 1 && keep;      // row-major nibble image: vector epilogue / panel kernel
+    if (keep_rm && (!epi_vec || p.c_rs != p.N || batch != 1 || p.splitk != 1 || p.accumulate != A3T_ACC_STORE || p.N % 8 ||
+                    (p.keep_out && p.R) || (p.keep_in && p.S)))
+        return false;
+    if (p.a_signmask && (AK || BKC || p.taps > 1 || p.kshift_mode)) return false;   // (fragment-register pass of the m-contiguous A only)
+    p.epi_vec = epi_vec;
+    const int ly = (AK && BKC) ? L_NT : (AK ? L_NN : L_TN);
+    // N = 384 outputs: one 160-row panel x all columns per workgroup
+    if (!(p.keep_out || (p.keep_in && !keep_rm) || p.a_signmask || p.A2 || aview) && pn_plan(p, batch, ly, pl)) return true;
+    if (!p.a_signmask && !keep_rm && !p.A2 && !aview) {   // many-tile k-contiguous GEMMs and token reductions: the 8-phase kernels
+        if (g8_plan(p, batch, ly, pl)) return true;
+        if (keep) return false;                           // (the tile-major keep-bit image exists in the 8-phase kernel only)
+    }
+    // score-sized A operand x [k][n] slices (attention backward): one streaming workgroup per CU
+    if (!BKC && !keep && !aview && tt_plan(p, batch, AK ? L_NN : L_TN, pl)) return true;
+    if (p.A2) return false;        // two products in one launch: the streaming kernel only (a3t_gemm_tt_supported)
+    glds_plan(p, batch, ly, pl);
+    return true;
+}
+
+// Validates the descriptor, fills the kernel argument and walks the routes: fused conv weight gradient, fp32, the direct-to-LDS
+// bf16 kernels, the legacy bf16 kernel.  Returns 0 or A3T_EINVAL; launches nothing.
+static int gemm_plan(const a3t_gemm_desc* d, GP* gp, GemmPlan* pl) {
     if (!d || !d->A || !d->B || !d->C || d->M <= 0 || d->N <= 0 || d->K <= 0) return A3T_EINVAL;
-    GP p;
+    GP& p = *gp;
+    p = GP{};
+    *pl = GemmPlan{};
     p.A = d->A, p.B = d->B, p.C = d->C, p.bias = d->bias, p.R = d->R, p.S = d->S;
     p.M = d->M, p.N = d->N, p.K = d->K;
     p.taps = d->taps < 1 ? 1 : d->taps;
@@ -459,7 +549,6 @@ extern "C" int a3t_gemm(const a3t_gemm_desc* d, void* stream_) {
     if (p.splitk > 1 && p.accumulate != A3T_ACC_ATOMIC) return A3T_EINVAL;
     p.c_dtype = d->c_dtype;
     p.s_dtype = d->s_dtype;
-    p.epi_vec = 0;
     p.colsum = d->colsum, p.colsum_bs1 = d->colsum_bs1, p.colsum_scale = d->colsum_scale;
     p.colsum_slots = d->colsum_slots > 1 ? d->colsum_slots : 1, p.colsum_ss = d->colsum_ss;
     if (d->drop_p < 0.f || d->drop_p >= 1.f) return A3T_EINVAL;
@@ -467,8 +556,6 @@ extern "C" int a3t_gemm(const a3t_gemm_desc* d, void* stream_) {
     p.drop_thr = (unsigned int)((double)d->drop_p * 4294967296.0);
     p.drop_inv = d->drop_p > 0.f ? 1.f / (1.f - d->drop_p) : 0.f;
     p.keep_out = (unsigned char*)d->keep_out, p.keep_in = (const unsigned char*)d->keep_in;
-    p.a_bytes = p.b_bytes = 0;
-    p.slab = nullptr;
     p.a_signmask = d->a_signmask ? 1 : 0;
     p.A2 = d->A2, p.B2 = d->B2, p.b2_cs = d->b2_cs, p.b2_bs0 = d->b2_bs0, p.b2_bs1 = d->b2_bs1, p.colsum2 = d->colsum2;
     p.a2_rs = d->a2_rs, p.a_unaligned = d->a_unaligned;
@@ -485,16 +572,14 @@ extern "C" int a3t_gemm(const a3t_gemm_desc* d, void* stream_) {
     const bool AK = (d->a_cs == 1), BKC = (d->b_cs == 1);
     if (!AK && d->a_rs != 1) return A3T_EINVAL;
     if (!BKC && d->b_rs != 1) return A3T_EINVAL;
-    if (p.taps > 1 && !AK) {  // fused conv weight gradient: only the direct-to-LDS bf16 kernel implements it
+    p.tiles_n = (p.N + 127) / 128;
+    if (p.taps > 1 && !AK) {  // fused conv weight gradient: only the direct-to-LDS bf16 kernels implement it
         if (d->compute != A3T_BF16 || d->a_dtype != A3T_BF16 || d->b_dtype != A3T_BF16 || d->b_cs == 1 || p.a_signmask || p.A2) return A3T_EINVAL;
-        p.tiles_n = (p.N + 127) / 128;
-        int rc = a3t_gemm_bf16_glds(p, batch, false, false, stream);
-        return rc >= 0 ? rc : A3T_EINVAL;
+        return glds_routes(p, batch, false, false, pl) ? 0 : A3T_EINVAL;
     }
     if (!AK && BKC) return A3T_EINVAL;         // (TT layout is never needed on this path)
-    p.tiles_n = (p.N + 127) / 128;
     const int tiles_m = (p.M + 127) / 128;
-    dim3 grid((unsigned)(p.tiles_n * tiles_m), (unsigned)(batch * p.splitk)), block(256);
+    const dim3 grid((unsigned)(p.tiles_n * tiles_m), (unsigned)(batch * p.splitk));
 
     if (d->compute == A3T_F32) {
         if (d->a_dtype != A3T_F32 || d->b_dtype != A3T_F32 || d->colsum || p.a_signmask || p.A2) return A3T_EINVAL;
@@ -507,64 +592,95 @@ extern "C" int a3t_gemm(const a3t_gemm_desc* d, void* stream_) {
             vec = vec && m4(p.b_rs, 4) && m4(p.K, 4) && m4(p.Kc, 4) && m4(p.b_ts, 4);
         else
             vec = vec && m4(p.b_cs, 4) && m4(p.b_ts, 4);
-#define LAUNCH_F32(ak, bk)                                                                    \
-    do {                                                                                      \
-        if (vec)                                                                              \
-            hipLaunchKernelGGL((gemm_f32_kernel<ak, bk, true>), grid, block, 0, stream, p);   \
-        else                                                                                  \
-            hipLaunchKernelGGL((gemm_f32_kernel<ak, bk, false>), grid, block, 0, stream, p);  \
-    } while (0)
-        if (AK && BKC)
-            LAUNCH_F32(true, true);
-        else if (AK && !BKC)
-            LAUNCH_F32(true, false);
-        else
-            LAUNCH_F32(false, false);
-#undef LAUNCH_F32
-        a3t_note_kernel("gemm_f32_kernel<%s, %s, %s>", AK ? "true" : "false", BKC ? "true" : "false", vec ? "true" : "false");
-        return (int)hipGetLastError();
+        pl->route = GR_F32, pl->ak = AK, pl->bkc = BKC, pl->vec = vec, pl->grid = grid;
+        snprintf(pl->name, sizeof(pl->name), "gemm_f32_kernel<%s, %s, %s>", tf(AK), tf(BKC), tf(vec));
+        return 0;
     }
     if (d->compute != A3T_BF16) return A3T_EINVAL;
-    if (d->a_dtype == A3T_BF16 && d->b_dtype == A3T_BF16) {
-        int rc = a3t_gemm_bf16_glds(p, batch, AK, BKC, stream);   // direct-to-LDS production kernel
-        if (rc >= 0) return rc;                                   // -1: alignment contract not met
-    }
+    if (d->a_dtype == A3T_BF16 && d->b_dtype == A3T_BF16 && glds_routes(p, batch, AK, BKC, pl)) return 0;
     if (keep || p.a_signmask || p.A2 || p.a_unaligned) return A3T_EINVAL;        // keep-bit images only exist in the 8-phase kernel, sign masks in the direct-to-LDS TN kernels
     if (d->colsum) return A3T_EINVAL;   // fused column sums live in the direct-to-LDS kernel's epilogue
-    {
-        const int ea = d->a_dtype == A3T_BF16 ? 2 : 4, eb = d->b_dtype == A3T_BF16 ? 2 : 4;
-        bool ok = al(p.A, 16) && al(p.B, 16);
-        // k-contiguous operands are read in chunks of 8 elements, row-contiguous in chunks of 4
-        if (AK)
-            ok = ok && m4(p.a_rs, 8) && m4(p.K, 8) && m4(p.Kc, 8) && m4(p.a_bs0, 8) && m4(p.a_bs1, 8);
-        else
-            ok = ok && m4(p.a_cs, 4) && m4(p.a_bs0, 4) && m4(p.a_bs1, 4);
-        if (BKC)
-            ok = ok && m4(p.b_rs, 8) && m4(p.K, 8) && m4(p.Kc, 8) && m4(p.b_ts, 8) && m4(p.b_bs0, 8) && m4(p.b_bs1, 8);
-        else
-            ok = ok && m4(p.b_cs, 4) && m4(p.b_ts, 4) && m4(p.b_bs0, 4) && m4(p.b_bs1, 4);
-        (void)ea, (void)eb;
-        if (!ok) return A3T_EINVAL;
-    }
-#define LAUNCH_BF(TA, TB)                                                                              \
-    do {                                                                                               \
-        if (AK && BKC)                                                                                 \
-            hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, true, true>), grid, block, 0, stream, p);     \
-        else if (AK && !BKC)                                                                           \
-            hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, true, false>), grid, block, 0, stream, p);    \
-        else                                                                                           \
-            hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, false, false>), grid, block, 0, stream, p);   \
+    // the legacy register-staged kernel: k-contiguous operands are read in chunks of 8 elements, row-contiguous in chunks of 4
+    bool ok = al(p.A, 16) && al(p.B, 16);
+    if (AK)
+        ok = ok && m4(p.a_rs, 8) && m4(p.K, 8) && m4(p.Kc, 8) && m4(p.a_bs0, 8) && m4(p.a_bs1, 8);
+    else
+        ok = ok && m4(p.a_cs, 4) && m4(p.a_bs0, 4) && m4(p.a_bs1, 4);
+    if (BKC)
+        ok = ok && m4(p.b_rs, 8) && m4(p.K, 8) && m4(p.Kc, 8) && m4(p.b_ts, 8) && m4(p.b_bs0, 8) && m4(p.b_bs1, 8);
+    else
+        ok = ok && m4(p.b_cs, 4) && m4(p.b_ts, 4) && m4(p.b_bs0, 4) && m4(p.b_bs1, 4);
+    if (!ok) return A3T_EINVAL;
+    pl->route = GR_BF16_LEGACY, pl->ak = AK, pl->bkc = BKC, pl->grid = grid;
+    pl->a_f32 = d->a_dtype == A3T_F32, pl->b_f32 = d->b_dtype == A3T_F32;
+    snprintf(pl->name, sizeof(pl->name), "gemm_bf16_kernel<%s, %s, %s, %s>", pl->a_f32 ? "float" : "unsigned short",
+             pl->b_f32 ? "float" : "unsigned short", tf(AK), tf(BKC));
+    return 0;
+}
+
+static int f32_launch(const GP& p, const GemmPlan& pl, hipStream_t stream) {
+#define LAUNCH_F32(ak, bk)                                                                          \
+    do {                                                                                            \
+        if (pl.vec)                                                                                 \
+            hipLaunchKernelGGL((gemm_f32_kernel<ak, bk, true>), pl.grid, dim3(256), 0, stream, p);  \
+        else                                                                                        \
+            hipLaunchKernelGGL((gemm_f32_kernel<ak, bk, false>), pl.grid, dim3(256), 0, stream, p); \
     } while (0)
-    if (d->a_dtype == A3T_F32 && d->b_dtype == A3T_F32)
+    if (pl.ak && pl.bkc)
+        LAUNCH_F32(true, true);
+    else if (pl.ak)
+        LAUNCH_F32(true, false);
+    else
+        LAUNCH_F32(false, false);
+#undef LAUNCH_F32
+    return (int)hipGetLastError();
+}
+
+static int legacy_launch(const GP& p, const GemmPlan& pl, hipStream_t stream) {
+#define LAUNCH_BF(TA, TB)                                                                                   \
+    do {                                                                                                    \
+        if (pl.ak && pl.bkc)                                                                                \
+            hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, true, true>), pl.grid, dim3(256), 0, stream, p);   \
+        else if (pl.ak)                                                                                     \
+            hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, true, false>), pl.grid, dim3(256), 0, stream, p);  \
+        else                                                                                                \
+            hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, false, false>), pl.grid, dim3(256), 0, stream, p); \
+    } while (0)
+    if (pl.a_f32 && pl.b_f32)
         LAUNCH_BF(float, float);
-    else if (d->a_dtype == A3T_F32 && d->b_dtype == A3T_BF16)
+    else if (pl.a_f32)
         LAUNCH_BF(float, unsigned short);
-    else if (d->a_dtype == A3T_BF16 && d->b_dtype == A3T_F32)
+    else if (pl.b_f32)
         LAUNCH_BF(unsigned short, float);
     else
         LAUNCH_BF(unsigned short, unsigned short);
 #undef LAUNCH_BF
-    a3t_note_kernel("gemm_bf16_kernel<%s, %s, %s, %s>", d->a_dtype == A3T_F32 ? "float" : "unsigned short",
-                    d->b_dtype == A3T_F32 ? "float" : "unsigned short", AK ? "true" : "false", BKC ? "true" : "false");
     return (int)hipGetLastError();
+}
+
+extern "C" int a3t_gemm(const a3t_gemm_desc* d, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GP p;
+    GemmPlan pl;
+    const int rc = gemm_plan(d, &p, &pl);
+    if (rc) return rc;
+    int r;
+    switch (pl.route) {
+        case GR_F32: r = f32_launch(p, pl, stream); break;
+        case GR_BF16_LEGACY: r = legacy_launch(p, pl, stream); break;
+        case GR_GLDS_128: r = glds_launch(p, pl, stream); break;
+        case GR_PN: r = pn_launch(p, pl, stream); break;
+        case GR_TT: r = tt_launch(p, pl, stream); break;
+        default: r = g8_launch(p, pl, stream); break;   // GR_G8, GR_G8_TN, GR_G8_TN3
+    }
+    a3t_note_kernel(pl.name);
+    return r;
+}
+
+extern "C" int a3t_gemm_plan(const a3t_gemm_desc* d, char* name, int len) {
+    GP p;
+    GemmPlan pl;
+    const int rc = gemm_plan(d, &p, &pl);
+    if (!rc && name && len > 0) snprintf(name, (size_t)len, "%s", pl.name);
+    return rc;
 }

@@ -34,8 +34,6 @@ __device__ __attribute__((aligned(16))) unsigned int a3t_zero_page[16];
 #define LDS_AS(p) ((__attribute__((address_space(3))) void*)(p))
 #define GLB_AS(p) ((const __attribute__((address_space(1))) void*)(p))
 
-enum { L_NT = 0, L_NN = 1, L_TN = 2 };
-
 // -DGLDS_TIMING (A3T_EXTRA_FLAGS): per-workgroup phase times of the single-buffer K loop (round-2 tool, see profiles/NOTEBOOK_r01_r03.md)
 #ifdef GLDS_TIMING
 __device__ unsigned long long glds_dbg[16384 * 8];
@@ -455,13 +453,6 @@ __global__ __launch_bounds__(128 * WM, (WN == 3 ? (STAGES == 2 ? 2 : 3) : (STAGE
     if (WN == 3) panel(std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{});
 }
 
-static inline bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-static inline bool m8(int64_t v) { return (v % 8) == 0; }
-
-int a3t_gemm_bf16_8p(const GP& p, int batch, int ly, hipStream_t stream);   // gemm_bf16_8p.hip
-int a3t_gemm_bf16_pn(const GP& p, int batch, int ly, hipStream_t stream);   // gemm_bf16_pn.hip
-int a3t_gemm_bf16_tt(const GP& p, int batch, int ly, hipStream_t stream);   // gemm_bf16_tt.hip
-
 template <int LY, int ST, int WM, int CV, int WN = 2>
 static void launch_variant(const GP& pv, dim3 grid, hipStream_t stream) {
     constexpr int lds = ST * (64 * WM + 64 * WN) * 64 * 2;
@@ -470,93 +461,46 @@ static void launch_variant(const GP& pv, dim3 grid, hipStream_t stream) {
     hipLaunchKernelGGL((gemm_bf16_glds_kernel<LY, ST, WM, CV, WN>), grid, dim3(128 * WM), lds, stream, pv);
 }
 
-// returns -1 when the descriptor does not meet the alignment contract of this kernel
-int a3t_gemm_bf16_glds(const GP& p, int batch, bool AK, bool BKC, hipStream_t stream) {
-    const bool aview = (p.a_unaligned & 1) != 0;     // A: a 2-byte aligned strided view (the loaders only do pointer arithmetic)
-    bool ok = (aview || al16(p.A)) && al16(p.B) && m8(p.a_bs0) && m8(p.a_bs1) && m8(p.b_bs0) && m8(p.b_bs1);
-    if (AK || BKC) ok = ok && m8(p.Kc);      // (16-byte granules run along k only for k-contiguous operands)
-    if (AK)
-        ok = ok && (aview || m8(p.a_rs)) && m8(p.K);
-    else
-        ok = ok && (aview || m8(p.a_cs)) && m8(p.M);
-    if (BKC)
-        ok = ok && m8(p.b_rs) && m8(p.K) && m8(p.b_ts);
-    else
-        ok = ok && m8(p.b_cs) && m8(p.b_ts) && m8(p.N);
-    if (!AK && p.taps > 1) ok = ok && ((p.N / p.taps) % 128 == 0) && (p.N % p.taps == 0) && p.Tseq > 0;
-    if (!ok) return -1;
-    GP pv = p;
-    if (p.colsum && (p.accumulate == A3T_ACC_ATOMIC)) return -1;
-    // vector epilogue contract: 4-column groups never straddle N and every C/R/S/bias access is aligned
-    pv.epi_vec = (p.N % 4 == 0) && (p.c_rs % 4 == 0) && (p.c_bs0 % 4 == 0) && (p.c_bs1 % 4 == 0) &&
-                 al16(p.C) && (!p.R || al16(p.R)) && (!p.S || ((uintptr_t)p.S & 7) == 0) && (!p.bias || al16(p.bias));
-    if (p.colsum && !pv.epi_vec) return -1;
-
-    const bool keep_rm = p.keep_layout == 1 && (p.keep_in || p.keep_out);      // row-major nibble image: vector epilogue / panel kernel
-    if (keep_rm && (!pv.epi_vec || p.c_rs != p.N || batch != 1 || p.splitk != 1 || p.accumulate != A3T_ACC_STORE || p.N % 8 ||
-                    (p.keep_out && p.R) || (p.keep_in && p.S)))
-        return A3T_EINVAL;
-    if (p.a_signmask && (AK || BKC || p.taps > 1 || p.kshift_mode)) return -1;   // (fragment-register pass of the m-contiguous A only)
-    if (!(pv.keep_out || (pv.keep_in && !keep_rm) || p.a_signmask || p.A2 || aview)) {   // N = 384 outputs: one 160-row panel x all columns per workgroup (-1: does not qualify)
-        const int rc = a3t_gemm_bf16_pn(pv, batch, (AK && BKC) ? L_NT : (AK ? L_NN : L_TN), stream);
-        if (rc != -1) return rc;
-    }
-    if (!p.a_signmask && !keep_rm && !p.A2 && !aview) {   // many-tile k-contiguous GEMMs: persistent 256x256 8-phase kernel (returns -1 when the problem does not qualify)
-        const int rc = a3t_gemm_bf16_8p(pv, batch, (AK && BKC) ? L_NT : (AK ? L_NN : L_TN), stream);
-        if (rc != -1) return rc;
-    }
-    if (!BKC && !(pv.keep_in || pv.keep_out) && !aview) {   // score-sized A operand x [k][n] slices (attention backward): one streaming workgroup per CU
-        const int rc = a3t_gemm_bf16_tt(pv, batch, AK ? L_NN : L_TN, stream);
-        if (rc != -1) return rc;
-    }
-    if (p.A2) return A3T_EINVAL;        // two products in one launch: the streaming kernel only (ask a3t_gemm_tt_supported first)
-    static int forced_st = -1;
-    if (forced_st < 0) {
-        const char* e = getenv("A3T_GEMM_STAGES");
-        forced_st = e ? (e[0] == '1' ? 1 : 2) : 0;
-    }
-    // Variant choice (measured on MI355X, tools/gemm_bench*.py): single LDS buffer + 3-4 co-resident workgroups per CU
-    // when the grid is large, double buffering inside the workgroup when it is small.  (A 256-row tile, WM = 4, moves
-    // 25 % fewer DMA bytes per flop but halves the co-resident workgroups; it lost 5-40 % on every shape but one and
-    // that one is now faster on the 4-per-CU 128-row variant, so only WM = 2 is instantiated.)
+// The last route of the direct-to-LDS family: every descriptor that meets the alignment contract and reaches it runs here.
+// Variant choice (measured on MI355X, tools/gemm_bench*.py): single LDS buffer + 3-4 co-resident workgroups per CU
+// when the grid is large, double buffering inside the workgroup when it is small.  (A 256-row tile, WM = 4, moves
+// 25 % fewer DMA bytes per flop but halves the co-resident workgroups; it lost 5-40 % on every shape but one and
+// that one is now faster on the 4-per-CU 128-row variant, so only WM = 2 is instantiated.)
+void glds_plan(const GP& p, int batch, int ly, GemmPlan* pl) {
     constexpr int wm = 2;
-    const int ly = (AK && BKC) ? L_NT : (AK ? L_NN : L_TN);
     int conv = 0;
     if (p.taps > 1 || p.kshift_mode)
         conv = (p.taps > 1 && ly != L_TN && p.Kc % 64 == 0 && p.K % 64 == 0 && (ly != L_NT || p.b_ts == p.Kc)) ? 1 : 2;
     // 192-column tiles when they waste clearly fewer padded columns than 128-column tiles (N = 192: 0 vs 33 %)
-    static int wn_mode = -1;
-    if (wn_mode < 0) {
-        const char* e = getenv("A3T_GEMM_WN3");
-        wn_mode = e ? (e[0] == '0' ? 0 : 2) : 1;
-    }
+    const int wn_mode = gemm_switch(SW_WN3);
     const long pad128 = (long)((p.N + 127) / 128) * 128, pad192 = (long)((p.N + 191) / 192) * 192;
-    const bool wn3 = conv == 0 && pv.epi_vec && p.accumulate != A3T_ACC_ATOMIC && wn_mode != 0 && (wn_mode == 2 || pad192 * 10 <= pad128 * 8);
-    pv.tiles_n = wn3 ? (p.N + 191) / 192 : (p.N + 127) / 128;
-    const int tiles_m = (p.M + 64 * wm - 1) / (64 * wm);
-    const long tiles = (long)pv.tiles_n * tiles_m * batch * p.splitk;
-    const int stages = forced_st ? forced_st : (tiles >= (wn3 ? 512 : 768) ? 1 : 2);
-    pv.ntiles = pv.tiles_n * tiles_m;
-    dim3 grid((unsigned)((long)pv.ntiles * batch * p.splitk));
-    if (wn3) {
-#define V3(LY, ST)                                             \
-    if (ly == LY && stages == ST) {                            \
-        launch_variant<LY, ST, 2, 0, 3>(pv, grid, stream);     \
-        a3t_note_kernel("gemm_bf16_glds_kernel<%d, %d, 2, 0, 3>", LY, ST); \
-        return (int)hipGetLastError();                         \
-    }
+    const bool wn3 = conv == 0 && p.epi_vec && p.accumulate != A3T_ACC_ATOMIC && wn_mode != 0 && (wn_mode == 2 || pad192 * 10 <= pad128 * 8);
+    const int tiles_n = wn3 ? (p.N + 191) / 192 : (p.N + 127) / 128, tiles_m = (p.M + 64 * wm - 1) / (64 * wm);
+    const long tiles = (long)tiles_n * tiles_m * batch * p.splitk;
+    const int forced_st = gemm_switch(SW_STAGES);
+    pl->route = GR_GLDS_128, pl->ly = ly, pl->conv = conv, pl->wn = wn3 ? 3 : 2;
+    pl->stages = forced_st ? forced_st : (tiles >= (wn3 ? 512 : 768) ? 1 : 2);
+    pl->tiles_n = tiles_n, pl->ntiles = tiles_n * tiles_m;
+    pl->grid = dim3((unsigned)((long)pl->ntiles * batch * p.splitk));
+    snprintf(pl->name, sizeof(pl->name), "gemm_bf16_glds_kernel<%d, %d, %d, %d, %d>", ly, pl->stages, wm, conv, pl->wn);
+}
+
+int glds_launch(const GP& p, const GemmPlan& pl, hipStream_t stream) {
+    GP pv = p;
+    pv.tiles_n = pl.tiles_n, pv.ntiles = pl.ntiles;
+    const int ly = pl.ly, st = pl.stages, cv = pl.conv;
+    if (pl.wn == 3) {
+#define V3(LY, ST) \
+    if (ly == LY && st == ST) launch_variant<LY, ST, 2, 0, 3>(pv, pl.grid, stream);
         V3(L_NT, 1) V3(L_NT, 2) V3(L_NN, 1) V3(L_NN, 2) V3(L_TN, 1) V3(L_TN, 2)
 #undef V3
-    }
-#define V(LY, ST, WM_, CV)                                   \
-    if (ly == LY && stages == ST && wm == WM_ && conv == CV) { \
-        launch_variant<LY, ST, WM_, CV>(pv, grid, stream);     \
-        a3t_note_kernel("gemm_bf16_glds_kernel<%d, %d, %d, %d, 2>", LY, ST, WM_, CV); \
-        return (int)hipGetLastError();                         \
-    }
-    V(L_NT, 1, 2, 0) V(L_NT, 2, 2, 0) V(L_NT, 1, 2, 1) V(L_NT, 2, 2, 1) V(L_NT, 1, 2, 2) V(L_NT, 2, 2, 2)
-    V(L_NN, 1, 2, 0) V(L_NN, 2, 2, 0) V(L_NN, 1, 2, 1) V(L_NN, 2, 2, 1) V(L_NN, 1, 2, 2) V(L_NN, 2, 2, 2)
-    V(L_TN, 1, 2, 0) V(L_TN, 2, 2, 0) V(L_TN, 1, 2, 2) V(L_TN, 2, 2, 2)
+    } else {
+#define V(LY, ST, CV) \
+    if (ly == LY && st == ST && cv == CV) launch_variant<LY, ST, 2, CV>(pv, pl.grid, stream);
+        V(L_NT, 1, 0) V(L_NT, 2, 0) V(L_NT, 1, 1) V(L_NT, 2, 1) V(L_NT, 1, 2) V(L_NT, 2, 2)
+        V(L_NN, 1, 0) V(L_NN, 2, 0) V(L_NN, 1, 1) V(L_NN, 2, 1) V(L_NN, 1, 2) V(L_NN, 2, 2)
+        V(L_TN, 1, 0) V(L_TN, 2, 0) V(L_TN, 1, 2) V(L_TN, 2, 2)
 #undef V
-    return A3T_EINVAL;
+    }
+    return (int)hipGetLastError();
 }

@@ -1139,45 +1139,34 @@ extern "C" int a3t_release_workspaces(void) {
     return 0;
 }
 
-static int g8_cus() {          // per device (a process may drive several GPUs)
-    static int n[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!n[dev]) {
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-        n[dev] = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-    }
-    return n[dev];
-}
-
 template <bool CV>
 static void launch_8p(const GP& pv, int grid, hipStream_t stream) {
     (void)hipFuncSetAttribute((const void*)gemm_bf16_8p_kernel<CV>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
     hipLaunchKernelGGL((gemm_bf16_8p_kernel<CV>), dim3(grid), dim3(512), LDS_TOTAL, stream, pv);
 }
 
-// mode: 0 never, 1 whenever legal, 2 heuristic (default); A3T_GEMM_8P or a3t_gemm_8p_mode()
-static int g_8p_mode = -1;
-static int g8_mode() {
-    if (g_8p_mode < 0) {
-        const char* e = getenv("A3T_GEMM_8P");
-        g_8p_mode = e ? atoi(e) : 2;
-    }
-    return g_8p_mode;
-}
-extern "C" int a3t_gemm_8p_mode(int mode) {
-    const int old = g8_mode();
-    g_8p_mode = mode;
-    return old;
-}
 extern "C" int64_t a3t_gemm_keep_bytes(int M, int N) { return (int64_t)((M + 255) / 256) * ((N + 255) / 256) * 8192; }
 
-// Is the 8-phase kernel the one a3t_gemm picks for this problem?  (The engine asks before it chooses the keep-bit
-// protocol: both GEMMs of a pair must agree.)
-static bool g8_applicable(const GP& p, int batch, int ly, bool keep) {
-    const int mode = g8_mode();
-    if (mode == 0 || ly != 0 || batch != 1 || p.splitk != 1 || p.accumulate != A3T_ACC_STORE) return false;
+// K splits of a token-reduction grid of `tiles` output tiles over nkt 64-wide K-tiles: fill the chip, >= 16 K-tiles per workgroup.
+// folds: the splits that get K-tiles as the kernels deal them out (an even number each; later splits write nothing) = the fold's splitk.
+static void g8_split_k(long tiles, int nkt, int& splits, int& folds) {
+    splits = (int)(gemm_cus() / tiles);
+    if (splits < 1) splits = 1;
+    if (splits > nkt / 16) splits = nkt / 16 > 0 ? nkt / 16 : 1;
+    int per = (nkt + splits - 1) / splits;
+    per += per & 1;
+    folds = (nkt + per - 1) / per;
+}
+
+// Is an 8-phase kernel the one a3t_gemm picks for this problem?  ly L_NT: the persistent 256 x 256 kernel (the engine asks through
+// a3t_gemm_8p_supported before it chooses the keep-bit protocol: both GEMMs of a pair must agree); L_TN: the token reductions
+// (g8_tn_plan, no keep bits).  mode (A3T_GEMM_8P, a3t_gemm_8p_mode): 0 never, 1 whenever legal, 2 (default) the cost model.
+static bool g8_tn_plan(const GP& p, int batch, GemmPlan* pl);
+bool g8_plan(const GP& p, int batch, int ly, GemmPlan* pl) {
+    const bool keep = p.keep_in || p.keep_out;
+    if (ly == L_TN) return !keep && g8_tn_plan(p, batch, pl);
+    const int mode = gemm_switch(SW_8P);
+    if (mode == 0 || ly != L_NT || batch != 1 || p.splitk != 1 || p.accumulate != A3T_ACC_STORE) return false;
     if (p.K % 128 != 0 || p.N % 8 != 0 || p.c_rs % 8 != 0 || p.a_cs != 1 || p.b_cs != 1) return false;
     if (p.S || p.kshift_mode) return false;
     if (p.R && (((uintptr_t)p.R & 15) || p.keep_out)) return false;
@@ -1189,6 +1178,8 @@ static bool g8_applicable(const GP& p, int batch, int ly, bool keep) {
     const int64_t a_bytes = ((int64_t)p.M * p.a_rs) * 2, b_bytes = ((int64_t)p.N * p.b_rs) * 2;
     if (a_bytes >= (1ll << 31) || b_bytes >= (1ll << 31) || (int64_t)p.M * p.c_rs >= (1ll << 32)) return false;
     if (keep && (p.N % 256 != 0)) return false;
+    const long tm = (p.M + 255) / 256, tn = (p.N + 255) / 256, tiles = tm * tn;
+    const int cus = gemm_cus();
     if (mode == 2) {
         // Cost model fitted on MI355X (round 3: profiles/r03_g8_check.txt, r03_g8_c4_shapes.txt): one 128-KiB workgroup per CU runs its K loop
         // at ~1.65 us per 64-wide K-tile (1.3 PFLOP/s) but nothing overlaps a tile's fixed costs -- pipeline refill and
@@ -1196,8 +1187,6 @@ static bool g8_applicable(const GP& p, int batch, int ly, bool keep) {
         // filled last round of the grid; the 128x128 kernel (4 workgroups per CU, epilogues hidden behind its neighbours)
         // sustains ~780 TFLOP/s on the same problems.  It wins for long K and grids that fill their rounds: configs[3]'s
         // d=512 / ff=2048 FFN (+8 % and +28 %), not configs[1]'s N=1536, K=1152 convs (4 rounds for 3.28, 18 K-tiles: -8 %).
-        const long tm = (p.M + 255) / 256, tn = (p.N + 255) / 256, tiles = tm * tn;
-        const int cus = g8_cus();
         const double rounds = (double)((tiles + cus - 1) / cus);
         double fixed = 7.0;
         if (p.bias || p.act != A3T_ACT_NONE) fixed += 1.5;
@@ -1209,22 +1198,16 @@ static bool g8_applicable(const GP& p, int batch, int ly, bool keep) {
         const double t128 = 2.0 * p.M * p.N * (double)p.K / 780e6;     // us
         if (tiles < cus / 2 || t8 > 0.95 * t128) return false;
     }
+    pl->route = GR_G8, pl->cv = p.taps > 1, pl->tiles_n = (int)tn, pl->ntiles = (int)tiles;
+    pl->grid = dim3((unsigned)(tiles < cus ? tiles : cus));
+    snprintf(pl->name, sizeof(pl->name), "gemm_bf16_8p_kernel<%s>", tf(pl->cv));
     return true;
 }
 
-// flags: 1 bias / activation, 2 dropout, 4 keep bits out, 8 keep bits in, 16 fp32 output / residual, 32 column sums
+// flags as for gemm_rep, keep_in (8) as the tile-major bit image
 extern "C" int a3t_gemm_8p_supported(int M, int N, int K, int taps, int flags) {
-    static float dummy[4] __attribute__((aligned(16)));
-    GP p = {};
-    p.M = M, p.N = N, p.K = K, p.taps = taps < 1 ? 1 : taps, p.Kc = K / p.taps, p.b_ts = p.Kc;
-    p.a_rs = p.Kc, p.a_cs = 1, p.b_rs = K, p.b_cs = 1, p.c_rs = N, p.splitk = 1, p.accumulate = A3T_ACC_STORE;
-    p.Tseq = 1, p.colsum_slots = 1, p.c_dtype = (flags & 16) ? A3T_F32 : A3T_BF16;
-    if (flags & 1) p.bias = dummy, p.act = A3T_ACT_RELU;
-    if (flags & 2) p.drop_inv = 1.25f;
-    if (flags & 4) p.keep_out = (unsigned char*)dummy;
-    if (flags & 8) p.keep_in = (const unsigned char*)dummy;
-    if (flags & 32) p.colsum = dummy;
-    return g8_applicable(p, 1, 0, (flags & 12) != 0) ? 1 : 0;
+    GemmPlan pl;
+    return g8_plan(gemm_rep(M, N, K, taps, flags, 0), 1, L_NT, &pl) ? 1 : 0;
 }
 
 template <bool WGF>
@@ -1239,51 +1222,103 @@ static void launch_8p_tn3(const GP& pv, const TN3Group& grp, int grid, hipStream
     hipLaunchKernelGGL((gemm_bf16_8p_tn3_kernel<WGF>), dim3(grid), dim3(512), 2 * TILE_BYTES, stream, pv, grp);
 }
 
-// 128 x 384 tiles (gemm_bf16_8p_tn3_kernel): -1 = not applicable / not chosen.  A3T_GEMM_8P_TN3 = 0 never, 1 whenever legal,
-// 2 (default) when the tiles fit the output exactly enough and there is enough K per workgroup.
-static int g_tn3_mode = -1;
-static int tn3_mode() {
-    if (g_tn3_mode < 0) {
-        const char* e = getenv("A3T_GEMM_8P_TN3");
-        g_tn3_mode = e ? atoi(e) : 2;
-    }
-    return g_tn3_mode;
-}
-extern "C" int a3t_gemm_tn3_mode(int mode) {
-    const int old = tn3_mode();
-    g_tn3_mode = mode;
-    return old;
-}
-static int gemm_8p_tn3(const GP& p, hipStream_t stream, int64_t a_bytes, int64_t b_bytes) {
-    const int on = tn3_mode();
-    if (on == 0) return -1;
+// 128 x 384 tiles (gemm_bf16_8p_tn3_kernel), asked by g8_tn_plan under A3T_GEMM_8P_TN3 = 1 (whenever legal) or 2 (default: when
+// the tiles fit the output exactly enough and there is enough K per workgroup).
+static bool g8_tn3_plan(const GP& p, GemmPlan* pl) {
     const long tm = (p.M + 127) / 128, tn = (p.N + 383) / 384, tiles = tm * tn;
-    const int cus = g8_cus(), nkt = (p.K + 63) / 64;
-    int splits = (int)(cus / tiles);
-    if (splits < 1) splits = 1;
-    if (splits > nkt / 16) splits = nkt / 16 > 0 ? nkt / 16 : 1;       // >= 16 K-tiles per workgroup
-    if (on == 2) {
+    int splits, folds;
+    g8_split_k(tiles, (p.K + 63) / 64, splits, folds);
+    if (gemm_switch(SW_8P_TN3) == 2) {
         const double fill = (double)p.M * p.N / ((double)tm * 128 * tn * 384);
-        if (fill < 0.85 || tiles * splits < 96) return -1;
+        if (fill < 0.85 || tiles * splits < 96) return false;
     }
-    int per = (nkt + splits - 1) / splits;
-    per += per & 1;
-    GP pv = p;
-    pv.tiles_n = (int)tn, pv.ntiles = (int)tiles, pv.splitk = splits;
-    pv.a_bytes = (unsigned)a_bytes, pv.b_bytes = (unsigned)b_bytes;
-    pv.slab = g8_slab(stream, (size_t)tiles * splits * 49152 * sizeof(float));
-    if (!pv.slab) return (int)hipErrorOutOfMemory;
+    pl->route = GR_G8_TN3, pl->cv = p.taps > 1, pl->tiles_n = (int)tn, pl->ntiles = (int)tiles;
+    pl->splits = splits, pl->folds = folds, pl->grid = dim3((unsigned)(tiles * splits));
+    pl->slab_floats = (size_t)tiles * splits * 49152;
+    snprintf(pl->name, sizeof(pl->name), "gemm_bf16_8p_tn3_kernel<%s>", tf(pl->cv));
+    return true;
+}
+
+// weight gradients: reduction-strided operands, K (tokens) split over workgroups
+static bool g8_tn_plan(const GP& p, int batch, GemmPlan* pl) {
+    // Its K loop runs 1.55 us per K-tile (1.39 PFLOP/s) but the ~240 workgroups of a split-K grid finish together and their
+    // 15.7 M fp32 atomics cost 20-35 us with nothing to hide them behind, and a 128-KiB / 496-register workgroup shares its CU
+    // with nobody (the 128x128 weight-gradient kernel runs beside the main stream's kernels).  configs[1]'s FFN weight
+    // gradients: 153 / 165 us against 170 / 171 us alone, +1 ms per step inside the step; configs[3]'s (K = 28800, 90 K-tiles per
+    // workgroup): -1 ms per step.  Hence the margin below.  A3T_GEMM_8P_TN=0 / 1: never / whenever legal.
+    const int mode = gemm_switch(SW_8P), tn_on = gemm_switch(SW_8P_TN);
+    if (mode == 0 || tn_on == 0) return false;
+    if (batch != 1 || p.c_dtype != A3T_F32 || p.M % 8 != 0 || p.N % 8 != 0) return false;
+    if (p.a_rs != 1 || p.b_rs != 1 || p.bias || p.R || p.S || p.colsum || p.act != A3T_ACT_NONE || p.drop_inv > 0.f) return false;
     const bool wg = p.taps > 1;
-    const int grid = (int)(tiles * splits);
-    TN3Group none = {};
-    if (wg)
-        launch_8p_tn3<true>(pv, none, grid, stream);
+    if (wg && ((p.N % p.taps) || ((p.N / p.taps) % 128) || p.Tseq <= 0 || p.Tseq >= 32768)) return false;
+    if (!wg && p.kshift_mode) return false;
+    if (((uintptr_t)p.A | (uintptr_t)p.B | (uintptr_t)p.C) & 15) return false;
+    const int64_t a_bytes = (int64_t)p.K * p.a_cs * 2, b_bytes = (int64_t)p.K * p.b_cs * 2;
+    if (a_bytes >= (1ll << 31) || b_bytes >= (1ll << 31) || p.a_cs % 8 || p.b_cs % 8) return false;
+    const long tm = (p.M + 255) / 256, tn = (p.N + 255) / 256, tiles = tm * tn;
+    const int nkt = (p.K + 63) / 64;
+    int splits, folds;
+    g8_split_k(tiles, nkt, splits, folds);
+    // Which tile: 256 x 256 (four quadrants per K-tile, 1.55 us: the better K loop) when it covers the output exactly --
+    // configs[3]'s 2048 x 1536 / 512 x 6144: 67.97 ms per step against 68.70 on the 128 x 384 tile -- and 128 x 384 (three
+    // quadrants, 1.41 us, 176 registers: leaves the CU's other wave slots to the main stream's kernels) where 256 x 256 tiles
+    // would be partly empty -- configs[1]'s 1536 x 1152 / 384 x 4608 (fill 0.90 / 0.75): 43.2 ms per step against 44.6.
+    const double fill = (double)p.M * p.N / ((double)tm * 256 * tn * 256);
+    bool ok22 = true;
+    if (mode == 2 && tn_on == 2) {
+        const double t8 = (double)((nkt + splits - 1) / splits) * 1.55 + 25.0;      // us: K loop + prologue, partial stores, fold
+        const double t128 = 2.0 * p.M * p.N * (double)p.K / 680e6;                 // us at the 128x128 kernel's ~680 TFLOP/s
+        ok22 = !(fill < 0.7 || tiles * splits < 160 || nkt / splits < 32 || t8 > 0.7 * t128);
+    }
+    const int t3 = gemm_switch(SW_8P_TN3);
+    if ((t3 == 1 || (t3 == 2 && !(ok22 && fill >= 0.95))) && g8_tn3_plan(p, pl)) return true;
+    if (!ok22) return false;
+    // K splits always leave through the slab + fold (the fp32-atomic epilogue of rounds 3-4 lost by 21 us per launch and left in
+    // round 6; a single split writes C directly in the mode the descriptor asks for)
+    pl->route = GR_G8_TN, pl->cv = wg, pl->tiles_n = (int)tn, pl->ntiles = (int)tiles;
+    pl->splits = splits, pl->folds = folds, pl->grid = dim3((unsigned)(tiles * splits));
+    pl->slab_floats = splits > 1 ? (size_t)tiles * splits * 65536 : 0;
+    snprintf(pl->name, sizeof(pl->name), "gemm_bf16_8p_tn_kernel<%s>", tf(wg));
+    return true;
+}
+
+int g8_launch(const GP& p, const GemmPlan& pl, hipStream_t stream) {
+    GP pv = p;
+    pv.tiles_n = pl.tiles_n, pv.ntiles = pl.ntiles;
+    const int grid = (int)pl.grid.x;
+    if (pl.route != GR_G8) {     // token reductions: K splits leave through the slab and the fold
+        pv.splitk = pl.splits;
+        pv.a_bytes = (unsigned)((int64_t)p.K * p.a_cs * 2), pv.b_bytes = (unsigned)((int64_t)p.K * p.b_cs * 2);
+        pv.slab = nullptr;
+        if (pl.slab_floats) {
+            pv.slab = g8_slab(stream, pl.slab_floats * sizeof(float));
+            if (!pv.slab) return (int)hipErrorOutOfMemory;
+        }
+        GP pf = pv;
+        pf.splitk = pl.folds;
+        if (pl.route == GR_G8_TN3) {
+            TN3Group none = {};
+            if (pl.cv)
+                launch_8p_tn3<true>(pv, none, grid, stream);
+            else
+                launch_8p_tn3<false>(pv, none, grid, stream);
+            hipLaunchKernelGGL(gemm_8p_tn3_fold_kernel, dim3(48, (unsigned)pl.ntiles), dim3(256), 0, stream, pf, none);
+        } else {
+            if (pl.cv)
+                launch_8p_tn<true>(pv, grid, stream);
+            else
+                launch_8p_tn<false>(pv, grid, stream);
+            if (pv.slab) hipLaunchKernelGGL(gemm_8p_tn_fold_kernel, dim3(64, (unsigned)pl.ntiles), dim3(256), 0, stream, pf);
+        }
+        return (int)hipGetLastError();
+    }
+    pv.a_bytes = (unsigned)(((int64_t)p.M * p.a_rs) * 2);
+    pv.b_bytes = (unsigned)(((int64_t)p.N * p.b_rs) * 2);
+    if (pl.cv)
+        launch_8p<true>(pv, grid, stream);
     else
-        launch_8p_tn3<false>(pv, none, grid, stream);
-    GP pf = pv;
-    pf.splitk = (nkt + per - 1) / per;
-    hipLaunchKernelGGL(gemm_8p_tn3_fold_kernel, dim3(48, (unsigned)tiles), dim3(256), 0, stream, pf, none);
-    a3t_note_kernel("gemm_bf16_8p_tn3_kernel<%s>", wg ? "true" : "false");
+        launch_8p<false>(pv, grid, stream);
     return (int)hipGetLastError();
 }
 
@@ -1294,7 +1329,7 @@ static int gemm_8p_tn3(const GP& p, hipStream_t stream, int64_t a_bytes, int64_t
 extern "C" int a3t_gemm_tn3_group(const a3t_gemm_desc* d, int n, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!d || n < 1 || n > 8) return A3T_EINVAL;
-    if (g8_mode() == 0 || tn3_mode() == 0) return -1;
+    if (gemm_switch(SW_8P) == 0 || gemm_switch(SW_8P_TN3) == 0) return -1;
     TN3Group grp = {};
     grp.n = n;
     long tiles = 0;
@@ -1323,116 +1358,21 @@ extern "C" int a3t_gemm_tn3_group(const a3t_gemm_desc* d, int n, void* stream_) 
             const char* ei = ci + ((int64_t)(d[i].M - 1) * d[i].c_rs + d[i].N) * 4, *ej = cj + ((int64_t)(d[j].M - 1) * d[j].c_rs + d[j].N) * 4;
             if (ci < ej && cj < ei) return -1;
         }
-    if (tn3_mode() == 2) {       // partly empty 384-column tiles (input widths that are no multiple of 384) lose to the single launches
+    if (gemm_switch(SW_8P_TN3) == 2) {       // partly empty 384-column tiles (input widths that are no multiple of 384) lose to the single launches
         double out = 0.0;
         for (int i = 0; i < n; ++i) out += (double)d[i].M * d[i].N;
         if (out / ((double)tiles * 128 * 384) < 0.85) return -1;
     }
-    const int cus = g8_cus(), nkt = (K + 63) / 64;
-    int splits = (int)(cus / tiles);
-    if (splits < 1) splits = 1;
-    if (splits > nkt / 16) splits = nkt / 16 > 0 ? nkt / 16 : 1;
-    int per = (nkt + splits - 1) / splits;
-    per += per & 1;
+    int splits, folds;
+    g8_split_k(tiles, (K + 63) / 64, splits, folds);
     GP pv = {};
     pv.K = K, pv.taps = 1, pv.Tseq = 1, pv.ntiles = (int)tiles, pv.splitk = splits, pv.tiles_n = 1;
     pv.slab = g8_slab(stream, (size_t)tiles * splits * 49152 * sizeof(float));
     if (!pv.slab) return (int)hipErrorOutOfMemory;
     launch_8p_tn3<false>(pv, grp, (int)(tiles * splits), stream);
     GP pf = pv;
-    pf.splitk = (nkt + per - 1) / per;
+    pf.splitk = folds;
     hipLaunchKernelGGL(gemm_8p_tn3_fold_kernel, dim3(48, (unsigned)tiles), dim3(256), 0, stream, pf, grp);
     a3t_note_kernel("gemm_bf16_8p_tn3_kernel<false>");
-    return (int)hipGetLastError();
-}
-
-// weight gradients: reduction-strided operands, K (tokens) split over workgroups
-static int gemm_8p_tn(const GP& p, int batch, hipStream_t stream) {
-    // Its K loop runs 1.55 us per K-tile (1.39 PFLOP/s) but the ~240 workgroups of a split-K grid finish together and their
-    // 15.7 M fp32 atomics cost 20-35 us with nothing to hide them behind, and a 128-KiB / 496-register workgroup shares its CU
-    // with nobody (the 128x128 weight-gradient kernel runs beside the main stream's kernels).  configs[1]'s FFN weight
-    // gradients: 153 / 165 us against 170 / 171 us alone, +1 ms per step inside the step; configs[3]'s (K = 28800, 90 K-tiles per
-    // workgroup): -1 ms per step.  Hence the margin below.  A3T_GEMM_8P_TN=0 / 1: never / whenever legal.
-    static int tn_on = -1;
-    if (tn_on < 0) {
-        const char* e = getenv("A3T_GEMM_8P_TN");
-        tn_on = e ? atoi(e) : 2;
-    }
-    const int mode = g8_mode();
-    if (mode == 0 || tn_on == 0) return -1;
-    if (batch != 1 || p.c_dtype != A3T_F32 || p.M % 8 != 0 || p.N % 8 != 0) return -1;
-    if (p.a_rs != 1 || p.b_rs != 1 || p.bias || p.R || p.S || p.colsum || p.act != A3T_ACT_NONE || p.drop_inv > 0.f) return -1;
-    const bool wg = p.taps > 1;
-    if (wg && ((p.N % p.taps) || ((p.N / p.taps) % 128) || p.Tseq <= 0 || p.Tseq >= 32768)) return -1;
-    if (!wg && p.kshift_mode) return -1;
-    if (((uintptr_t)p.A | (uintptr_t)p.B | (uintptr_t)p.C) & 15) return -1;
-    const int64_t a_bytes = (int64_t)p.K * p.a_cs * 2, b_bytes = (int64_t)p.K * p.b_cs * 2;
-    if (a_bytes >= (1ll << 31) || b_bytes >= (1ll << 31) || p.a_cs % 8 || p.b_cs % 8) return -1;
-    const long tm = (p.M + 255) / 256, tn = (p.N + 255) / 256, tiles = tm * tn;
-    const int cus = g8_cus(), nkt = (p.K + 63) / 64;
-    int splits = (int)(cus / tiles);
-    if (splits < 1) splits = 1;
-    if (splits > nkt / 16) splits = nkt / 16 > 0 ? nkt / 16 : 1;       // >= 16 K-tiles per workgroup
-    // Which tile: 256 x 256 (four quadrants per K-tile, 1.55 us: the better K loop) when it covers the output exactly --
-    // configs[3]'s 2048 x 1536 / 512 x 6144: 67.97 ms per step against 68.70 on the 128 x 384 tile -- and 128 x 384 (three
-    // quadrants, 1.41 us, 176 registers: leaves the CU's other wave slots to the main stream's kernels) where 256 x 256 tiles
-    // would be partly empty -- configs[1]'s 1536 x 1152 / 384 x 4608 (fill 0.90 / 0.75): 43.2 ms per step against 44.6.
-    const double fill = (double)p.M * p.N / ((double)tm * 256 * tn * 256);
-    bool ok22 = true;
-    if (mode == 2 && tn_on == 2) {
-        const double t8 = (double)((nkt + splits - 1) / splits) * 1.55 + 25.0;      // us: K loop + prologue, partial stores, fold
-        const double t128 = 2.0 * p.M * p.N * (double)p.K / 680e6;                 // us at the 128x128 kernel's ~680 TFLOP/s
-        ok22 = !(fill < 0.7 || tiles * splits < 160 || nkt / splits < 32 || t8 > 0.7 * t128);
-    }
-    const int t3 = tn3_mode();
-    if (t3 == 1 || (t3 == 2 && !(ok22 && fill >= 0.95))) {
-        const int r3 = gemm_8p_tn3(p, stream, a_bytes, b_bytes);
-        if (r3 != -1) return r3;
-    }
-    if (!ok22) return -1;
-    GP pv = p;
-    pv.tiles_n = (int)tn, pv.ntiles = (int)tiles, pv.splitk = splits;
-    pv.a_bytes = (unsigned)a_bytes, pv.b_bytes = (unsigned)b_bytes;
-    pv.slab = nullptr;
-    // K splits always leave through the slab + fold (the fp32-atomic epilogue of rounds 3-4 lost by 21 us per launch and left in
-    // round 6; a single split writes C directly in the mode the descriptor asks for)
-    if (splits > 1) {
-        pv.slab = g8_slab(stream, (size_t)tiles * splits * 65536 * sizeof(float));
-        if (!pv.slab) return (int)hipErrorOutOfMemory;
-    }
-    const int grid = (int)(tiles * splits);
-    if (wg)
-        launch_8p_tn<true>(pv, grid, stream);
-    else
-        launch_8p_tn<false>(pv, grid, stream);
-    if (pv.slab) {
-        int per = (nkt + splits - 1) / splits;       // as the kernel computes it: splits past the last K-tile write nothing
-        per += per & 1;
-        GP pf = pv;
-        pf.splitk = (nkt + per - 1) / per;
-        hipLaunchKernelGGL(gemm_8p_tn_fold_kernel, dim3(64, (unsigned)tiles), dim3(256), 0, stream, pf);
-    }
-    a3t_note_kernel("gemm_bf16_8p_tn_kernel<%s>", wg ? "true" : "false");
-    return (int)hipGetLastError();
-}
-
-// Called by a3t_gemm_bf16_glds after the alignment contract has been checked.  Returns -1 when not applicable.
-int a3t_gemm_bf16_8p(const GP& p, int batch, int ly, hipStream_t stream) {
-    if (ly == 2) return (p.keep_in || p.keep_out) ? A3T_EINVAL : gemm_8p_tn(p, batch, stream);
-    const bool keep = p.keep_in || p.keep_out;
-    if (!g8_applicable(p, batch, ly, keep)) return keep ? A3T_EINVAL : -1;
-    GP pv = p;
-    const long tm = (p.M + 255) / 256, tn = (p.N + 255) / 256;
-    pv.tiles_n = (int)tn;
-    pv.ntiles = (int)(tm * tn);
-    pv.a_bytes = (unsigned)(((int64_t)p.M * p.a_rs) * 2);
-    pv.b_bytes = (unsigned)(((int64_t)p.N * p.b_rs) * 2);
-    const int grid = (int)(pv.ntiles < g8_cus() ? pv.ntiles : g8_cus());
-    const bool conv = p.taps > 1;
-    if (conv)
-        launch_8p<true>(pv, grid, stream);
-    else
-        launch_8p<false>(pv, grid, stream);
-    a3t_note_kernel("gemm_bf16_8p_kernel<%s>", conv ? "true" : "false");
     return (int)hipGetLastError();
 }

@@ -348,36 +348,10 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pn_kernel(GP p) {
     if (pend) epi(e_tile, e_chunk);
 }
 
-static int pn_cus() {          // per device (a process may drive several GPUs)
-    static int n[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!n[dev]) {
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-        n[dev] = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-    }
-    return n[dev];
-}
-
-// mode: 0 never, 1 whenever legal, 2 cost model (default), 3 cost model for N = 384 only; A3T_GEMM_PN or a3t_gemm_pn_mode()
-static int g_pn_mode = -1;
-static int pn_mode() {
-    if (g_pn_mode < 0) {
-        const char* e = getenv("A3T_GEMM_PN");
-        g_pn_mode = e ? atoi(e) : 2;
-    }
-    return g_pn_mode;
-}
-extern "C" int a3t_gemm_pn_mode(int mode) {
-    const int old = pn_mode();
-    g_pn_mode = mode;
-    return old;
-}
-
-static bool pn_applicable(const GP& p, int batch, int ly) {
-    const int mode = pn_mode();
-    if (mode == 0 || ly != 0 || batch != 1 || p.splitk != 1 || p.accumulate != A3T_ACC_STORE) return false;
+// mode (A3T_GEMM_PN, a3t_gemm_pn_mode): 0 never, 1 whenever legal, 2 cost model (default), 3 cost model for N = 384 only
+bool pn_plan(const GP& p, int batch, int ly, GemmPlan* pl) {
+    const int mode = gemm_switch(SW_PN);
+    if (mode == 0 || ly != L_NT || batch != 1 || p.splitk != 1 || p.accumulate != A3T_ACC_STORE) return false;
     if (p.N % 8 != 0 || p.K % 64 != 0 || p.c_rs % 8 != 0 || p.a_cs != 1 || p.b_cs != 1) return false;
     if (p.kshift_mode || p.keep_out || (p.keep_in && p.keep_layout != 1)) return false;      // (keep_in: the row-major nibble image only)
     if (p.S && ((uintptr_t)p.S & 15)) return false;
@@ -390,6 +364,7 @@ static bool pn_applicable(const GP& p, int batch, int ly) {
     const int64_t a_bytes = ((int64_t)p.M * p.a_rs) * 2, b_bytes = ((int64_t)p.N * p.b_rs) * 2;
     if (a_bytes >= (1ll << 31) || b_bytes >= (1ll << 31) || (int64_t)p.M * p.c_rs >= (1ll << 32)) return false;
     if (mode == 3 && p.N != PN_COLS) return false;
+    const int panels = (p.M + PN_ROWS - 1) / PN_ROWS, cus = gemm_cus();
     if (mode >= 2) {
         // Cost model fitted on MI355X (tools/probes/gemm_pn.hip, profiles/r03_pn_check.txt): a tile (panel x 384-column chunk) costs ~1.55 us per
         // 64-wide K-tile plus ~8 us of pipeline fill and epilogue (dropout hashes and an fp32 residual add ~3 more; the later
@@ -401,8 +376,7 @@ static bool pn_applicable(const GP& p, int batch, int ly) {
         // next launch, a step does not.  The exception is the data gradient of the second FFN conv, whose ReLU' mask read makes the
         // 128x128 kernel's epilogue slow: -0.5 ms per step.  Hence: several chunks only for problems that carry a mask tensor.
         if (p.N % PN_COLS != 0 || (p.N > PN_COLS && !p.S && !p.keep_in)) return false;
-        const long panels = (p.M + PN_ROWS - 1) / PN_ROWS, chunks = p.N / PN_COLS;
-        const int cus = pn_cus();
+        const long chunks = p.N / PN_COLS;
         const double rounds = (double)((panels + cus - 1) / cus);
         double fixed = 8.0;
         if (p.drop_inv > 0.f) fixed += 1.5;
@@ -412,24 +386,17 @@ static bool pn_applicable(const GP& p, int batch, int ly) {
         const double t128 = 2.0 * p.M * p.N * (double)p.K / (p.K >= 1024 ? (p.N >= 1024 ? 780e6 : 700e6) : 450e6) + 6.0;     // us
         if (panels < cus / 2 || tpn > 0.9 * t128) return false;
     }
+    pl->route = GR_PN, pl->cv = p.taps > 1;
+    pl->tiles_n = (p.N + PN_COLS - 1) / PN_COLS, pl->ntiles = panels * pl->tiles_n;
+    pl->grid = dim3((unsigned)(panels < cus ? panels : cus));
+    snprintf(pl->name, sizeof(pl->name), "gemm_bf16_pn_kernel<%s>", tf(pl->cv));
     return true;
 }
 
-// flags as for a3t_gemm_8p_supported: 1 bias / activation, 2 dropout, 16 fp32 output / residual, 32 column sums, 64 ReLU' mask
-// tensor S, 8 keep_in as the row-major nibble image of a3t_gemm_desc::keep_layout = 1 (4: never)
+// flags as for gemm_rep, keep_in (8) as the row-major nibble image of a3t_gemm_desc::keep_layout = 1 (keep_out, 4: never)
 extern "C" int a3t_gemm_pn_supported(int M, int N, int K, int taps, int flags) {
-    static float dummy[4] __attribute__((aligned(16)));
-    GP p = {};
-    p.M = M, p.N = N, p.K = K, p.taps = taps < 1 ? 1 : taps, p.Kc = K / p.taps, p.b_ts = p.Kc;
-    p.a_rs = p.Kc, p.a_cs = 1, p.b_rs = K, p.b_cs = 1, p.c_rs = N, p.splitk = 1, p.accumulate = A3T_ACC_STORE;
-    p.Tseq = 1, p.colsum_slots = 1, p.c_dtype = (flags & 16) ? A3T_F32 : A3T_BF16;
-    if (flags & 1) p.bias = dummy, p.act = A3T_ACT_RELU;
-    if (flags & 2) p.drop_inv = 1.25f;
-    if (flags & 4) p.keep_out = (unsigned char*)dummy;
-    if (flags & 8) p.keep_in = (const unsigned char*)dummy, p.keep_layout = 1;      // (the row-major nibble image)
-    if (flags & 32) p.colsum = dummy;
-    if (flags & 64) p.S = dummy, p.s_dtype = A3T_BF16;
-    return pn_applicable(p, 1, 0) ? 1 : 0;
+    GemmPlan pl;
+    return pn_plan(gemm_rep(M, N, K, taps, flags, 1), 1, L_NT, &pl) ? 1 : 0;
 }
 
 template <bool CV>
@@ -439,21 +406,14 @@ static void launch_pn(const GP& pv, int grid, hipStream_t stream) {
     hipLaunchKernelGGL((gemm_bf16_pn_kernel<CV>), dim3(grid), dim3(512), lds, stream, pv);
 }
 
-// Called by a3t_gemm_bf16_glds after the alignment contract has been checked.  Returns -1 when not applicable.
-int a3t_gemm_bf16_pn(const GP& p, int batch, int ly, hipStream_t stream) {
-    if (!pn_applicable(p, batch, ly)) return -1;
+int pn_launch(const GP& p, const GemmPlan& pl, hipStream_t stream) {
     GP pv = p;
-    const int panels = (int)((p.M + PN_ROWS - 1) / PN_ROWS);
-    pv.tiles_n = (p.N + PN_COLS - 1) / PN_COLS;
-    pv.ntiles = panels * pv.tiles_n;
+    pv.tiles_n = pl.tiles_n, pv.ntiles = pl.ntiles;
     pv.a_bytes = (unsigned)(((int64_t)p.M * p.a_rs) * 2);
     pv.b_bytes = (unsigned)(((int64_t)p.N * p.b_rs) * 2);
-    const int grid = panels < pn_cus() ? panels : pn_cus();
-    const bool conv = p.taps > 1;
-    if (conv)
-        launch_pn<true>(pv, grid, stream);
+    if (pl.cv)
+        launch_pn<true>(pv, (int)pl.grid.x, stream);
     else
-        launch_pn<false>(pv, grid, stream);
-    a3t_note_kernel("gemm_bf16_pn_kernel<%s>", conv ? "true" : "false");
+        launch_pn<false>(pv, (int)pl.grid.x, stream);
     return (int)hipGetLastError();
 }

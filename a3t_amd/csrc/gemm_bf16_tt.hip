@@ -296,31 +296,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tt_kernel(GP p, int TR) {
 #endif
 }
 
-// mode: 0 never, 1 whenever legal, 2 (default) when the grid fills the chip; A3T_GEMM_TT or a3t_gemm_tt_mode()
-static int g_tt_mode = -1;
-static int tt_mode() {
-    if (g_tt_mode < 0) {
-        const char* e = getenv("A3T_GEMM_TT");
-        g_tt_mode = e ? atoi(e) : 2;
-    }
-    return g_tt_mode;
-}
-extern "C" int a3t_gemm_tt_mode(int mode) {
-    const int old = tt_mode();
-    g_tt_mode = mode;
-    return old;
-}
-
-static int tt_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t pr;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-    }
-    return n;
-}
-
 template <bool ATN, int NJ, bool ASGN = false, bool DUAL = false>
 static void launch_tt(const GP& pv, int TR, int grid, hipStream_t stream) {
     (void)hipFuncSetAttribute((const void*)gemm_bf16_tt_kernel<ATN, NJ, ASGN, DUAL>, hipFuncAttributeMaxDynamicSharedMemorySize, TT_LDS);
@@ -333,7 +308,7 @@ static void launch_tt(const GP& pv, int TR, int grid, hipStream_t stream) {
 // elements) -> 4 tiles of 288 rows = 256 workgroups = one round; configs[3] (M = 1800) -> 8 tiles of 256 rows = two full rounds
 // (6 tiles of 320 would be 1.5 rounds for the price of two).  A last tile with a few rows is cheap (its A pieces are zeros).
 static bool tt_tiling(int M, int N, int K, int batch, int mode, int& tiles, int& TR) {
-    const int cus = tt_cus();
+    const int cus = gemm_cus();
     tiles = 0, TR = 0;
     long best = 0;
     for (int t = (M + TT_MAX_ROWS - 1) / TT_MAX_ROWS, n = 0; n < 6; ++t, ++n) {
@@ -354,65 +329,77 @@ static bool tt_tiling(int M, int N, int K, int batch, int mode, int& tiles, int&
     return true;
 }
 
-// 1 when a3t_gemm runs the batched bf16 product (M x N per batch element, reduction K, A score-sized [m][k], B [k][n]) on the
-// streaming kernel under the current mode -- the engine asks before it hands it TWO products for one launch (a3t_gemm_desc::A2)
-extern "C" int a3t_gemm_tt_supported(int M, int N, int K, int batch) {
-    int tiles, TR;
-    const int mode = tt_mode();
-    if (mode == 0 || N > 192 || N % 8 || M % 8 || K % 8) return 0;
-    return tt_tiling(M, N, K, batch, mode, tiles, TR) ? 1 : 0;
-}
-
-// Called by a3t_gemm_bf16_glds after the alignment contract has been checked (ly: 1 = NN, 2 = TN; B is [k][n], n-contiguous).
-// Returns -1 when not applicable.
-int a3t_gemm_bf16_tt(const GP& p, int batch, int ly, hipStream_t stream) {
-    const int mode = tt_mode();
-    if (mode == 0 || (ly != 1 && ly != 2) || p.splitk != 1 || p.accumulate == A3T_ACC_ATOMIC) return -1;
-    if (p.a_signmask && ly != 2) return -1;
+// ly: L_NN ([m][k] A) or L_TN ([k][m] A); B is [k][n], n-contiguous.  mode (A3T_GEMM_TT, a3t_gemm_tt_mode): 0 never, 1 whenever
+// legal, 2 (default) when the grid fills the chip
+bool tt_plan(const GP& p, int batch, int ly, GemmPlan* pl) {
+    const int mode = gemm_switch(SW_TT);
+    if (mode == 0 || (ly != L_NN && ly != L_TN) || p.splitk != 1 || p.accumulate == A3T_ACC_ATOMIC) return false;
+    if (p.a_signmask && ly != L_TN) return false;
     if (p.A2) {
         const bool v2 = (p.a_unaligned & 2) != 0;       // A2: a 2-byte aligned view with any row stride
         const int64_t a2 = p.a2_rs ? p.a2_rs : p.a_rs;
-        if (ly != 1 || p.accumulate != A3T_ACC_STORE || !p.B2 || p.b2_cs % 8 || (p.b2_bs0 | p.b2_bs1) % 8 || ((uintptr_t)p.B2 & 15) ||
+        if (ly != L_NN || p.accumulate != A3T_ACC_STORE || !p.B2 || p.b2_cs % 8 || (p.b2_bs0 | p.b2_bs1) % 8 || ((uintptr_t)p.B2 & 15) ||
             ((uintptr_t)p.A2 & (v2 ? 1 : 15)) || (!v2 && a2 % 8) || a2 < p.K || a2 * 2 * (int64_t)p.M >= (1ll << 31) ||
             p.b2_cs * 2 * (int64_t)p.K >= (1ll << 31) || (p.colsum != nullptr) != (p.colsum2 != nullptr))
-            return -1;
+            return false;
     }
-    if (p.taps > 1 || p.kshift_mode || p.keep_in || p.keep_out || !p.epi_vec) return -1;
-    if (p.b_rs != 1 || p.N > 192 || p.N % 8 || p.M % 8 || p.K % 8) return -1;
-    if (ly == 1 ? (p.a_cs != 1 || p.a_rs % 8) : (p.a_rs != 1 || p.a_cs % 8)) return -1;
-    if (p.b_cs % 8 || (p.a_bs0 | p.a_bs1 | p.b_bs0 | p.b_bs1) % 8) return -1;
-    if (p.bias || p.R || p.S || p.act != A3T_ACT_NONE || p.drop_inv > 0.f || p.c_dtype != A3T_BF16) return -1;
+    if (p.taps > 1 || p.kshift_mode || p.keep_in || p.keep_out || !p.epi_vec) return false;
+    if (p.b_rs != 1 || p.N > 192 || p.N % 8 || p.M % 8 || p.K % 8) return false;
+    if (ly == L_NN ? (p.a_cs != 1 || p.a_rs % 8) : (p.a_rs != 1 || p.a_cs % 8)) return false;
+    if (p.b_cs % 8 || (p.a_bs0 | p.a_bs1 | p.b_bs0 | p.b_bs1) % 8) return false;
+    if (p.bias || p.R || p.S || p.act != A3T_ACT_NONE || p.drop_inv > 0.f || p.c_dtype != A3T_BF16) return false;
     // one batch element's operands through 32-bit buffer offsets
-    const int64_t a_ld = ly == 1 ? p.a_rs : p.a_cs;
-    if (a_ld * 2 * (int64_t)(ly == 1 ? p.M : p.K) >= (1ll << 31) || p.b_cs * 2 * (int64_t)p.K >= (1ll << 31)) return -1;
+    const int64_t a_ld = ly == L_NN ? p.a_rs : p.a_cs;
+    if (a_ld * 2 * (int64_t)(ly == L_NN ? p.M : p.K) >= (1ll << 31) || p.b_cs * 2 * (int64_t)p.K >= (1ll << 31)) return false;
     int tiles = 0, TR = 0;
-    if (!tt_tiling(p.M, p.N, p.K, batch, mode, tiles, TR)) return -1;
-    const long units = (long)tiles * batch;
+    if (!tt_tiling(p.M, p.N, p.K, batch, mode, tiles, TR)) return false;
+    pl->route = GR_TT, pl->ly = ly, pl->ntiles = tiles, pl->TR = TR, pl->grid = dim3((unsigned)((long)tiles * batch));
+    pl->nj = p.N <= 128 ? 2 : 3;
+    pl->atn = ly == L_TN, pl->asgn = pl->atn && p.a_signmask, pl->dual = !pl->atn && p.A2;
+    snprintf(pl->name, sizeof(pl->name), "gemm_bf16_tt_kernel<%s, %d, %s, %s>", tf(pl->atn), pl->nj, tf(pl->asgn), tf(pl->dual));
+    return true;
+}
+
+// 1 when a3t_gemm runs the batched bf16 product (M x N per batch element, reduction K, A score-sized [m][k], B [k][n]) on the
+// streaming kernel under the current mode -- the engine asks before it hands it TWO products for one launch (a3t_gemm_desc::A2).
+// The plan's own predicate on a representative descriptor: dense operands, 16-byte aligned, bf16 C stored by the vector epilogue.
+extern "C" int a3t_gemm_tt_supported(int M, int N, int K, int batch) {
+    static float dummy[4] __attribute__((aligned(16)));
+    GP p = {};
+    p.A = dummy, p.B = dummy, p.C = dummy;
+    p.M = M, p.N = N, p.K = K, p.Kc = K, p.taps = 1, p.alpha = 1.f, p.colsum_slots = 1;
+    p.a_rs = K, p.a_cs = 1, p.b_rs = 1, p.b_cs = N, p.c_rs = N;
+    p.batch_inner = 1, p.a_bs0 = (int64_t)M * K, p.b_bs0 = (int64_t)K * N, p.c_bs0 = (int64_t)M * N;
+    p.splitk = 1, p.accumulate = A3T_ACC_STORE, p.c_dtype = A3T_BF16, p.epi_vec = 1;
+    GemmPlan pl;
+    return tt_plan(p, batch, L_NN, &pl) ? 1 : 0;
+}
+
+int tt_launch(const GP& p, const GemmPlan& pl, hipStream_t stream) {
     GP pv = p;
-    pv.ntiles = tiles;
-    const int nj = p.N <= 128 ? 2 : 3;
-    if (ly == 2 && p.a_signmask) {
-        if (nj == 3)
-            launch_tt<true, 3, true>(pv, TR, (int)units, stream);
+    pv.ntiles = pl.ntiles;
+    const int TR = pl.TR, grid = (int)pl.grid.x;
+    const bool nj3 = pl.nj == 3;
+    if (pl.asgn) {
+        if (nj3)
+            launch_tt<true, 3, true>(pv, TR, grid, stream);
         else
-            launch_tt<true, 2, true>(pv, TR, (int)units, stream);
-    } else if (ly == 2) {
-        if (nj == 3)
-            launch_tt<true, 3>(pv, TR, (int)units, stream);
+            launch_tt<true, 2, true>(pv, TR, grid, stream);
+    } else if (pl.atn) {
+        if (nj3)
+            launch_tt<true, 3>(pv, TR, grid, stream);
         else
-            launch_tt<true, 2>(pv, TR, (int)units, stream);
-    } else if (p.A2) {
-        if (nj == 3)
-            launch_tt<false, 3, false, true>(pv, TR, (int)units, stream);
+            launch_tt<true, 2>(pv, TR, grid, stream);
+    } else if (pl.dual) {
+        if (nj3)
+            launch_tt<false, 3, false, true>(pv, TR, grid, stream);
         else
-            launch_tt<false, 2, false, true>(pv, TR, (int)units, stream);
+            launch_tt<false, 2, false, true>(pv, TR, grid, stream);
     } else {
-        if (nj == 3)
-            launch_tt<false, 3>(pv, TR, (int)units, stream);
+        if (nj3)
+            launch_tt<false, 3>(pv, TR, grid, stream);
         else
-            launch_tt<false, 2>(pv, TR, (int)units, stream);
+            launch_tt<false, 2>(pv, TR, grid, stream);
     }
-    a3t_note_kernel("gemm_bf16_tt_kernel<%s, %d, %s, %s>", ly == 2 ? "true" : "false", nj, (ly == 2 && p.a_signmask) ? "true" : "false",
-                    (ly == 1 && p.A2) ? "true" : "false");
     return (int)hipGetLastError();
 }

@@ -2,12 +2,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include "../../include/a3t_hip.h"
 #include "dtype_io.h"
 
 // Introspection for bench.py / profilers: a3t_gemm records the name (as rocprofv3 prints it) of the kernel variant
 // its dispatcher picked for the calling thread's last launch; read back with a3t_gemm_last_kernel().
-void a3t_note_kernel(const char* fmt, ...);
+void a3t_note_kernel(const char* name);
+
+enum { L_NT = 0, L_NN = 1, L_TN = 2 };   // operand layouts of the direct-to-LDS kernels: A k-contiguous x B k-contiguous / [k][n] / A [k][m]
 
 struct GP {
     const void* A;
@@ -214,3 +217,41 @@ __device__ __forceinline__ void colsum_flush(const GP& p, float4 cs, int lane, b
         atomicAdd(o + 2, p.colsum_scale * cs.z), atomicAdd(o + 3, p.colsum_scale * cs.w);
     }
 }
+
+// =============================================================================================
+// host: kernel selection.  gemm_plan (gemm.hip) validates a descriptor and walks the routes in order; each kernel file owns one
+// X_plan (predicate, cost model, geometry: pure host code, false = not this kernel) and one X_launch.
+// =============================================================================================
+enum GemmRoute { GR_F32, GR_BF16_LEGACY, GR_GLDS_128, GR_PN, GR_G8, GR_G8_TN, GR_G8_TN3, GR_TT };
+struct GemmPlan {
+    GemmRoute route;
+    bool ak, bkc, vec;          // F32 / BF16_LEGACY: A / B k-contiguous; F32: 16-byte loads
+    bool a_f32, b_f32;          // BF16_LEGACY: fp32 operand storage
+    int ly, stages, wn, conv;   // GLDS_128: layout, LDS stages, 64-column groups per tile, conv mode (ly also for TT)
+    bool cv;                    // PN / G8: implicit-im2col conv; G8_TN / G8_TN3: fused conv weight gradient
+    int nj;                     // TT: template selectors
+    bool atn, asgn, dual;
+    dim3 grid;
+    int tiles_n, ntiles, splits, folds, TR;   // splits: GP::splitk of a K-split grid, folds: that of its fold launch
+    size_t slab_floats;                       // split-K partial slab (G8_TN / G8_TN3; 0: none)
+    char name[96];                            // as a3t_gemm_last_kernel reports it
+};
+
+int gemm_cus();                      // compute units of the current device (256 without one), cached per device
+// kernel-selection switches A3T_GEMM_8P, _PN, _TT, _8P_TN, _8P_TN3, _STAGES, _WN3 (gemm.hip: meanings, defaults)
+enum GemmSwitch { SW_8P, SW_PN, SW_TT, SW_8P_TN, SW_8P_TN3, SW_STAGES, SW_WN3 };
+int gemm_switch(int s);
+int gemm_switch_set(int s, int v);   // v < 0: read the environment again; returns the previous value
+// the k-contiguous bf16 problem the *_supported queries ask about; flags: 1 bias / ReLU, 2 dropout, 4 keep_out, 8 keep_in (in
+// `keep_layout`), 16 fp32 output, 32 column sums, 64 bf16 ReLU' mask tensor S
+GP gemm_rep(int M, int N, int K, int taps, int flags, int keep_layout);
+static inline const char* tf(bool b) { return b ? "true" : "false"; }
+
+void glds_plan(const GP& p, int batch, int ly, GemmPlan* pl);   // gemm_bf16.hip (takes whatever reaches it)
+int glds_launch(const GP& p, const GemmPlan& pl, hipStream_t stream);
+bool pn_plan(const GP& p, int batch, int ly, GemmPlan* pl);     // gemm_bf16_pn.hip
+int pn_launch(const GP& p, const GemmPlan& pl, hipStream_t stream);
+bool g8_plan(const GP& p, int batch, int ly, GemmPlan* pl);     // gemm_bf16_8p.hip: G8, G8_TN, G8_TN3
+int g8_launch(const GP& p, const GemmPlan& pl, hipStream_t stream);
+bool tt_plan(const GP& p, int batch, int ly, GemmPlan* pl);     // gemm_bf16_tt.hip
+int tt_launch(const GP& p, const GemmPlan& pl, hipStream_t stream);

@@ -8,7 +8,7 @@ import torch
 from . import _lib as L
 from ._lib import ACC_ADD, ACC_ATOMIC, ACC_SOLE, ACC_STORE, ACT_NONE, ACT_RELU, ACT_SWISH, ACT_TANH, BF16, F32
 
-__all__ = ["gemm", "linear_fwd", "linear_bwd_data", "linear_bwd_weight", "conv_fwd", "conv_bwd_data",
+__all__ = ["gemm", "gemm_plan", "linear_fwd", "linear_bwd_data", "linear_bwd_weight", "conv_fwd", "conv_bwd_data",
            "conv_bwd_weight"]
 
 
@@ -35,12 +35,12 @@ def _dt(t):
     raise TypeError(f"unsupported dtype {t.dtype}")
 
 
-def gemm(A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, c_rs, *, b_ts=0, bias=None, R=None, S=None, batch=1,
-         batch_inner=1, a_bs=(0, 0), b_bs=(0, 0), c_bs=(0, 0), taps=1, pad=0, dil=1, Tseq=0, kshift=0, alpha=1.0,
-         act=ACT_NONE, acc=ACC_STORE, splitk=1, compute=F32, colsum=None, colsum_bs1=0, colsum_scale=1.0,
-         drop=None, colsum_slots=1, colsum_ss=0, keep_out=None, keep_in=None, a_signmask=False, keep_layout=0, second=None, a_view=False):
-    """C (op)= alpha*mask(act(A(m,k) B(n,k) + bias)) + R  -- see a3t_gemm_desc in include/a3t_hip.h."""
-    lib = L.load()
+def _gemm_desc(A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, c_rs, *, b_ts=0, bias=None, R=None, S=None, batch=1,
+               batch_inner=1, a_bs=(0, 0), b_bs=(0, 0), c_bs=(0, 0), taps=1, pad=0, dil=1, Tseq=0, kshift=0, alpha=1.0,
+               act=ACT_NONE, acc=ACC_STORE, splitk=1, compute=F32, colsum=None, colsum_bs1=0, colsum_scale=1.0,
+               drop=None, colsum_slots=1, colsum_ss=0, keep_out=None, keep_in=None, a_signmask=False, keep_layout=0, second=None,
+               a_view=False):
+    """The a3t_gemm_desc of C (op)= alpha*mask(act(A(m,k) B(n,k) + bias)) + R  -- see include/a3t_hip.h."""
     d = L.GemmDesc()
     d.A, d.B, d.C = A.data_ptr(), B.data_ptr(), C.data_ptr()
     d.bias = bias.data_ptr() if bias is not None else None
@@ -73,15 +73,30 @@ def gemm(A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, c_rs, *, b_ts=0, bias=None, R
         if len(second) > 5:
             d.a2_rs = second[5]
             d.a_unaligned |= 2
+    return d
+
+
+def gemm(*args, **kw):
+    """C (op)= alpha*mask(act(A(m,k) B(n,k) + bias)) + R; arguments as _gemm_desc."""
+    lib = L.load()
+    d = _gemm_desc(*args, **kw)
     if PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()          # torch's current stream == the stream handed to a3t_gemm
         L.check(lib.a3t_gemm(ctypes.byref(d), _stream()), "a3t_gemm")
         e1.record()
-        PROFILE.append((lib.a3t_gemm_last_kernel().decode(), (2.0 if second is None else 4.0) * M * N * K * batch, e0, e1,
-                        (M, N, K, batch, taps, splitk)))
+        PROFILE.append((lib.a3t_gemm_last_kernel().decode(), (4.0 if d.A2 else 2.0) * d.M * d.N * d.K * d.batch, e0, e1,
+                        (d.M, d.N, d.K, d.batch, d.taps, d.splitk)))
         return
     L.check(lib.a3t_gemm(ctypes.byref(d), _stream()), "a3t_gemm")
+
+
+def gemm_plan(*args, **kw):
+    """Name of the kernel gemm(*args, **kw) would launch (as a3t_gemm_last_kernel reports it), or None where a3t_gemm would
+    reject the descriptor.  Host code only (a3t_gemm_plan): nothing runs and no tensor is read, so they may live on the CPU."""
+    name = ctypes.create_string_buffer(128)
+    rc = L.load().a3t_gemm_plan(ctypes.byref(_gemm_desc(*args, **kw)), name, len(name))
+    return name.value.decode() if rc == 0 else None
 
 
 _SPLITK_TARGET = 1000      # workgroups of a split-K grid on the 128x128 kernel (500 / 700 / 1500 / 2000 measured in round 3: slower)

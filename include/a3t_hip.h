@@ -101,8 +101,8 @@ typedef struct a3t_gemm_desc {
     const void* keep_in;               /*   in the kernel's tile-major image of a3t_gemm_keep_bytes(M, N) bytes; keep_in applies
                                             such an image as a mask in the place of S (the ReLU'/dropout mask of
                                             multi_layer_conv.py:52-63's hidden layer on its way back).  a3t_gemm fails with
-                                            A3T_EINVAL when either is set and the 8-phase kernel does not take the problem:
-                                            ask a3t_gemm_8p_supported first. */
+                                            A3T_EINVAL when either is set and the 8-phase kernel does not take the problem
+                                            (a3t_gemm_8p_supported answers by shape and epilogue, a3t_gemm_plan by descriptor). */
     int32_t a_signmask;                /* 1: bf16 elements of A whose sign bit is set are read as zero -- the dV product of the
                                             attention backward (attention.py:64-96) over the probabilities a3t_attn_fwd_train
                                             stores with the dropout mask in their sign bits.  m-contiguous bf16 A only (the
@@ -120,8 +120,8 @@ typedef struct a3t_gemm_desc {
     const void* B2;                    /*   A2 has A's strides and batch strides, B2 [k][n] n-contiguous with row stride b2_cs and batch
                                             strides b2_bs0/1; same M, N, K.  dq = dS K + dBD P of the attention backward
                                             (attention.py:190-203 on its way back) as ONE launch of the streaming kernel
-                                            (csrc/gemm_bf16_tt.hip, [m][k] operand, A3T_ACC_STORE): anything else A3T_EINVAL -- ask
-                                            a3t_gemm_tt_supported first. */
+                                            (csrc/gemm_bf16_tt.hip, [m][k] operand, A3T_ACC_STORE): anything else A3T_EINVAL
+                                            (a3t_gemm_tt_supported answers by shape, a3t_gemm_plan by descriptor). */
     int64_t b2_cs, b2_bs0, b2_bs1;
     float* colsum2;                    /* with colsum: column sums of the second product's share (colsum takes the first's); same
                                             slots / strides as colsum */
@@ -134,6 +134,10 @@ typedef struct a3t_gemm_desc {
 } a3t_gemm_desc;
 
 int a3t_gemm(const a3t_gemm_desc* d, void* stream);
+/* What a3t_gemm returns for d before it launches (0 or A3T_EINVAL) and, on 0, the name of the kernel it launches (as
+ * a3t_gemm_last_kernel reports it) in name[len].  Host code only: needs no device (then as one of 256 compute units) and reads
+ * nothing through d's pointers -- their alignment is part of the choice. */
+int a3t_gemm_plan(const a3t_gemm_desc* d, char* name, int len);
 /* 1 when a3t_gemm runs the k-contiguous bf16 problem (M, N, K = taps * channels) on the persistent 256x256 8-phase kernel
  * (csrc/gemm_bf16_8p.hip) with the epilogue `flags` (1 bias/activation, 2 dropout, 4 keep_out, 8 keep_in, 16 fp32 output or
  * residual, 32 column sums); bytes of a keep-bit image */

@@ -10,6 +10,7 @@ dev = "cuda"
 lib = _lib.load()
 rng = random.Random(0)
 fails, seen = 0, {}
+mismatched = []      # launches whose ops.gemm_plan named another kernel than the one a3t_gemm launched
 
 def check(name, got, ref, k):
     global fails
@@ -19,6 +20,10 @@ def check(name, got, ref, k):
     if not (err < 2e-2) or not math.isfinite(err):
         fails += 1
         print(f"FAIL {name}: relerr {err:.3e}  kernel {var}")
+    if mismatched:
+        fails += 1
+        print(f"FAIL {name}: {mismatched}")
+        mismatched.clear()
 
 desc = [""]
 
@@ -83,12 +88,26 @@ def run(seed=0, n_cases=120, verbose=True):
     global fails, seen, rng
     rng = random.Random(seed)
     fails, seen = 0, {}
-    for case in range(n_cases):
-        try:
-            run_case(case)
-        except Exception as e:  # noqa: BLE001
-            fails += 1
-            print(f"EXC case {case} [{desc[0]}]: {type(e).__name__}: {e}")
+    mismatched.clear()
+    gemm = ops.gemm
+
+    def gemm_and_plan(*args, **kw):
+        planned = ops.gemm_plan(*args, **kw)
+        gemm(*args, **kw)
+        launched = lib.a3t_gemm_last_kernel().decode()
+        if planned != launched:
+            mismatched.append(f"planned {planned}, launched {launched}")
+
+    ops.gemm = gemm_and_plan
+    try:
+        for case in range(n_cases):
+            try:
+                run_case(case)
+            except Exception as e:  # noqa: BLE001
+                fails += 1
+                print(f"EXC case {case} [{desc[0]}]: {type(e).__name__}: {e}")
+    finally:
+        ops.gemm = gemm
     torch.cuda.synchronize()
     if verbose:
         print(f"{n_cases} cases, {fails} failures; kernel variants hit:")

@@ -72,3 +72,49 @@ def test_gemm_desc_layout_as_the_c_compiler_sees_the_header(tmp_path):
     for n in names:
         assert int(out[n]) == getattr(GemmDesc, n).offset, n
     assert int(out["sizeof"]) == ctypes.sizeof(GemmDesc)
+
+
+def _planned_arg(v):
+    """A recorded ops.gemm argument: a tensor becomes a small CPU tensor of its dtype at an address with the recorded alignment
+    (mod 256) -- the plan reads addresses, never data."""
+    import torch
+    if isinstance(v, list):
+        return [_planned_arg(x) for x in v]
+    if not isinstance(v, dict):
+        return v
+    buf = torch.empty(512, dtype=torch.uint8)
+    off = (v["al"] - buf.data_ptr()) % 256
+    return buf[off:off + 64].view(getattr(torch, v["dtype"]))
+
+
+def test_gemm_plan_names_the_kernel_a3t_gemm_launched():
+    """ops.gemm_plan (a3t_gemm_plan: host code; without a device the plan assumes 256 CUs, as on the MI355X) against what a3t_gemm
+    launched on an MI355X (a3t_gemm_last_kernel, recorded in tests/golden/gemm_routes.json): every GEMM call of one configs[1] and one
+    configs[3] training step, the fp32 and legacy paths, and every A3T_EINVAL branch reachable through ops.gemm (None).  The
+    a3t_gemm_*_supported queries of those steps answer as recorded under modes 0, 1 and 2."""
+    import json
+    from a3t_amd import _lib, build, ops
+    build.build(verbose=False)
+    lib = _lib.load()
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_routes.json")))
+    modes = {"8p": lib.a3t_gemm_8p_mode, "pn": lib.a3t_gemm_pn_mode, "tt": lib.a3t_gemm_tt_mode, "tn3": lib.a3t_gemm_tn3_mode}
+    old = {k: f(2) for k, f in modes.items()}
+    try:
+        bad = []
+        for leg in ("configs1", "configs3", "table"):
+            assert len(rec[leg]) > 50
+            for c in rec[leg]:
+                got = ops.gemm_plan(*_planned_arg(c["args"]), **{k: _planned_arg(v) for k, v in c["kw"].items()})
+                if got != c["kernel"]:
+                    bad.append((leg, c.get("case"), c["args"][3:11], got, c["kernel"]))
+        assert not bad, bad[:8]
+        assert sum(c["kernel"] is None for c in rec["table"]) >= 30
+        for name, args, answers in rec["queries"]:
+            mode = modes[name.split("_")[1]]
+            for m, want in answers.items():
+                mode(int(m))
+                assert getattr(ops, name)(*args) == want, (name, args, m)
+            mode(2)
+    finally:
+        for k, f in modes.items():
+            f(old[k])
