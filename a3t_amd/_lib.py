@@ -92,6 +92,7 @@ _SIGS = {
                       _P],
     "a3t_clip_adam_noam": [_P, _P, _P, _P, _P, _P, c_int64, _P, c_float, c_float, c_float, c_float, c_float, c_float,
                            c_float, c_float, _P],
+    "a3t_sgd_step": [_P, _P, c_int64, c_float, c_float, _P],
     "a3t_pwg_gate": [_P, _P, _P, c_int64, c_int, _P],
     "a3t_pwg_res_skip": [_P, _P, _P, c_int64, c_int, c_int, _P],
     "a3t_pwg_upsample": [_P, _P, _P, c_int64, c_int64, c_int, c_int, _P],

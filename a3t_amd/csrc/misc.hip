@@ -480,6 +480,32 @@ extern "C" int a3t_clip_adam_noam(float* p, const float* g, float* m, float* v, 
     return (int)hipGetLastError();
 }
 
+// Plain SGD on the flat parameter buffer (torch.optim.SGD(lr): no momentum, weight decay, clipping or finite-gradient guard --
+// the optimiser of the inference driver's dynamic_evaluation, sedit_inference.py:748-776): p[i] -= step * g[i] with
+// step = lr * gscale rounded to fp32 once; the product and the subtraction are two roundings (-ffp-contract=off), like torch's
+// p.add_(g, alpha=-step).  A streaming kernel, 12 bytes per parameter: 16 bytes per lane and access, 256 threads, a grid-stride
+// loop over at most 2048 workgroups (8 per CU, the grid of the Adam sweep above); the n % 4 tail -- and everything, when a
+// pointer is not 16-byte aligned -- goes through the scalar loop.
+__global__ __launch_bounds__(256) void sgd_step_kernel(float* __restrict__ p, const float* __restrict__ g, const int64_t n,
+                                                       const float step) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g)) & 15) == 0;
+    const int64_t n4 = vec ? n / 4 : 0;
+    for (int64_t i = tid; i < n4; i += nthr) {
+        float4 pi = ((float4*)p)[i];
+        const float4 gi = ((const float4*)g)[i];
+        pi.x -= step * gi.x, pi.y -= step * gi.y, pi.z -= step * gi.z, pi.w -= step * gi.w;
+        ((float4*)p)[i] = pi;
+    }
+    for (int64_t i = n4 * 4 + tid; i < n; i += nthr) p[i] -= step * g[i];
+}
+extern "C" int a3t_sgd_step(float* p, const float* g, int64_t n, float lr, float gscale, void* stream) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(sgd_step_kernel, dim3(nblocks((n + 3) / 4, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, n,
+                       lr * gscale);
+    return (int)hipGetLastError();
+}
+
 // ---------------------------------------------------------------- ParallelWaveGAN helpers
 __global__ void pwg_gate_kernel(const float* __restrict__ y, const float* __restrict__ c, float* __restrict__ out,
                                 int64_t n, int H) {

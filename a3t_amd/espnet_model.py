@@ -5,7 +5,8 @@ forward :155-187, _forward :350-375, inference :239-284, collect_feats :125-128)
 signature, same ``(loss, stats, weight)`` return contract (AbsESPnetModel,
 espnet2/train/abs_espnet_model.py:9-42), same ``state_dict`` keys/shapes, so
 ``Trainer.train_one_epoch`` (espnet2/train/trainer.py:545,610) can drive it unchanged:
-``loss.backward()`` runs the hand-written backward schedule and leaves gradients in ``p.grad``.
+``loss.backward()`` runs the hand-written backward schedule and leaves gradients in ``p.grad``
+(in ``eval()`` mode too, when grad is enabled: sedit_inference.py's dynamic_evaluation relies on it).
 
 There is no CPU execution path: calling forward without the HIP library / a GPU raises.
 """
@@ -164,7 +165,10 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
         batch_size = speech.shape[0]
         batch = self._batch(speech, text, masked_position, speech_mask, text_mask, speech_segment_pos,
                             text_segment_pos, spembs)
-        if torch.is_grad_enabled() and self.training:
+        if torch.is_grad_enabled():
+            # train() and eval() alike, as in the reference model (its dynamic evaluation calls eval() and then
+            # loss.backward()): the eval engine runs without dropout and with BatchNorm on its running statistics.  Under
+            # torch.no_grad() -- and in inference() -- the pass is forward-only: no saved tensors, no transposed weight shadows.
             loss = _TrainStep.apply(self, batch, *self._params.values())
         else:
             loss = self._engine().forward(batch, need_grad=False)["loss"].clone()

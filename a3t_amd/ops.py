@@ -516,6 +516,14 @@ def clip_adam_noam(p, g, m, v, partial, norm_out, state, base_lr, model_size, wa
                                         clip, gscale, _stream()), "clip_adam_noam")
 
 
+def sgd_step(p, g, lr, gscale=1.0):
+    """p -= (lr * gscale) * g on the flat fp32 buffers, one launch: torch.optim.SGD(lr) without momentum, weight decay, clipping
+    or a finite-gradient guard (a3t_sgd_step; the step is rounded to fp32 once, the product and the difference separately)."""
+    if p.dtype != torch.float32 or g.dtype != torch.float32 or p.numel() != g.numel() or not (p.is_contiguous() and g.is_contiguous()):
+        raise ValueError("sgd_step: p and g must be contiguous fp32 buffers of one size")
+    L.check(L.load().a3t_sgd_step(_ptr(p), _ptr(g), p.numel(), float(lr), float(gscale), _stream()), "sgd_step")
+
+
 def pwg_gate(y, c, out):
     T, H = out.shape
     L.check(L.load().a3t_pwg_gate(_ptr(y), _ptr(c), _ptr(out), T, H, _stream()), "pwg_gate")

@@ -357,6 +357,11 @@ int a3t_clip_adam_noam(float* p, const float* g, float* m, float* v, const doubl
                        int32_t* state, float base_lr, float model_size, float warmup, float beta1, float beta2,
                        float eps, float clip, float gscale, void* stream);
 
+/* Plain SGD step of the inference driver's dynamic evaluation (sedit_inference.py:748-776, torch.optim.SGD(lr) without
+ * momentum, weight decay or clipping, and without a finite-gradient guard) on the flat fp32 parameter buffer, one launch:
+ * p[i] -= (lr * gscale) * g[i], the step rounded to fp32 once, multiply and subtract rounded separately. */
+int a3t_sgd_step(float* p, const float* g, int64_t n, float lr, float gscale, void* stream);
+
 /* ParallelWaveGAN helpers (espnet2/gan_tts/wavenet/residual_block.py:114-169,
  * parallel_wavegan/upsample.py:22-189), channels-last [T][C]. */
 /* g = tanh(xa+ca)*sigmoid(xb+cb), y/c [T][2H] (a|b), out [T][H] */
