@@ -98,6 +98,11 @@ _SIGS = {
     "a3t_pwg_upsample": [_P, _P, _P, c_int64, c_int64, c_int, c_int, _P],
     "a3t_replicate_pad": [_P, _P, c_int64, c_int64, c_int, c_int, _P],
     "a3t_bias_act": [_P, _P, c_int64, c_int, c_int, c_float, _P],
+    "a3t_replicate_pad_ragged": [_P, _P, _P, c_int64, c_int64, c_int, c_int, _P],
+    "a3t_pwg_upsample_ragged": [_P, _P, _P, _P, c_int, c_int64, c_int64, c_int, c_int, _P],
+    "a3t_zero_tail": [_P, _P, c_int, c_int64, c_int64, c_int, _P],
+    "a3t_splice_spans": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
+    "a3t_pwg_block_ragged": [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_duration_head": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P],
     "a3t_l2_normalize": [_P, _P, c_int, c_int, c_float, _P],
     "a3t_dropout": [_P, c_int, _P, c_int, c_int64, c_float, ctypes.c_uint32, c_float, _P],

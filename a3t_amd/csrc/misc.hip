@@ -581,6 +581,106 @@ extern "C" int a3t_replicate_pad(const float* x, float* y, int64_t B, int64_t T,
     hipLaunchKernelGGL(replicate_pad_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, x, y, B, T, C, pad);
     return (int)hipGetLastError();
 }
+// ---- ragged twins: the padded [B][Tmax] layout stays, row b is valid for lens[b] * mul rows and is computed exactly as if it
+// had been passed alone; nothing behind a row's length is read into a valid output.
+__global__ void pwg_upsample_ragged_kernel(const float* __restrict__ c, const float* __restrict__ w, float* __restrict__ out,
+                                           const int32_t* __restrict__ lens, int mul, int64_t B, int64_t Tin, int C, int scale) {
+    const int64_t Tout = Tin * scale;
+    const int64_t n = B * Tout * C;
+    GRID_STRIDE(i, n) {
+        const int64_t ta = i / C;
+        const int ch = (int)(i - ta * C);
+        const int64_t b = ta / Tout, t = ta - b * Tout;
+        const int64_t Lout = (int64_t)lens[b] * mul * scale;      // the stretched signal is zero outside [0, Lout)
+        const float* cb = c + b * Tin * C;
+        float acc = 0.f;
+        if (t < Lout)
+            for (int j = 0; j <= 2 * scale; ++j) {
+                int64_t u = t + j - scale;
+                if (u >= 0 && u < Lout) acc += w[j] * cb[(u / scale) * C + ch];
+            }
+        out[i] = acc;
+    }
+}
+extern "C" int a3t_pwg_upsample_ragged(const float* c, const float* w, float* out, const int32_t* lens, int mul, int64_t B,
+                                       int64_t Tin, int C, int scale, void* stream) {
+    if (B <= 0 || Tin <= 0 || C <= 0 || scale <= 0 || mul <= 0) return A3T_EINVAL;
+    int64_t n = B * Tin * scale * C;
+    hipLaunchKernelGGL(pwg_upsample_ragged_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, c, w, out, lens, mul,
+                       B, Tin, C, scale);
+    return (int)hipGetLastError();
+}
+__global__ void replicate_pad_ragged_kernel(const float* x, float* y, const int32_t* __restrict__ lens, int64_t B, int64_t T,
+                                            int C, int pad) {
+    const int64_t Tp = T + 2 * pad, n = B * Tp * C;
+    GRID_STRIDE(i, n) {
+        const int64_t ta = i / C;
+        const int c = (int)(i - ta * C);
+        const int64_t b = ta / Tp;
+        const int64_t L = lens[b];
+        int64_t t = ta - b * Tp - pad;
+        t = t < 0 ? 0 : (t >= L ? L - 1 : t);
+        y[i] = L > 0 ? x[(b * T + t) * C + c] : 0.f;
+    }
+}
+extern "C" int a3t_replicate_pad_ragged(const float* x, float* y, const int32_t* lens, int64_t B, int64_t T, int C, int pad,
+                                        void* stream) {
+    if (B <= 0 || T <= 0 || C <= 0 || pad < 0) return A3T_EINVAL;
+    int64_t n = B * (T + 2 * pad) * C;
+    hipLaunchKernelGGL(replicate_pad_ragged_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, x, y, lens, B, T, C,
+                       pad);
+    return (int)hipGetLastError();
+}
+// x[b][t][:] = 0 for t >= lens[b] * mul (stores only: whatever the tail held, NaN included, is gone)
+__global__ void zero_tail_kernel(float* __restrict__ x, const int32_t* __restrict__ lens, int mul, int64_t B, int64_t T, int C) {
+    const int64_t n = B * T * C;
+    GRID_STRIDE(i, n) {
+        const int64_t ta = i / C;
+        const int64_t b = ta / T, t = ta - b * T;
+        if (t >= (int64_t)lens[b] * mul) x[i] = 0.f;
+    }
+}
+extern "C" int a3t_zero_tail(float* x, const int32_t* lens, int mul, int64_t B, int64_t T, int C, void* stream) {
+    if (B <= 0 || T <= 0 || C <= 0 || mul <= 0) return A3T_EINVAL;
+    hipLaunchKernelGGL(zero_tail_kernel, dim3(nblocks(B * T * C)), dim3(256), 0, (hipStream_t)stream, x, lens, mul, B, T, C);
+    return (int)hipGetLastError();
+}
+// Batched splice of the infill (decode_with_model, one row per request): out[b][t] = after[b][t] inside the row's span,
+// speech[b][t] for the other valid frames, 0 behind the row's length = number of set entries of its (prefix) speech_mask.
+// Every workgroup counts its row's mask itself (a few KiB, L2 hits); the first one of a row also writes lens[b].
+__global__ __launch_bounds__(256) void splice_spans_kernel(const float* __restrict__ after, const float* __restrict__ speech,
+                                                           const uint8_t* __restrict__ mask, const int32_t* __restrict__ spans,
+                                                           float* __restrict__ out, int32_t* __restrict__ lens, int Tin,
+                                                           int Tout, int C) {
+    __shared__ int cnt[4];
+    const int b = blockIdx.y;
+    int n = 0;
+    for (int t = threadIdx.x; t < Tin; t += 256) n += mask[(int64_t)b * Tin + t] ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o, 64);
+    if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = n;
+    __syncthreads();
+    const int L = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    if (blockIdx.x == 0 && threadIdx.x == 0) lens[b] = L;
+    const int s = spans[2 * b], e = spans[2 * b + 1];
+    const int64_t m = (int64_t)Tout * C;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) {
+        const int t = (int)(i / C), c = (int)(i - (int64_t)t * C);
+        float v = 0.f;
+        if (t < L && t < Tin) {
+            const int64_t j = ((int64_t)b * Tin + t) * C + c;
+            v = (t >= s && t < e) ? after[j] : speech[j];
+        }
+        out[(int64_t)b * m + i] = v;
+    }
+}
+extern "C" int a3t_splice_spans(const float* after, const float* speech, const uint8_t* speech_mask, const int32_t* spans,
+                                float* out, int32_t* lens, int B, int Tin, int Tout, int C, void* stream) {
+    if (B <= 0 || B > 65535 || Tin <= 0 || Tout <= 0 || C <= 0) return A3T_EINVAL;
+    const int gx = nblocks((int64_t)Tout * C, 64);
+    hipLaunchKernelGGL(splice_spans_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, after, speech, speech_mask, spans,
+                       out, lens, Tin, Tout, C);
+    return (int)hipGetLastError();
+}
 __global__ void bias_act_kernel(float* x, const float* bias, int64_t n, int C, int act, float scale) {
     GRID_STRIDE(i, n) {
         float v = x[i] * scale;

@@ -28,9 +28,14 @@ struct PwgArgs {
     float* x_out;         // stage 1 out
     float* skips;         // stage 1 accumulate
     int B, Tw, dil, tiles_t;
+    const int4* tiles;    // RAGGED: [ntiles] {row b, first sample t0, valid samples W_b of row b, 0}: the tiles that hold valid samples
+    int ntiles;           // RAGGED: entries of `tiles`
 };
 
-template <int STAGE>
+// RAGGED: row b is valid for W_b <= Tw samples and is computed as if it were alone: a tap beyond W_b is zero like one beyond
+// the utterance, rows behind W_b are neither loaded, computed nor stored, and the persistent loop walks the host-built list of
+// the tiles that hold valid samples instead of all B * tiles_t (one uniform 16-byte load per tile and walker).
+template <int STAGE, bool RAGGED>
 __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
     // 8 waves = 4 (rows) x 2 (columns), each a 64 x 64 sub-tile of the 256-sample tile: two waves per SIMD, so one wave's
     // epilogue / LDS latency is covered by its partner's MFMAs (the weights leave room for ONE workgroup per CU only)
@@ -46,22 +51,36 @@ __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
     const int wm = (w >> 1) * 64, wn = (w & 1) * 64, lr = lane & 31, lk = lane >> 5;
     for (int i = tid; i < KL * 128 / 4; i += 512) ((float4*)Wt)[i] = ((const float4*)a.wt)[i];
 
-    const int ntiles = a.B * a.tiles_t;
+    const int ntiles = RAGGED ? a.ntiles : a.B * a.tiles_t;
+    // tile index -> row, first sample and the row's valid length.  RAGGED: the list entry is fetched when the tile index
+    // changes, not per chunk (the chunk requests and the MFMA loop each walk the tiles in order, so each keeps its last entry
+    // instead of putting a uniform load and its wait in front of every chunk request; measured cost of the list on equal
+    // lengths: profiles/sedit_batch_latency.txt)
+    struct TileAt { int tile; int4 e; } req = {-1, {}}, cur = {-1, {}};
+    auto locate = [&](TileAt& at, int tile, int& b, int& t0, int& Wb) {
+        if (RAGGED) {
+            if (tile != at.tile) at.e = a.tiles[tile < ntiles ? tile : 0], at.tile = tile;
+            b = at.e.x, t0 = at.e.y, Wb = at.e.z;
+        } else {
+            b = tile / a.tiles_t, t0 = (tile - b * a.tiles_t) * TILE, Wb = a.Tw;
+        }
+    };
     const int r0 = tid >> 1, kq = (tid & 1) * (BK / 2);
     // The activation chunks are requested TWO chunks ahead of the MFMAs that consume them (register ring P0 / P1): with
     // one persistent workgroup per CU nothing else hides the HBM latency (one chunk = 1024 / 2048 MFMA cycles per wave).
     float4 P0[2], P1[2];
     auto load_chunk = [&](float4* dst, int tile, int kc) {
-        const int b = tile / a.tiles_t, t0 = (tile - b * a.tiles_t) * TILE;
+        int b, t0, Wb;
+        locate(req, tile, b, t0, Wb);
         const int k = kc * BK + kq;
         const int t = t0 + r0;
         float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
-        if (tile < ntiles && t < a.Tw) {
+        if (tile < ntiles && t < Wb) {
             const float* src = nullptr;
             if (STAGE == 0) {
                 if (k < 192) {
                     const int ts = t + ((k >> 6) - 1) * a.dil;
-                    if (ts >= 0 && ts < a.Tw) src = a.x_in + ((int64_t)b * a.Tw + ts) * 64 + (k & 63);
+                    if (ts >= 0 && ts < Wb) src = a.x_in + ((int64_t)b * a.Tw + ts) * 64 + (k & 63);
                 } else {
                     src = a.cu + ((int64_t)b * a.Tw + t) * 80 + (k - 192);
                 }
@@ -114,13 +133,14 @@ __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
         advance(t2, k2);         // chunk s+2
         if (t1 < ntiles) load_chunk(P1, t2, k2);
         if (STAGE == 1 && kc == 0) {
-            const int b = tile / a.tiles_t, t0 = (tile - b * a.tiles_t) * TILE;
+            int b, t0, Wb;
+            locate(cur, tile, b, t0, Wb);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int t = t0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                    const int64_t i0 = ((int64_t)b * a.Tw + (t < a.Tw ? t : 0)) * 64 + lr;
+                    const int64_t i0 = ((int64_t)b * a.Tw + (t < Wb ? t : 0)) * 64 + lr;
                     old[i][0][r] = oldsrc[i0];
                     old[i][1][r] = oldsrc[i0 + 32];
                 }
@@ -143,13 +163,14 @@ __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
             acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
         }
         if (kc == NCH - 1) {     // tile finished: gate / residual / skip straight from the accumulators
-            const int b = tile / a.tiles_t, t0 = (tile - b * a.tiles_t) * TILE;
+            int b, t0, Wb;
+            locate(cur, tile, b, t0, Wb);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int t = t0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                    if (t >= a.Tw) continue;
+                    if (t >= Wb) continue;
                     const int64_t row = (int64_t)b * a.Tw + t;
                     if (STAGE == 0) {
                         const float ya = acc[i][0][r] + bj0, yb = acc[i][1][r] + bj1;
@@ -191,6 +212,25 @@ static int pwg_blocks() {
     return n;
 }
 
+template <bool RAGGED>
+static int pwg_launch(PwgArgs a, const float* wt0, const float* b0, const float* wt1, const float* b1, int ntiles, void* stream) {
+    constexpr int lds0 = (272 * 128 + 2 * 8 * 260) * 4, lds1 = (64 * 128 + 2 * 16 * 260) * 4;
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)pwg_stage_kernel<0, RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds0);
+        (void)hipFuncSetAttribute((const void*)pwg_stage_kernel<1, RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1);
+        attr = true;
+    }
+    const int cus = pwg_blocks();
+    a.wt = wt0, a.bias = b0;
+    int g0 = ntiles < cus ? ntiles : cus;                 // stage 0: 153 KiB of LDS -> one persistent workgroup per CU
+    hipLaunchKernelGGL((pwg_stage_kernel<0, RAGGED>), dim3(g0), dim3(512), lds0, (hipStream_t)stream, a);
+    a.wt = wt1, a.bias = b1;
+    int g1 = ntiles < cus ? ntiles : cus;                 // stage 1: ~200 VGPRs x 8 waves -> one per CU as well
+    hipLaunchKernelGGL((pwg_stage_kernel<1, RAGGED>), dim3(g1), dim3(512), lds1, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
 // One residual block, in place on x and skips.  wt0: [272][128] (k = tap*64 + ch | 192 + aux ch; column n' = permuted
 // gate channel: see a3t_amd/vocoder.py), b0: [128] permuted the same way; wt1: [64][128] = conv1x1_out.weight^T, b1: [128].
 // g: scratch [B*Tw][64].
@@ -200,20 +240,21 @@ extern "C" int a3t_pwg_block(float* x, const float* cu, const float* wt0, const 
     PwgArgs a;
     a.x_in = x, a.cu = cu, a.gin = g, a.g = g, a.x_out = x, a.skips = skips;
     a.B = B, a.Tw = Tw, a.dil = dil, a.tiles_t = (Tw + 255) / 256;
-    const int ntiles = B * a.tiles_t;
-    constexpr int lds0 = (272 * 128 + 2 * 8 * 260) * 4, lds1 = (64 * 128 + 2 * 16 * 260) * 4;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)pwg_stage_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds0);
-        (void)hipFuncSetAttribute((const void*)pwg_stage_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1);
-        attr = true;
-    }
-    const int cus = pwg_blocks();
-    a.wt = wt0, a.bias = b0;
-    int g0 = ntiles < cus ? ntiles : cus;                 // stage 0: 153 KiB of LDS -> one persistent workgroup per CU
-    hipLaunchKernelGGL(pwg_stage_kernel<0>, dim3(g0), dim3(512), lds0, (hipStream_t)stream, a);
-    a.wt = wt1, a.bias = b1;
-    int g1 = ntiles < cus ? ntiles : cus;                 // stage 1: ~200 VGPRs x 8 waves -> one per CU as well
-    hipLaunchKernelGGL(pwg_stage_kernel<1>, dim3(g1), dim3(512), lds1, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    a.tiles = nullptr, a.ntiles = 0;
+    return pwg_launch<false>(a, wt0, b0, wt1, b1, B * a.tiles_t, stream);
+}
+
+// The same block over rows of different length in the padded [B][Tw] layout.  tiles: device int32 [ntiles][4] =
+// {row b, first sample t0 (a multiple of 256), valid samples W_b of row b, 0}, one entry per 256-sample tile with t0 < W_b
+// (0 <= b < B, W_b <= Tw: the caller's to guarantee, the kernel trusts the list).  Rows behind W_b keep what they held.
+extern "C" int a3t_pwg_block_ragged(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1,
+                                    const float* b1, float* g, float* skips, const int32_t* tiles, int ntiles, int B, int Tw,
+                                    int dil, void* stream) {
+    if (B <= 0 || Tw <= 0 || dil <= 0 || ntiles < 0 || !tiles || ((uintptr_t)tiles & 15)) return A3T_EINVAL;
+    if (ntiles == 0) return 0;
+    PwgArgs a;
+    a.x_in = x, a.cu = cu, a.gin = g, a.g = g, a.x_out = x, a.skips = skips;
+    a.B = B, a.Tw = Tw, a.dil = dil, a.tiles_t = (Tw + 255) / 256;
+    a.tiles = (const int4*)tiles, a.ntiles = ntiles;
+    return pwg_launch<true>(a, wt0, b0, wt1, b1, ntiles, stream);
 }

@@ -192,3 +192,31 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
         s, e = int(span_boundary[0]), int(span_boundary[1])
         sp = batch["speech"][:, :speech.shape[1]]          # (bf16 mode may have extended the padding)
         return dict(feat_gen=[sp[:, :s], zs[0][s:e].clone(), sp[:, e:]])
+
+    def inference_batch(self, speech, text, masked_position, speech_mask, text_mask, speech_segment_pos, text_segment_pos,
+                        span_boundary, spembs=None, use_teacher_forcing: bool = True):
+        """Teacher-forced infill of a whole batch: one forward-only pass, then a3t_splice_spans writes, per row b,
+        out[b][t] = after[b][t] for span_boundary[b][0] <= t < span_boundary[b][1], speech[b][t] for the other valid frames
+        and 0 behind the row's length speech_mask[b].sum() (the batch's speech_lengths are raw samples, as in the reference).
+        Returns (out (B, Tmax, odim) fp32, lengths (B,) int32), both on the device.
+
+        A row of a batch is what the reference's collate function and model give for that row IN that batch.  It is not
+        bit-identical to the same request run alone, in the reference either: the STFT reflects at the end of the padded
+        waveform, the convolution module does not mask padded frames and the legacy rel_shift depends on the padded length.
+        The model is trained on exactly such batches."""
+        from . import ops
+        if not use_teacher_forcing:
+            raise NotImplementedError("only use_teacher_forcing=True is functional in the reference")
+        B, Tmax = speech.shape[0], speech.shape[1]
+        sb = span_boundary if torch.is_tensor(span_boundary) else torch.tensor([[int(s), int(e)] for s, e in span_boundary])
+        if sb.shape != (B, 2):
+            raise ValueError(f"span_boundary must be (B, 2) = ({B}, 2), got {tuple(sb.shape)}")
+        batch = self._batch(speech, text, masked_position, speech_mask, text_mask, speech_segment_pos, text_segment_pos, spembs)
+        dev = self.store.device
+        spans = sb.to(torch.int32).contiguous().to(dev, non_blocking=True)
+        out = self._engine().forward(batch, need_grad=False)
+        sp = batch["speech"].contiguous()                     # (bf16 mode may have extended the padding)
+        res = torch.empty(B, Tmax, sp.shape[2], dtype=torch.float32, device=dev)
+        lens = torch.empty(B, dtype=torch.int32, device=dev)
+        ops.splice_spans(out["after"].contiguous(), sp, batch["speech_mask"].contiguous().view(B, -1), spans, res, lens)
+        return res, lens

@@ -554,6 +554,65 @@ def replicate_pad(x, y, pad):
     L.check(L.load().a3t_replicate_pad(_ptr(x), _ptr(y), B, T, C, pad, _stream()), "replicate_pad")
 
 
+def _i32(t, what):
+    if t.dtype != torch.int32 or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous int32 tensor")
+    return t
+
+
+def replicate_pad_ragged(x, y, lens, pad):
+    """x [B][T][C] -> y [B][T + 2 pad][C], row b clamped to its own [0, lens[b] - 1] (lens: device int32 [B])."""
+    B, T, C = x.shape
+    L.check(L.load().a3t_replicate_pad_ragged(_ptr(x), _ptr(y), _ptr(_i32(lens, "lens")), B, T, C, pad, _stream()),
+            "replicate_pad_ragged")
+
+
+def pwg_upsample_ragged(c, w, out, scale_, lens, mul):
+    """c [B][Tin][C] -> out [B][Tin*scale][C]; row b is valid for lens[b] * mul input rows, zero behind."""
+    B, Tin, C = c.shape
+    L.check(L.load().a3t_pwg_upsample_ragged(_ptr(c), _ptr(w), _ptr(out), _ptr(_i32(lens, "lens")), mul, B, Tin, C, scale_,
+                                             _stream()), "pwg_upsample_ragged")
+
+
+def zero_tail(x, lens, mul, B, T):
+    """x [B*T][C] (or [B][T][C]): rows t >= lens[b] * mul of every b are set to 0."""
+    C = x.shape[-1]
+    L.check(L.load().a3t_zero_tail(_ptr(x), _ptr(_i32(lens, "lens")), mul, B, T, C, _stream()), "zero_tail")
+
+
+def pwg_block_ragged(x, cu, wt0, b0, wt1, b1, g, skips, tiles, B, Tw, dil):
+    """Fused residual block over rows of different length (a3t_pwg_block_ragged); tiles: device int32 [ntiles][4] =
+    {row b, first sample t0, valid samples W_b, 0} (vocoder.pwg_tile_list).  The kernel indexes x / cu / g / skips with the list's
+    entries unchecked: 0 <= b < B, t0 < W_b <= Tw are the caller's to guarantee; what can be checked on the host is."""
+    if tiles.dim() != 2 or tiles.shape[1] != 4:
+        raise ValueError(f"pwg_block_ragged: tiles must be (ntiles, 4), got {tuple(tiles.shape)}")
+    if tiles.shape[0] > B * ((Tw + 255) // 256):
+        raise ValueError(f"pwg_block_ragged: {tiles.shape[0]} tiles do not fit {B} rows of {Tw} samples")
+    for name, t, C in (("x", x, 64), ("cu", cu, 80), ("g", g, 64), ("skips", skips, 64)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != B * Tw * C:
+            raise ValueError(f"pwg_block_ragged: {name} must be a contiguous fp32 [{B * Tw}][{C}] tensor")
+    L.check(L.load().a3t_pwg_block_ragged(_ptr(x), _ptr(cu), _ptr(wt0), _ptr(b0), _ptr(wt1), _ptr(b1), _ptr(g), _ptr(skips),
+                                          _ptr(_i32(tiles, "tiles")), tiles.shape[0], B, Tw, dil, _stream()),
+            "pwg_block_ragged")
+
+
+def splice_spans(after, speech, speech_mask, spans, out, lens):
+    """out[b][t] = after[b][t] inside spans[b], speech[b][t] for the other valid frames, 0 behind the row's length (the sum of
+    its speech_mask, written to lens).  after / speech [B][Tin][C] fp32, speech_mask [B][Tin] bool / uint8, out [B][Tout][C]."""
+    B, Tin, C = speech.shape
+    if after.shape != speech.shape or speech_mask.numel() != B * Tin or spans.shape != (B, 2) or out.shape[0] != B \
+            or out.shape[2] != C or lens.numel() != B:
+        raise ValueError("splice_spans: shapes do not fit")
+    for t in (after, speech, speech_mask, out):
+        if not t.is_contiguous():
+            raise ValueError("splice_spans: tensors must be contiguous")
+    if after.dtype != torch.float32 or speech.dtype != torch.float32 or out.dtype != torch.float32 \
+            or speech_mask.element_size() != 1:
+        raise TypeError("splice_spans: after / speech / out fp32, speech_mask one byte per frame")
+    L.check(L.load().a3t_splice_spans(_ptr(after), _ptr(speech), _ptr(speech_mask), _ptr(_i32(spans, "spans")), _ptr(out),
+                                      _ptr(_i32(lens, "lens")), B, Tin, out.shape[1], C, _stream()), "splice_spans")
+
+
 def bias_act(x, bias, act, scale_=1.0):
     M, C = x.shape
     L.check(L.load().a3t_bias_act(_ptr(x), _ptr(bias), M, C, act, scale_, _stream()), "bias_act")

@@ -19,6 +19,37 @@ from . import ops
 from ._lib import ACT_RELU, F32
 
 
+def pwg_margin_frames(layers=30, stacks=3, kernel_size=3, upsample_scales: Sequence[int] = (4, 5, 3, 5),
+                      aux_context_window=2) -> int:
+    """How many mel frames to each side of a frame span the generator's output inside the span depends on.  The residual
+    stack (`stacks` x dilations 1 .. 2^(layers/stacks - 1), kernel k) reaches R = stacks * (2^(layers/stacks) - 1) * (k - 1) / 2
+    samples, the smoothing convolution of upsampling stage i (2 * scale_i + 1 taps at its own rate) scale_i * prod_{j>i} scale_j
+    samples, conv_in another aux_context_window frames: ceil((R + U) / hop) + aux_context_window.  14 for the v1 plan."""
+    scales = [int(x) for x in upsample_scales]
+    hop = int(np.prod(scales))
+    R = stacks * (2 ** (layers // stacks) - 1) * (kernel_size - 1) // 2
+    U = sum(sc * int(np.prod(scales[i + 1:])) for i, sc in enumerate(scales))
+    return -(-(R + U) // hop) + int(aux_context_window)
+
+
+def span_window(n0: int, n1: int, T: int, margin: int):
+    """Frame window [w0, w1) that has to be vocoded so that the samples of span [n0, n1) of a T-frame utterance come out as in
+    a run over the whole utterance: span +- margin, clipped to the utterance (where it is clipped the window's edge IS the
+    utterance's edge and the generator's edge rules are the right ones)."""
+    n0, n1 = max(0, min(int(n0), T)), max(0, min(int(n1), T))
+    return max(0, n0 - margin), min(T, max(n1, n0) + margin)
+
+
+def pwg_tile_list(lengths: Sequence[int], hop: int, tile: int = 256) -> np.ndarray:
+    """The work list of a3t_pwg_block_ragged: int32 [ntiles][4] = {row b, first sample t0, valid samples W_b = lengths[b] * hop,
+    0}, one entry per `tile`-sample tile that holds a valid sample, rows in order."""
+    W = np.asarray(lengths, dtype=np.int64) * hop
+    nt = (W + tile - 1) // tile
+    b = np.repeat(np.arange(len(W)), nt)
+    t0 = (np.arange(int(nt.sum())) - np.repeat(np.cumsum(nt) - nt, nt)) * tile
+    return np.stack([b, t0, W[b], np.zeros_like(b)], axis=1).astype(np.int32).reshape(-1, 4)
+
+
 class ParallelWaveGANGeneratorHIP:
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", layers=30, stacks=3, residual_channels=64,
                  gate_channels=128, skip_channels=64, aux_channels=80, aux_context_window=2,
@@ -73,8 +104,14 @@ class ParallelWaveGANGeneratorHIP:
         self.b_l3 = t("last_conv_layers.3.bias")
 
     @torch.no_grad()
-    def inference(self, c: torch.Tensor, z: Optional[torch.Tensor] = None, normalize_before: bool = False):
-        """c (T_feats, aux) [or (B, T_feats, aux)], z (T_wav, 1) noise -> (T_wav, 1) [or (B, T_wav, 1)]."""
+    def inference(self, c: torch.Tensor, z: Optional[torch.Tensor] = None, normalize_before: bool = False,
+                  lengths: Optional[Sequence[int]] = None):
+        """c (T_feats, aux) [or (B, T_feats, aux)], z (T_wav, 1) noise -> (T_wav, 1) [or (B, T_wav, 1)].
+
+        lengths (host integers, one per row of a (B, Tmax, aux) batch): row b is computed exactly as if c[b, :L_b] (and
+        z[b, :L_b * hop]) had been passed alone -- replicate padding, the smoothing and the dilated convolutions see the row's
+        own end -- and the result (B, Tmax * hop, 1) is zero behind L_b * hop.  What the padding of c and z holds reaches no
+        valid sample, and with the fused blocks the padding costs no time."""
         single = (c.dim() == 2)
         c = c.to(self.dev, torch.float32)
         if single:
@@ -82,6 +119,10 @@ class ParallelWaveGANGeneratorHIP:
         B, Tf, A = c.shape
         if normalize_before and self.stats is not None:
             c = (c - self.stats[0]) / self.stats[1]
+        if lengths is not None:
+            if single:
+                raise ValueError("lengths= goes with a (B, Tmax, aux) batch")
+            return self._inference_ragged(c, z, lengths)
         Tw = Tf * self.upsample_factor
         if z is None:
             z = torch.randn(B, Tw, 1, device=self.dev)
@@ -127,5 +168,75 @@ class ParallelWaveGANGeneratorHIP:
         ops.linear_fwd(h, self.w_l3, wav, bias=self.b_l3, compute=F32)
         wav = wav.view(B, Tw, 1)
         return wav[0] if single else wav
+
+    @property
+    def margin_frames(self) -> int:
+        """pwg_margin_frames of this generator's configuration (kernel size 3: the only one the class builds)."""
+        return pwg_margin_frames(self.layers, self.stacks, 3, self.scales, self.ctx)
+
+    def _inference_ragged(self, c, z, lengths):
+        """Rows of different length in the padded (B, Tmax) layout; lens on the device, nothing is repacked."""
+        B, Tf, A = c.shape
+        hop = self.upsample_factor
+        lengths = [int(x) for x in lengths]
+        if len(lengths) != B or any(n < 0 or n > Tf for n in lengths):
+            raise ValueError(f"lengths {lengths} do not fit a batch of {B} rows of {Tf} frames")
+        Tw = Tf * hop
+        dev = self.dev
+        # one H2D copy: lens [B] | tile list [ntiles][4] = {b, t0, W_b, 0} for the fused blocks (offset kept 16-byte aligned)
+        tl = pwg_tile_list(lengths, hop)
+        off = (B + 3) // 4 * 4
+        host = np.zeros(off + tl.size, dtype=np.int32)
+        host[:B] = lengths
+        host[off:] = tl.reshape(-1)
+        meta = torch.from_numpy(host).to(dev)
+        lens, tiles = meta[:B], meta[off:].view(len(tl), 4)
+        if z is None:
+            z = torch.randn(B, Tw, 1, device=dev)
+        z = z.to(dev, torch.float32).reshape(B * Tw, 1).contiguous()
+        w = self.ctx
+        Tp = Tf + 2 * w
+        cp = torch.empty(B * Tp, A, device=dev)
+        ops.replicate_pad_ragged(c.contiguous(), cp.view(B, Tp, A), lens, w)
+        ci = torch.empty(B * Tp, A, device=dev)
+        ops.conv_fwd(cp, self.w_in, ci, Tp, w, compute=F32)
+        cu = ci.view(B, Tp, A)[:, w:w + Tf].contiguous()
+        T, mul = Tf, 1
+        for sc, wk in zip(self.scales, self.w_up):
+            out = torch.empty(B, T * sc, A, device=dev)
+            ops.pwg_upsample_ragged(cu, wk, out, sc, lens, mul)
+            cu, T, mul = out, T * sc, mul * sc
+        cu = cu.view(B * Tw, A)
+        x = torch.empty(B * Tw, self.R, device=dev)
+        ops.linear_fwd(z, self.w_first, x, bias=self.b_first, compute=F32)
+        skips = torch.zeros(B * Tw, self.S, device=dev)
+        g = torch.empty(B * Tw, self.G // 2, device=dev)
+        lps = self.layers // self.stacks
+        if self.fused:
+            for l, blk in enumerate(self.blocks):
+                if tiles.shape[0]:
+                    ops.pwg_block_ragged(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], g, skips, tiles, B, Tw,
+                                         2 ** (l % lps))
+        else:
+            # layer by layer: the rows behind W_b of x are zeroed after every block, so that the convolution's taps beyond a
+            # row's end read zeros like those beyond Tmax; what the tail of y / g / o / skips holds never reaches a valid row
+            y = torch.empty(B * Tw, self.G, device=dev)
+            ca = torch.empty(B * Tw, self.G, device=dev)
+            o = torch.empty(B * Tw, self.R + self.S, device=dev)
+            ops.zero_tail(x, lens, hop, B, Tw)
+            for l, blk in enumerate(self.blocks):
+                ops.conv_fwd(x, blk["w"], y, Tw, 1, 2 ** (l % lps), bias=blk["b"], compute=F32)
+                ops.linear_fwd(cu, blk["aux"], ca, compute=F32)
+                ops.pwg_gate(y, ca, g)
+                ops.linear_fwd(g, blk["out"], o, bias=blk["bout"], compute=F32)
+                ops.pwg_res_skip(o, x, skips)
+                ops.zero_tail(x, lens, hop, B, Tw)
+        ops.bias_act(skips, None, ACT_RELU, math.sqrt(1.0 / self.layers))
+        h = torch.empty(B * Tw, self.S, device=dev)
+        ops.linear_fwd(skips, self.w_l1, h, bias=self.b_l1, act=ACT_RELU, compute=F32)
+        wav = torch.empty(B * Tw, 1, device=dev)
+        ops.linear_fwd(h, self.w_l3, wav, bias=self.b_l3, compute=F32)
+        ops.zero_tail(wav, lens, hop, B, Tw)
+        return wav.view(B, Tw, 1)
 
     __call__ = inference

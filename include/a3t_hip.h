@@ -374,6 +374,22 @@ int a3t_pwg_upsample(const float* c, const float* w, float* out, int64_t B, int6
 /* x [B][T][C] -> y [B][T + 2 pad][C], edge frames replicated per utterance */
 int a3t_replicate_pad(const float* x, float* y, int64_t B, int64_t T, int C, int pad, void* stream);
 int a3t_bias_act(float* x, const float* bias, int64_t M, int C, int act, float scale, void* stream);
+/* Ragged twins for batches of utterances of different length in the padded [B][Tmax] layout: lens [B] int32 on the device,
+ * row b is valid for lens[b] * mul rows and is computed exactly as if it had been passed alone.
+ * a3t_replicate_pad_ragged: the clamp is to [0, lens[b] - 1].  a3t_pwg_upsample_ragged: the stretched signal is zero outside
+ * [0, lens[b] * mul * scale), rows behind it are written as 0 (mul = product of the scales already applied).
+ * a3t_zero_tail: x [B][T][C], rows t >= lens[b] * mul are set to 0 (stores only). */
+int a3t_replicate_pad_ragged(const float* x, float* y, const int32_t* lens, int64_t B, int64_t T, int C, int pad,
+                             void* stream);
+int a3t_pwg_upsample_ragged(const float* c, const float* w, float* out, const int32_t* lens, int mul, int64_t B,
+                            int64_t Tin, int C, int scale, void* stream);
+int a3t_zero_tail(float* x, const int32_t* lens, int mul, int64_t B, int64_t T, int C, void* stream);
+/* Batched splice of the teacher-forced infill (decode_with_model, sedit_inference.py:612-637, one row per request):
+ * out [B][Tout][C] = after[b][t] for spans[b][0] <= t < spans[b][1], speech[b][t] for the other frames t < L_b, 0 behind;
+ * L_b = number of set bytes of speech_mask [B][Tin] (a prefix mask), also written to lens [B] int32.  after / speech
+ * [B][Tin][C] fp32, spans [B][2] int32. */
+int a3t_splice_spans(const float* after, const float* speech, const uint8_t* speech_mask, const int32_t* spans, float* out,
+                     int32_t* lens, int B, int Tin, int Tout, int C, void* stream);
 
 /* FastSpeech2 duration head (fastspeech/duration_predictor.py:77-95, inference): per row of z [M][C] -- the last predictor
  * conv after its bias and ReLU -- LayerNorm over C (eps, biased variance), x = LN(z) . w + bias[0] (Linear(C -> 1); bias
@@ -402,6 +418,11 @@ int a3t_dropout_bwd_cast(const float* g, void* gm, int gm_dtype, float* colsum, 
  * b0 [128] permuted the same way.  wt1 [64][128] = conv1x1_out.weight^T (columns 0..63 residual, 64..127 skip), b1 [128]. */
 int a3t_pwg_block(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1,
                   float* g, float* skips, int B, int Tw, int dil, void* stream);
+/* a3t_pwg_block over rows of different length: tiles [ntiles][4] int32 on the device (16-byte aligned) = {row b, first
+ * sample t0 (multiple of 256), valid samples W_b <= Tw of row b, 0}, one entry per 256-sample tile with t0 < W_b.  A tap at
+ * ts is zero unless 0 <= ts < W_b; rows behind W_b are neither read nor written; tiles that are not listed cost nothing. */
+int a3t_pwg_block_ragged(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1,
+                         float* g, float* skips, const int32_t* tiles, int ntiles, int B, int Tw, int dil, void* stream);
 
 /* On-device half of MLMCollateFn (espnet2/train/collate_fn.py:330-385): masked_position, speech / text segment ids and the
  * two padding masks painted from integer span lists.  fs / fe [B][P] int32: frame span of phone j (floor(fs * t / hop) taken

@@ -1,0 +1,225 @@
+"""Latency of batched speech editing (a3t_amd/sedit.py: SpeechEditor.edit_batch) against a loop of single edits, and of the
+ragged ParallelWaveGAN blocks against the padded ones.  Synthetic requests: utterances of --frames-range mel frames, a run of
+words in the middle replaced so that the new span has roughly 40 to 200 frames; model `c2` (BASELINE configs[1]: 6 + 6
+blocks, d = 384) or `tiny`, procedural weights, PWG v1 vocoder with random noise.  The duration model is a host-side stand-in
+(a table look-up), NOT the FastSpeech2 model of duration.py: its leg shows how often and where it is called, not what that
+model would cost.
+
+  A       loop of SpeechEditor.edit over the N requests (the single-request path)
+  B full  edit_batch(requests): one collate, one infill, one ragged vocoder call over whole utterances
+  B span  edit_batch(requests, outputs=("orgin_replaced",)): the vocoder sees span +- margin_frames only
+  order A, B full, B span, A again; wall time of the whole call (final copy included), median over --calls after warm-up,
+  reported per request.  `legs`: the stages of B run one by one with a synchronisation after each (their sum exceeds the
+  whole call, where host and device overlap).
+
+  kernel  the 30 residual blocks alone, B x T frames: a3t_pwg_block, a3t_pwg_block_ragged with all lengths equal (the tile
+          list's cost), and ragged lengths (expected near valid / padded samples of the padded run)
+
+    python tools/sedit_batch_latency.py [--models c2] [--compute bf16 f32] [--n 1 4 8] [--calls 50] [--warmup 5] [--kernel]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from dyneval_latency import LEX, phonemise, prompt  # noqa: E402
+
+
+def request(frames, k, oc, seed):
+    """A `frames`-frame utterance of three-phone words with k words in the middle replaced by k other words."""
+    from a3t_amd.sedit import EditRequest
+    words = max(k + 4, frames // 17)
+    wav, times2, w2p, old_str, _ = prompt(words, frames, oc.fs, oc.hop_length, seed=seed)
+    old = old_str.split()
+    names = sorted(n.lower() for n in LEX)
+    i = (words - k) // 2
+    new = old[:i] + [names[(names.index(w) + 1) % len(names)] for w in old[i:i + k]] + old[i + k:]
+    new_str = " ".join(new)
+    new_phns, new_w2p = phonemise(new_str)
+    return EditRequest(wav, times2, w2p, new_phns, new_w2p, old_str, new_str)
+
+
+def vocoder_state():
+    """PWG v1 with procedural weights; the smoothing kernels of the upsampling network normalised like trained ones."""
+    from oracle import a3t_oracle as O
+    state = O.procedural_state(O.pwg_param_shapes(O.PWGConfig()), seed=4)
+    for k in state:
+        if "up_layers" in k:
+            state[k] = np.abs(state[k]) / np.abs(state[k]).sum()
+    return state
+
+
+def editor(which, compute):
+    from a3t_amd.vocoder import ParallelWaveGANGeneratorHIP
+    from dyneval_latency import editor as base
+    ed, oc = base(which, compute)
+    ed.vocoder = ParallelWaveGANGeneratorHIP(vocoder_state(), device="cuda")
+    return ed, oc
+
+
+def timed(fn, calls, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return 1e3 * float(np.median(ts))
+
+
+def legs(ed, reqs, span_only, calls, warmup):
+    """The stages of edit_batch one by one, a synchronisation after each; ms per request."""
+    from a3t_amd.sedit import plan_batch
+    from a3t_amd.vocoder import span_window
+    acc = {k: [] for k in ("plan", "duration_model", "collate", "infill", "vocoder", "splice_copy")}
+    B, hop = len(reqs), ed.hop
+    for it in range(warmup + calls):
+        t_dur = [0.0]
+
+        def dur(phns):
+            t0 = time.perf_counter()
+            out = ed.duration_fn(phns)
+            t_dur[0] += time.perf_counter() - t0
+            return out
+
+        t = [time.perf_counter()]
+
+        def lap():
+            torch.cuda.synchronize()
+            t.append(time.perf_counter())
+
+        plans, data = plan_batch(reqs, ed.fs, hop, dur, ed.token_id_fn)
+        lap()
+        feats = ed.collate_fn(data)[1]
+        flen = [int(n) for n in feats["speech_mask"].reshape(B, -1).sum(-1).tolist()]
+        feats = {k: v.to("cuda") for k, v in feats.items() if k not in ("span_boundary", "speech_lengths", "text_lengths")}
+        lap()
+        with torch.no_grad():
+            mel, _ = ed.model.inference_batch(**feats, span_boundary=[p.new_span_boundary for p in plans])
+        lap()
+        if span_only:
+            m = ed.vocoder.margin_frames
+            win = [span_window(*p.new_span_boundary, flen[b], m) for b, p in enumerate(plans)]
+            c = mel.new_zeros(B, max(w1 - w0 for w0, w1 in win), mel.shape[2])
+            for b, (w0, w1) in enumerate(win):
+                c[b, :w1 - w0] = mel[b, w0:w1]
+        else:
+            win, c = [(0, n) for n in flen], mel
+        wav = ed.vocoder.inference(c, lengths=[w1 - w0 for w0, w1 in win])
+        lap()
+        wav = wav.reshape(B, -1).cpu().numpy()
+        for b, (p, r, (w0, w1)) in enumerate(zip(plans, reqs, win)):
+            n0, n1 = p.new_span_boundary
+            o0, o1 = p.old_span_boundary
+            np.concatenate([r.wav_org[:hop * o0], wav[b, hop * (n0 - w0):hop * (n1 - w0)], r.wav_org[hop * o1:]])
+        lap()
+        if it >= warmup:
+            d = np.diff(t)
+            for k, v in zip(("plan", "collate", "infill", "vocoder", "splice_copy"), d):
+                acc[k].append(v - (t_dur[0] if k == "plan" else 0.0))
+            acc["duration_model"].append(t_dur[0])
+    return {k: round(1e3 * float(np.median(v)) / B, 3) for k, v in acc.items()}
+
+
+def kernel_bench(frames, lengths_sets, reps=5):
+    """30 fused residual blocks on B x frames x hop samples: padded, ragged with equal lengths, ragged lengths; ms."""
+    from a3t_amd import ops
+    from a3t_amd.vocoder import ParallelWaveGANGeneratorHIP, pwg_tile_list
+    gen = ParallelWaveGANGeneratorHIP(vocoder_state(), device="cuda")
+    hop, out = gen.upsample_factor, {}
+    for name, lengths in lengths_sets.items():
+        B, Tw = len(lengths), frames * hop
+        # activations of the size the generator sees (first conv of unit noise, log-mel-like aux): x and skips start afresh in
+        # every run and the result is checked to be finite, so the gate's exp / rcp work on ordinary numbers
+        x0 = 0.1 * torch.randn(B * Tw, 64, device="cuda")
+        cu = 1.5 * torch.randn(B * Tw, 80, device="cuda") - 4.0
+        g = torch.empty(B * Tw, 64, device="cuda")
+        tiles = torch.from_numpy(pwg_tile_list(lengths, hop)).to("cuda")
+        equal = all(n == frames for n in lengths)
+
+        def run(ragged):
+            x, sk = x0.clone(), torch.zeros(B * Tw, 64, device="cuda")
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for l, blk in enumerate(gen.blocks):
+                if ragged:
+                    ops.pwg_block_ragged(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], g, sk, tiles, B, Tw, 2 ** (l % 10))
+                else:
+                    ops.pwg_block(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], g, sk, B, Tw, 2 ** (l % 10))
+            b.record()
+            torch.cuda.synchronize()
+            fin.append(bool(torch.isfinite(x).all()) and bool(torch.isfinite(sk).all()))
+            return a.elapsed_time(b)
+
+        fin = []
+        run(False), run(True)
+        seq = ["padded", "ragged", "padded", "ragged", "padded"]          # padded first, between and last: its own spread
+        ts = {k: [] for k in ("padded", "ragged")}
+        for _ in range(reps):
+            for k in seq:
+                ts[k].append(run(k == "ragged"))
+        out[name] = dict(lengths=list(lengths), padded_ms=round(float(np.median(ts["padded"])), 3),
+                         padded_min_max_ms=[round(min(ts["padded"]), 3), round(max(ts["padded"]), 3)],
+                         ragged_ms=round(float(np.median(ts["ragged"])), 3),
+                         ragged_min_max_ms=[round(min(ts["ragged"]), 3), round(max(ts["ragged"]), 3)],
+                         valid_over_padded=round(sum(lengths) / (B * frames), 3), all_equal=equal, finite=all(fin))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--models", nargs="+", default=["c2"])
+    ap.add_argument("--compute", nargs="+", default=["bf16", "f32"])
+    ap.add_argument("--n", type=int, nargs="+", default=[1, 4, 8])
+    ap.add_argument("--frames-range", type=int, nargs=2, default=[300, 1000])
+    ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--kernel", action="store_true")
+    a = ap.parse_args()
+    prop = torch.cuda.get_device_properties(0)
+    out = {"device": f"{prop.name} ({getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs)"}
+    if a.kernel:
+        out["pwg_blocks"] = kernel_bench(1000, {"8x1000": [1000] * 8, "ragged": [1000, 700, 500, 300] * 2})
+    for which in a.models:
+        for compute in a.compute:
+            ed, oc = editor(which, compute)
+            for n in a.n:
+                rs = np.random.RandomState(n)
+                lo, hi = a.frames_range
+                reqs = [request(int(f), int(k), oc, seed=10 * n + i)
+                        for i, (f, k) in enumerate(zip(np.linspace(hi, lo, n).astype(int) if n > 1 else [(lo + hi) // 2],
+                                                       rs.randint(3, 11, n)))]
+                args = [(r.wav_org, r.times2, r.word2phns, r.new_phns, r.new_word2phns, r.old_str, r.new_str) for r in reqs]
+
+                def loop():
+                    for x in args:
+                        ed.edit(*x)
+
+                r = {"A_loop_of_edit_ms": round(timed(loop, a.calls, a.warmup) / n, 3),
+                     "B_full_ms": round(timed(lambda: ed.edit_batch(reqs), a.calls, a.warmup) / n, 3),
+                     "B_span_only_ms": round(timed(lambda: ed.edit_batch(reqs, outputs=("orgin_replaced",)), a.calls,
+                                                   a.warmup) / n, 3),
+                     "A_again_ms": round(timed(loop, a.calls, a.warmup) / n, 3)}
+                got = ed.edit_batch(reqs, outputs=("orgin_replaced",))
+                r["frames"] = [int(g["feat"].shape[0]) for g in got]
+                r["span_frames"] = [int(g["new_span_boundary"][1] - g["new_span_boundary"][0]) for g in got]
+                r["legs_full_ms"] = legs(ed, reqs, False, max(5, a.calls // 5), 2)
+                r["legs_span_only_ms"] = legs(ed, reqs, True, max(5, a.calls // 5), 2)
+                out[f"{which}.{compute}.n{n}"] = r
+                print(json.dumps({f"{which}.{compute}.n{n}": r}), flush=True)
+    print(json.dumps({"sedit_batch_latency": out}))
+
+
+if __name__ == "__main__":
+    main()
