@@ -101,6 +101,10 @@ _SIGS = {
     "a3t_replicate_pad_ragged": [_P, _P, _P, c_int64, c_int64, c_int, c_int, _P],
     "a3t_pwg_upsample_ragged": [_P, _P, _P, _P, c_int, c_int64, c_int64, c_int, c_int, _P],
     "a3t_zero_tail": [_P, _P, c_int, c_int64, c_int64, c_int, _P],
+    "a3t_layernorm_fwd_ragged": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P],
+    "a3t_glu_dwconv_fwd_ragged": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
+    "a3t_relpos_softmax_fwd_ragged": [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_float,
+                                      _P],
     "a3t_splice_spans": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_pwg_block_ragged": [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_duration_head": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P],

@@ -7,8 +7,10 @@ twice per edit with duration_adjust).  Only the part of FastSpeech2 that duratio
   - the x-vector integration (espnet2/tts/fastspeech2/fastspeech2.py:784-808, "add" or "concat");
   - the DurationPredictor (espnet/nets/pytorch_backend/fastspeech/duration_predictor.py) in inference mode: k-tap convs
     with ReLU and LayerNorm, then a3t_duration_head (last LayerNorm, Linear(C -> 1), clamp(round(exp(x) - offset), 0)).
-fp32 compute, eval mode.  Every phone sequence runs as its own B = 1 forward at its exact length n + 1 (the appended eos):
-legacy rel-pos attention reads pe[:T] and the conv module does not mask padded frames, so padding would change the result.
+fp32 compute, eval mode.  A single phone sequence runs as its own B = 1 forward at its exact length n + 1 (the appended eos):
+legacy rel-pos attention reads pe[:T] and the conv module does not mask padded frames, so plain padding would change the
+result.  Several sequences run as ONE padded forward with per-row lengths (forward_ids_batch): the engine's ragged block
+forward gives every row what it would get alone -- rel_shift at the row's own length, zeros behind it for every k-tap conv.
 """
 import math
 import os
@@ -223,6 +225,7 @@ class FS2DurationModel:
         self._keys1 = torch.ones(cfg.max_len, dtype=torch.uint8, device=self.dev)       # no padded keys: B = 1, exact T
         self._ids_host = torch.zeros(cfg.max_len, dtype=torch.int64, pin_memory=self.dev.type == "cuda")
         self._ids_dev = torch.zeros(cfg.max_len, dtype=torch.int64, device=self.dev)
+        self._stage_host = self._stage_dev = None       # predict_frames_batch: ids and lengths of one call, grow-only
 
     # ---- loading ---------------------------------------------------------------------------------------------------------
     def load_state_dict(self, sd):
@@ -299,6 +302,131 @@ class FS2DurationModel:
                           eps=1e-12, offset=c.dp_offset)
         return hs, logd, frames
 
+    def forward_ids_batch(self, ids, lens, spk_bias=None):
+        """ids: device int64 [B][Tmax] (eos included; entries behind a row's length: any valid id), lens: device int32 [B],
+        1 <= lens[b] <= Tmax.  One padded forward whose row b is computed as forward_ids computes it alone at lens[b]
+        (MLMEngine.block_fwd with lens); one speaker bias for the whole call.  Returns device tensors (hs [B][Tmax][d],
+        logd [B][Tmax], frames [B][Tmax] int64) valid until the next call; entries behind lens[b] are finite and mean nothing
+        (hs is 0 there when the predictor's convs have more than one tap).
+        The number of launches does not depend on B."""
+        c, p, ws = self.c, self.store.p, self.ws
+        if ids.dim() != 2 or ids.dtype != torch.int64 or not ids.is_contiguous():
+            raise ValueError("ids must be a contiguous int64 [B][Tmax] tensor")
+        B, T, d = int(ids.shape[0]), int(ids.shape[1]), c.adim
+        if not 1 <= T <= c.max_len:
+            raise ValueError(f"sequence length {T} outside 1..{c.max_len}")
+        if spk_bias is not None and c.spk_embed_dim <= 0:
+            raise ValueError("spk_bias given but the checkpoint has no x-vector projection")
+        eng, M = self.eng, B * T
+        if self._tpos0.numel() < M:
+            self._tpos0 = torch.zeros(M, dtype=torch.int64, device=self.dev)
+        tpos = self._tpos0[:M]
+        xs = ws.get("emb.xs", (M, d))
+        ops.embed_finish_fwd(None, p["temb"], self._seg0, ids, None, tpos, xs, B, 0, T, d, math.sqrt(d))
+        pos = eng.pe[:T]
+        x = xs
+        for i in range(c.enc_blocks):
+            x = eng.block_fwd(f"enc.{i}", x, pos, None, B, T, lens=lens)
+        hs = eng._ln_fwd("enc.after", x, "enc.after", out_dtype=torch.float32)
+        if spk_bias is not None:
+            if c.spk_integration == "add":
+                ops.bias_act(hs, spk_bias, ACT_NONE)
+            else:
+                hc = ws.get("spk.hs", (M, d))
+                ops.linear_fwd(hs, p["spk.wh"], hc, bias=spk_bias.view(-1), compute=F32)
+                hs = hc
+        y, pad = hs, (c.dp_kernel - 1) // 2
+        if pad > 0:      # the predictor's first conv reads zeros behind every row's length
+            ops.zero_tail(hs, lens, 1, B, T)
+        for l in range(c.dp_layers):
+            z = ws.get(f"dp.{l}.z", (M, c.dp_chans))
+            ops.conv_fwd(y, p[f"dp.{l}.w"], z, T, pad, bias=p[f"dp.{l}.b"], act=ACT_RELU, compute=F32)
+            if l < c.dp_layers - 1:
+                y = eng._ln_fwd(f"dp.{l}.ln", z, f"dp.{l}.ln", out_dtype=torch.float32,
+                                lens=lens if pad > 0 else None, T=T)
+        logd = ws.get("dp.logd", (M,))
+        frames = ws.get("dp.frames", (M,), torch.int64)
+        l = c.dp_layers - 1
+        ops.duration_head(z, p[f"dp.{l}.ln.g"], p[f"dp.{l}.ln.b"], p["dp.lin.w"], p["dp.lin.b"], logd, frames,
+                          eps=1e-12, offset=c.dp_offset)
+        return hs.view(B, T, d), logd.view(B, T), frames.view(B, T)
+
+    def _chunks(self, lengths, max_score_elems):
+        """Indices of `lengths` sorted by length and cut into consecutive chunks with B * H * Tmax^2 <= max_score_elems
+        (Tmax = the chunk's longest = last row); a row too long for the cap runs alone."""
+        order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
+        H, out, cur = self.c.heads, [], []
+        for i in order:
+            if cur and (len(cur) + 1) * H * lengths[i] ** 2 > max_score_elems:
+                out.append(cur)
+                cur = []
+            cur.append(i)
+        if cur:
+            out.append(cur)
+        return out
+
+    def predict_frames_batch(self, phn_lists, spk_bias=None, max_score_elems: int = 1 << 24) -> List[np.ndarray]:
+        """predict_frames for several phone lists: one int64 array per list (eos entry included), in the order given.
+        The ids of all lists go up through one pinned buffer in one copy and all frames come down in one: one host
+        synchronisation per call.  The lists are sorted by length and cut into chunks of B rows padded to the chunk's longest,
+        each chunk one forward_ids_batch.  max_score_elems caps B * H * Tmax^2 of a chunk, the size of each of the three
+        score-sized fp32 tensors of the materialised attention (content scores, position scores, probabilities): the default
+        2^24 holds them to 192 MiB together, and e.g. 90 lists of 300 phones at H = 2 still make one chunk.  A list longer
+        than the cap allows runs alone.  A chunk of one list, and so a call with one list, takes the B = 1 path of
+        predict_frames; every row of a larger chunk is computed as if alone, so the frames do not depend on the chunking."""
+        lists = [self.tokens_to_ids(list(ph)) for ph in phn_lists]
+        if not lists:
+            return []
+        if len(lists) == 1:
+            return [self.predict_frames(list(phn_lists[0]), spk_bias)]
+        lengths = [len(x) for x in lists]
+        if max(lengths) > self.c.max_len:
+            raise ValueError(f"{max(lengths)} tokens: more than max_len {self.c.max_len}")
+        chunks = self._chunks(lengths, int(max_score_elems))
+        # staging layout (int64 words): per chunk its padded ids [B][Tmax], then all lengths as int32 pairs
+        offs, n_ids = [], 0
+        for ch in chunks:
+            offs.append(n_ids)
+            n_ids += len(ch) * lengths[ch[-1]]
+        n_len = (len(lists) + 1) // 2
+        total = n_ids + n_len
+        if self._stage_host is None or self._stage_host.numel() < total:
+            cap = max(total, 2 * (self._stage_host.numel() if self._stage_host is not None else 0))
+            self._stage_host = torch.zeros(cap, dtype=torch.int64, pin_memory=self.dev.type == "cuda")
+            self._stage_dev = torch.zeros(cap, dtype=torch.int64, device=self.dev)
+        # the pinned staging buffer is free again: the previous call's copy finished before its result reached the host
+        host = np.zeros(total, np.int64)
+        hl = host[n_ids:].view(np.int32)
+        r = 0
+        for ch, o in zip(chunks, offs):
+            T = lengths[ch[-1]]
+            blk = host[o:o + len(ch) * T].reshape(len(ch), T)
+            for k, i in enumerate(ch):
+                blk[k, :lengths[i]] = lists[i]
+                hl[r + k] = lengths[i]
+            r += len(ch)
+        self._stage_host[:total].copy_(torch.from_numpy(host))
+        dev = self._stage_dev[:total]
+        dev.copy_(self._stage_host[:total], non_blocking=True)
+        dev_lens = dev[n_ids:].view(torch.int32)
+        out = self.ws.get("dp.frames.all", (n_ids,), torch.int64)
+        r = 0
+        for ch, o in zip(chunks, offs):
+            B, T = len(ch), lengths[ch[-1]]
+            if B == 1:
+                _, _, frames = self.forward_ids(dev[o:o + T], spk_bias)
+            else:
+                _, _, frames = self.forward_ids_batch(dev[o:o + B * T].view(B, T), dev_lens[r:r + B], spk_bias)
+            out[o:o + B * T].copy_(frames.reshape(-1))
+            r += B
+        got = out.cpu().numpy()
+        res = [None] * len(lists)
+        for ch, o in zip(chunks, offs):
+            T = lengths[ch[-1]]
+            for k, i in enumerate(ch):
+                res[i] = got[o + k * T:o + k * T + lengths[i]].copy()
+        return res
+
     def predict_frames(self, phns, spk_bias=None) -> np.ndarray:
         """Frames per phone of `phns` plus the eos entry (int64, host).  One host synchronisation."""
         ids = self.tokens_to_ids(phns)
@@ -315,11 +443,20 @@ class FS2DurationModel:
     def duration_fn(self, fs: int, hop_length: int, spembs=None):
         """duration_predict(phns, fs, hop_length, ...) of sedit_inference.py:398-425 as a callable for
         SpeechEditor(duration_fn=...): seconds per phone, frames * hop_length / fs in float32 as the reference computes it,
-        eos dropped.  spembs=None runs without the x-vector integration, as duration_predict does with sid=None."""
+        eos dropped.  spembs=None runs without the x-vector integration, as duration_predict does with sid=None.
+        The callable's .batch(list of phone lists) answers several lists from one batched forward (SpeechEditor.plan_batch
+        uses it when it is there)."""
         bias = self.speaker_bias(spembs) if spembs is not None else None
         hop, fs32 = int(hop_length), np.float32(fs)
 
-        def fn(phns):
-            frames = self.predict_frames(list(phns), bias)
+        def seconds(frames):
             return ((frames * hop).astype(np.float32) / fs32)[:-1].tolist()
+
+        def fn(phns):
+            return seconds(self.predict_frames(list(phns), bias))
+
+        def batch(phn_lists, max_score_elems: int = 1 << 24):
+            """One list of seconds per phone list, from one predict_frames_batch call (one host synchronisation)."""
+            return [seconds(f) for f in self.predict_frames_batch(list(phn_lists), bias, max_score_elems)]
+        fn.batch = batch
         return fn

@@ -385,13 +385,18 @@ class MLMEngine:
     def _act(self, name, shape):
         return self.ws.get(name, shape, self.adt)
 
-    def _ln_fwd(self, tag, x, pre, eps=1e-12, out_dtype=None):
+    def _ln_fwd(self, tag, x, pre, eps=1e-12, out_dtype=None, lens=None, T=0):
+        """lens (device int32 [B], rows of T frames): rows t >= lens[b] are stored as 0 -- the input of a k-tap convolution of a
+        ragged batch (_check_ragged)."""
         p = self.store.p
         M, D = x.shape
         y = self.ws.get(tag + ".y", (M, D), out_dtype or self.adt)
         mean = self.ws.get(tag + ".mean", (M,))
         rstd = self.ws.get(tag + ".rstd", (M,))
-        ops.layernorm_fwd(x, p[pre + ".g"], p[pre + ".b"], y, mean, rstd, eps)
+        if lens is not None:
+            ops.layernorm_fwd_ragged(x, p[pre + ".g"], p[pre + ".b"], y, mean, rstd, lens, M // T, T, eps)
+        else:
+            ops.layernorm_fwd(x, p[pre + ".g"], p[pre + ".b"], y, mean, rstd, eps)
         self.sv[tag] = (x, y, mean, rstd)
         return y
 
@@ -550,11 +555,13 @@ class MLMEngine:
             torch.cuda.current_stream().wait_stream(self.side)
 
     # ------------------------------------------------------------------ FFN (MultiLayeredConv1d)
-    def _ffn_fwd(self, tag, pre, x, T):
+    def _ffn_fwd(self, tag, pre, x, T, lens=None):
         p, c = self.store.p, self.c
         M = x.shape[0]
         pad = (c.ff_kernel - 1) // 2
-        y = self._ln_fwd(tag + ".ln", x, pre + ".ln")
+        if lens is not None and pad == 0:      # pointwise convs read no neighbour: nothing to zero
+            lens = None
+        y = self._ln_fwd(tag + ".ln", x, pre + ".ln", lens=lens, T=T)
         h = self._act(tag + ".h", (M, c.ff))
         keep, lay = None, 0
         if self._ffn_plan(M)[0]:  # one bit per element of h (value > 0 after relu / dropout) for the backward mask
@@ -563,6 +570,8 @@ class MLMEngine:
             keep, lay = self.ws.get(tag + ".keep4", (M * c.ff // 4,), torch.uint8), 1
         ops.conv_fwd(y, self.W(pre + ".w1"), h, T, pad, bias=p[pre + ".b1"], act=ACT_RELU, compute=self.cmp,
                      drop=self._drop(c.dropout_rate, tag + ".h"), keep_out=keep, keep_layout=lay)
+        if lens is not None:      # the second conv's taps read zeros behind every row's length, not relu(b1 + ...)
+            ops.zero_tail(h, lens, 1, M // T, T)
         xo = self.ws.get(tag + ".xo", (M, c.adim))
         ops.conv_fwd(h, self.W(pre + ".w2"), xo, T, pad, bias=p[pre + ".b2"], R=x, alpha=0.5, compute=self.cmp,
                      drop=self._drop(c.dropout_rate, tag + ".o"))
@@ -608,7 +617,7 @@ class MLMEngine:
         return g
 
     # ------------------------------------------------------------------ rel-pos self-attention
-    def _mha_fwd(self, tag, pre, x, pos, keymask, B, T):
+    def _mha_fwd(self, tag, pre, x, pos, keymask, B, T, lens=None):
         p, c = self.store.p, self.c
         d, H, dk = c.adim, c.heads, c.dk
         M = B * T
@@ -616,6 +625,8 @@ class MLMEngine:
         y = self._ln_fwd(tag + ".ln", x, pre + ".ln")
         qkv = self._act(tag + ".qkv", (M, 3 * d))
         ops.linear_fwd(y, self.W(pre + ".wqkv"), qkv, bias=p[pre + ".bqkv"], compute=cmp)
+        if lens is not None:
+            return self._mha_fwd_ragged(tag, pre, x, qkv, pos, lens, B, T)
         # q + pos_bias_u / q + pos_bias_v (attention.py:190-194): the fused kernels add the biases as they load their query
         # fragments (bit for bit what a3t_add_pos_bias stores); the two [M][d] tensors only exist for the materialised forward and,
         # in the backward, as operands of the dK / d linear_pos products (made there, off the main stream)
@@ -694,6 +705,38 @@ class MLMEngine:
         ops.linear_fwd(ctx, self.W(pre + ".wo"), xo, bias=p[pre + ".bo"], R=x, compute=cmp,
                        drop=self._drop(c.dropout_rate, tag + ".o"))
         self.sv[tag] = (y, qkv, qu, qv, P, probs, ctx, pos, pdrop)
+        return xo
+
+    def _mha_fwd_ragged(self, tag, pre, x, qkv, pos, lens, B, T):
+        """The materialised forward over rows of their own length (fp32, forward only): the key mask is j < lens[b] and the
+        legacy rel_shift is taken at lens[b] (a3t_relpos_softmax_fwd_ragged).  P = linear_pos(pe[:T]) serves every row: its
+        first n rows are pe[:n] projected.  Query rows behind a row's length come out as 0 from the softmax, so the probs @ V
+        product and what follows stay finite there; no valid row reads them."""
+        p, c = self.store.p, self.c
+        d, H, dk = c.adim, c.heads, c.dk
+        M = B * T
+        cmp = self.cmp
+        qu = self._act(tag + ".qu", (M, d))
+        qv = self._act(tag + ".qv", (M, d))
+        ops.add_pos_bias(qkv, p[pre + ".u"], p[pre + ".v"], qu, qv)
+        P = self._act(tag + ".P", (T, d))
+        ops.linear_fwd(pos, self.W(pre + ".wpos"), P, compute=cmp)
+        ac = self.ws.get("tmp.ac", (B, H, T, T))
+        bd = self.ws.get("tmp.bd", (B, H, T, T))
+        kk = qkv.view(-1)[d:]
+        vv = qkv.view(-1)[2 * d:]
+        ops.gemm(qu, kk, ac, T, T, dk, d, 1, 3 * d, 1, T, batch=B * H, batch_inner=H, a_bs=(T * d, dk),
+                 b_bs=(T * 3 * d, dk), c_bs=(H * T * T, T * T), compute=cmp)
+        ops.gemm(qv, P, bd, T, T, dk, d, 1, d, 1, T, batch=B * H, batch_inner=H, a_bs=(T * d, dk), b_bs=(0, dk),
+                 c_bs=(H * T * T, T * T), compute=cmp)
+        probs = self._act(tag + ".probs", (B, H, T, T))
+        ops.relpos_softmax_fwd_ragged(ac, bd, lens, probs, B, H, T, 1.0 / math.sqrt(dk))
+        ctx = self._act(tag + ".ctx", (M, d))
+        ops.gemm(probs, vv, ctx, T, dk, T, T, 1, 1, 3 * d, d, batch=B * H, batch_inner=H,
+                 a_bs=(H * T * T, T * T), b_bs=(T * 3 * d, dk), c_bs=(T * d, dk), compute=cmp)
+        xo = self.ws.get(tag + ".xo", (M, d))
+        ops.linear_fwd(ctx, self.W(pre + ".wo"), xo, bias=p[pre + ".bo"], R=x, compute=cmp)
+        self.sv[tag] = None          # forward only: nothing is kept for a backward
         return xo
 
     def _mha_bwd(self, tag, pre, g, B, T, nb=None, nxt=None):
@@ -872,7 +915,7 @@ class MLMEngine:
         ops.bn_act_bwd(dy, z, mean, rstd, p[pre + ".g"], p[pre + ".b"], sums, dz, gr[pre + ".g"], gr[pre + ".b"],
                        self.training, act, zero=False)
 
-    def _conv_fwd(self, tag, pre, x, T):
+    def _conv_fwd(self, tag, pre, x, T, lens=None):
         p, c = self.store.p, self.c
         M, d = x.shape
         cmp = self.cmp
@@ -881,7 +924,10 @@ class MLMEngine:
         ops.linear_fwd(y, self.W(pre + ".pw1"), g2, bias=p[pre + ".pb1"], compute=cmp)
         glu = self._act(tag + ".glu", (M, d))
         z = self.ws.get(tag + ".z", (M, d))
-        ops.glu_dwconv_fwd(g2, p[pre + ".dw"], p[pre + ".db"], glu, z, T)
+        if lens is not None:
+            ops.glu_dwconv_fwd_ragged(g2, p[pre + ".dw"], p[pre + ".db"], glu, z, lens, M // T, T)
+        else:
+            ops.glu_dwconv_fwd(g2, p[pre + ".dw"], p[pre + ".db"], glu, z, T)
         s = self._act(tag + ".s", (M, d))
         self._bn_fwd(tag, z, pre + ".bn", pre + ".bn", ACT_SWISH, s)
         xo = self.ws.get(tag + ".xo", (M, d))
@@ -915,12 +961,26 @@ class MLMEngine:
         return g
 
     # ------------------------------------------------------------------ one Conformer block
-    def block_fwd(self, pre, x, pos, keymask, B, T):
+    def _check_ragged(self, lens, B):
+        if self.bf16 or self.training or self._need_grad:
+            raise ValueError("lens: ragged rows need an engine in fp32 compute, eval mode, forward only "
+                             f"(compute={'bf16' if self.bf16 else 'f32'}, training={self.training}, "
+                             f"need_grad={self._need_grad})")
+        if lens.dtype != torch.int32 or lens.numel() != B or lens.device.type != self.dev.type:
+            raise ValueError(f"lens must be an int32 tensor of {B} entries on {self.dev}")
+
+    def block_fwd(self, pre, x, pos, keymask, B, T, lens=None):
+        """lens (device int32 [B]): the rows of the padded [B][T] batch have their own lengths and row b comes out as if it had
+        been passed alone at lens[b]: keys j >= lens[b] are masked (keymask is not read), the legacy rel_shift is taken at
+        lens[b], and every convolution with more than one tap reads zeros behind lens[b].  Rows behind a length hold finite
+        values nobody reads.  fp32 compute, eval mode, forward only."""
         # (encoder_layer.py:117-181)
-        x = self._ffn_fwd(pre + ".ffm", pre + ".ffm", x, T)
-        x = self._mha_fwd(pre + ".mha", pre + ".mha", x, pos, keymask, B, T)
-        x = self._conv_fwd(pre + ".cnv", pre + ".cnv", x, T)
-        x = self._ffn_fwd(pre + ".ff", pre + ".ff", x, T)
+        if lens is not None:
+            self._check_ragged(lens, B)
+        x = self._ffn_fwd(pre + ".ffm", pre + ".ffm", x, T, lens)
+        x = self._mha_fwd(pre + ".mha", pre + ".mha", x, pos, keymask, B, T, lens)
+        x = self._conv_fwd(pre + ".cnv", pre + ".cnv", x, T, lens)
+        x = self._ffn_fwd(pre + ".ff", pre + ".ff", x, T, lens)
         return self._ln_fwd(pre + ".fin", x, pre + ".fin.ln", out_dtype=torch.float32)
 
     def block_bwd(self, pre, g, B, T):

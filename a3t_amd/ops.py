@@ -580,6 +580,42 @@ def zero_tail(x, lens, mul, B, T):
     L.check(L.load().a3t_zero_tail(_ptr(x), _ptr(_i32(lens, "lens")), mul, B, T, C, _stream()), "zero_tail")
 
 
+def _ragged_f32(what, *ts):
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError(f"{what}: tensors must be contiguous fp32")
+
+
+def layernorm_fwd_ragged(x, g, b, y, mean, rstd, lens, B, T, eps):
+    """layernorm_fwd over x [B*T][D] whose rows t >= lens[b] are stored as 0; mean / rstd: both or None."""
+    M, D = x.shape
+    _ragged_f32("layernorm_fwd_ragged", x, y, mean, rstd)
+    if M != B * T or y.shape != x.shape or lens.numel() != B:
+        raise ValueError("layernorm_fwd_ragged: shapes do not fit")
+    L.check(L.load().a3t_layernorm_fwd_ragged(_ptr(x), _ptr(g), _ptr(b), _ptr(y), _ptr(mean), _ptr(rstd),
+                                              _ptr(_i32(lens, "lens")), B, T, D, eps, _stream()), "ln_fwd_ragged")
+
+
+def glu_dwconv_fwd_ragged(g, wdw, bdw, glu, z, lens, B, Tseq):
+    """glu_dwconv_fwd whose taps read 0 behind lens[b]; glu and z are 0 there."""
+    M, C = glu.shape
+    _ragged_f32("glu_dwconv_fwd_ragged", g, glu, z)
+    if M != B * Tseq or g.shape != (M, 2 * C) or z.shape != glu.shape or lens.numel() != B:
+        raise ValueError("glu_dwconv_fwd_ragged: shapes do not fit")
+    L.check(L.load().a3t_glu_dwconv_fwd_ragged(_ptr(g), _ptr(wdw), _ptr(bdw), _ptr(glu), _ptr(z), _ptr(_i32(lens, "lens")),
+                                               B, Tseq, C, wdw.shape[1], _stream()), "glu_dwconv_fwd_ragged")
+
+
+def relpos_softmax_fwd_ragged(ac, bd, lens, probs, B, H, T, scale):
+    """relpos_softmax_fwd with per-row lengths: key mask j < lens[b], rel_shift at lens[b], query rows behind it 0.  The
+    library refuses anything but fp32 scores and probabilities."""
+    if min(ac.numel(), bd.numel(), probs.numel()) < B * H * T * T or lens.numel() != B:
+        raise ValueError("relpos_softmax_fwd_ragged: shapes do not fit")
+    L.check(L.load().a3t_relpos_softmax_fwd_ragged(_ptr(ac), _ptr(bd), _dt(ac), _ptr(_i32(lens, "lens")), _ptr(probs),
+                                                   _dt(probs), B, H, T, T * T, T * T, T * T, scale, _stream()),
+            "softmax_fwd_ragged")
+
+
 def pwg_block_ragged(x, cu, wt0, b0, wt1, b1, g, skips, tiles, B, Tw, dil):
     """Fused residual block over rows of different length (a3t_pwg_block_ragged); tiles: device int32 [ntiles][4] =
     {row b, first sample t0, valid samples W_b, 0} (vocoder.pwg_tile_list).  The kernel indexes x / cu / g / skips with the list's

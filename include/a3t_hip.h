@@ -384,6 +384,23 @@ int a3t_replicate_pad_ragged(const float* x, float* y, const int32_t* lens, int6
 int a3t_pwg_upsample_ragged(const float* c, const float* w, float* out, const int32_t* lens, int mul, int64_t B,
                             int64_t Tin, int C, int scale, void* stream);
 int a3t_zero_tail(float* x, const int32_t* lens, int mul, int64_t B, int64_t T, int C, void* stream);
+/* Length-aware twins of three row kernels for the batched duration model (csrc/ragged_rows.hip): fp32, forward only, padded
+ * [B][T] rows with lens [B] int32 on the device, n = lens[b] (clamped to 0..T); row b gets what it would get alone at length n.
+ * a3t_layernorm_fwd_ragged: a3t_layernorm_fwd over x [B*T][D] (same arithmetic) whose rows t >= n are stored as 0 -- what a
+ *   k-tap convolution behind it has to read there; mean / rstd [B*T] optional (both or neither; 0 for the rows behind n).
+ * a3t_glu_dwconv_fwd_ragged: a3t_glu_dwconv_fwd (g [B*Tseq][2C] -> glu, z [B*Tseq][C]) whose taps read 0 for t >= n and across
+ *   the row boundary; glu and z are stored as 0 for t >= n.  K odd, <= 31.
+ * a3t_relpos_softmax_fwd_ragged: a3t_relpos_softmax_fwd without dropout whose key mask is j < n and whose legacy rel_shift is
+ *   taken at n in the place of T on the compact bd of the padded launch (row stride T): for i, j < n, j <= i -> bd[i][n-1-i+j],
+ *   j == i+1 -> 0, j > i+1 -> bd[i+1][j-i-2].  Keys j >= n get probability 0 and query rows i >= n are written as 0, so the
+ *   probs @ V product reads nothing undefined.  fp32 scores and probabilities only (A3T_EINVAL otherwise); *_bs >= T*T. */
+int a3t_layernorm_fwd_ragged(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
+                             const int32_t* lens, int B, int T, int D, float eps, void* stream);
+int a3t_glu_dwconv_fwd_ragged(const float* g, const float* wdw, const float* bdw, float* glu, float* z, const int32_t* lens,
+                              int B, int Tseq, int C, int K, void* stream);
+int a3t_relpos_softmax_fwd_ragged(const void* ac, const void* bd, int scores_dtype, const int32_t* lens, void* probs,
+                                  int probs_dtype, int B, int H, int T, int64_t ac_bs, int64_t bd_bs, int64_t p_bs,
+                                  float scale, void* stream);
 /* Batched splice of the teacher-forced infill (decode_with_model, sedit_inference.py:612-637, one row per request):
  * out [B][Tout][C] = after[b][t] for spans[b][0] <= t < spans[b][1], speech[b][t] for the other frames t < L_b, 0 behind;
  * L_b = number of set bytes of speech_mask [B][Tin] (a prefix mask), also written to lens [B] int32.  after / speech

@@ -5,6 +5,17 @@ procedural weights.  Launch counts: run under `rocprofv3 --kernel-trace --stats 
 --calls 1 --warmup 0` and divide the dispatch count by the number of calls (one per length).
 
     python tools/duration_latency.py [--phones 60 300] [--calls 50] [--warmup 5]
+
+--batch N [N ...]: the batched path instead.  For every N, N distinct lists of 20-120 phones (seeded); wall time per list of
+(A) a loop of N single calls and (B) one `.batch` call of the same lists, measured in the order A, B, A in one process,
+median of --calls repetitions after --warmup.  The yardstick of B is A in the same run; the spread between the two A runs is
+the noise a difference has to exceed.  Every N also checks that B returns what A returns.
+
+    python tools/duration_latency.py --batch 1 2 8 16
+
+Launches of ONE batched forward: --batch N --only B --calls K --warmup 0 makes exactly K `.batch` calls and nothing else after
+the model is built, so the dispatch counts of two `rocprofv3 --kernel-trace --stats` runs with K = 1 and K = 2 differ by the
+launches of one call (copies to the staging buffers and torch's own kernels included).
 """
 import argparse
 import json
@@ -19,11 +30,55 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def _timed(call, calls, warmup):
+    """Wall times (s) of `calls` repetitions of call() after `warmup`; every call ends with its frames on the host."""
+    for _ in range(warmup):
+        call()
+    ts = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        call()
+        ts.append(time.perf_counter() - t0)
+    return ts
+
+
+def batch_latency(fn, phones, a, rs):
+    out = {}
+    for n in a.batch:
+        lists, seen = [], set()
+        while len(lists) < n:
+            ph = tuple(phones[i] for i in rs.randint(0, len(phones), rs.randint(20, 121)))
+            if ph not in seen:
+                seen.add(ph)
+                lists.append(list(ph))
+        legs = {"A": lambda: [fn(x) for x in lists], "B": lambda: fn.batch(lists)}
+        if a.only is not None:
+            ts = _timed(legs[a.only], a.calls, a.warmup)
+            out[n] = {a.only: dict(median_ms_per_list=round(1e3 * float(np.median(ts)) / n, 4), calls=a.calls)}
+            continue
+        same = legs["A"]() == legs["B"]()
+        row = dict(phones=[len(x) for x in lists], same_result=bool(same))
+        for name, leg in (("A1", "A"), ("B", "B"), ("A2", "A")):
+            ts = _timed(legs[leg], a.calls, a.warmup)
+            row[name] = dict(median_ms_per_list=round(1e3 * float(np.median(ts)) / n, 4),
+                             min_ms_per_list=round(1e3 * float(np.min(ts)) / n, 4),
+                             max_ms_per_list=round(1e3 * float(np.max(ts)) / n, 4))
+        a1, a2, b = (row[k]["median_ms_per_list"] for k in ("A1", "A2", "B"))
+        row["A_spread_ms"] = round(abs(a1 - a2), 4)
+        row["B_over_A"] = round(b / (0.5 * (a1 + a2)), 4)
+        row["faster_beyond_spread"] = bool(min(a1, a2) - b > abs(a1 - a2))
+        row["calls"] = a.calls
+        out[n] = row
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--phones", type=int, nargs="+", default=[60, 300])
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batch", type=int, nargs="+", default=None, help="batched path: numbers of lists per call")
+    ap.add_argument("--only", choices=["A", "B"], default=None, help="with --batch: run one leg only (for kernel traces)")
     a = ap.parse_args()
     from a3t_amd.duration import FS2DurationConfig, FS2DurationModel
     from oracle import a3t_oracle as O
@@ -43,6 +98,9 @@ def main():
     fn = m.duration_fn(24000, 300)
     rs = np.random.RandomState(0)
     out = {}
+    if a.batch is not None:
+        print(json.dumps({"duration_batch_latency": batch_latency(fn, phones, a, rs)}))
+        return
     for n in a.phones:
         phns = [phones[i] for i in rs.randint(0, len(phones), n)]
         for _ in range(a.warmup):
