@@ -107,6 +107,8 @@ _SIGS = {
                                       _P],
     "a3t_splice_spans": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_pwg_block_ragged": [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
+    "a3t_pwg_block_f16": [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
+    "a3t_cast_f16_sat": [_P, _P, c_int64, _P],
     "a3t_duration_head": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P],
     "a3t_l2_normalize": [_P, _P, c_int, c_int, c_float, _P],
     "a3t_dropout": [_P, c_int, _P, c_int, c_int64, c_float, ctypes.c_uint32, c_float, _P],

@@ -632,6 +632,40 @@ def pwg_block_ragged(x, cu, wt0, b0, wt1, b1, g, skips, tiles, B, Tw, dil):
             "pwg_block_ragged")
 
 
+def cast_f16_sat(src, dst):
+    """dst (fp16) = src (fp32) rounded to nearest even and saturated to +-65504 (a3t_cast_f16_sat)."""
+    if src.dtype != torch.float32 or dst.dtype != torch.float16 or src.numel() != dst.numel() \
+            or not (src.is_contiguous() and dst.is_contiguous()):
+        raise ValueError("cast_f16_sat: src must be contiguous fp32, dst contiguous fp16 of the same size")
+    L.check(L.load().a3t_cast_f16_sat(_ptr(src), _ptr(dst), src.numel(), _stream()), "cast_f16_sat")
+
+
+def pwg_block_f16(x_in, x_out, cu16, w0h, b0, w1h, b1, skips, tiles, B, Tw, dil):
+    """Fused residual block in one launch on the 16-bit MFMA (a3t_pwg_block_f16): x_in -> x_out (two different buffers), skips in
+    place.  cu16 / w0h / w1h fp16 (cast_f16_sat, vocoder.pack_pwg_block_f16); tiles: None = all rows Tw samples long, else the
+    list of pwg_block_ragged."""
+    for name, t, C, dt in (("x_in", x_in, 64, torch.float32), ("x_out", x_out, 64, torch.float32), ("cu16", cu16, 80, torch.float16),
+                           ("skips", skips, 64, torch.float32)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != B * Tw * C:
+            raise ValueError(f"pwg_block_f16: {name} must be a contiguous {dt} [{B * Tw}][{C}] tensor")
+    for name, t, shape, dt in (("w0h", w0h, (272, 128), torch.float16), ("w1h", w1h, (64, 128), torch.float16),
+                               ("b0", b0, (128,), torch.float32), ("b1", b1, (128,), torch.float32)):
+        if t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError(f"pwg_block_f16: {name} must be a contiguous {dt} tensor of shape {shape}")
+    nt = 0
+    if tiles is not None:
+        if tiles.dim() != 2 or tiles.shape[1] != 4:
+            raise ValueError(f"pwg_block_f16: tiles must be (ntiles, 4), got {tuple(tiles.shape)}")
+        if tiles.shape[0] > B * ((Tw + 255) // 256):
+            raise ValueError(f"pwg_block_f16: {tiles.shape[0]} tiles do not fit {B} rows of {Tw} samples")
+        nt = tiles.shape[0]
+        _i32(tiles, "tiles")
+        if nt == 0:      # (an empty tensor has no address: NULL would mean "dense")
+            return
+    L.check(L.load().a3t_pwg_block_f16(_ptr(x_in), _ptr(x_out), _ptr(cu16), _ptr(w0h), _ptr(b0), _ptr(w1h), _ptr(b1),
+                                       _ptr(skips), _ptr(tiles), nt, B, Tw, dil, _stream()), "pwg_block_f16")
+
+
 def splice_spans(after, speech, speech_mask, spans, out, lens):
     """out[b][t] = after[b][t] inside spans[b], speech[b][t] for the other valid frames, 0 behind the row's length (the sum of
     its speech_mask, written to lens).  after / speech [B][Tin][C] fp32, speech_mask [B][Tin] bool / uint8, out [B][Tout][C]."""

@@ -50,11 +50,59 @@ def pwg_tile_list(lengths: Sequence[int], hop: int, tile: int = 256) -> np.ndarr
     return np.stack([b, t0, W[b], np.zeros_like(b)], axis=1).astype(np.int32).reshape(-1, 4)
 
 
+F16_MAX = 65504.0
+
+
+def pwg_gate_perm(gate_channels: int = 128) -> np.ndarray:
+    """Column order of the fused blocks' first product: column n' holds gate channel c = 32*(n'//64) + n'%32, its tanh half for
+    (n'//32)%2 == 0, else its sigmoid half (channel c + gate_channels/2 of the convolution): a wave's two 32-column MFMA blocks
+    then hold both pre-activations of the same 32 channels."""
+    n = np.arange(gate_channels)
+    return (n // 64) * 32 + n % 32 + (gate_channels // 2) * ((n // 32) % 2)
+
+
+def pack_pwg_block_f16(conv_w, conv_b, aux_w, out_w):
+    """Operands of a3t_pwg_block_f16 from one residual block's parameters (CPU or device tensors; pure).
+
+    conv_w (128, 64, 3) dilated conv, conv_b (128,), aux_w (128, 80[, 1]) conv1x1_aux, out_w (128, 64[, 1]) conv1x1_out ->
+    w0h fp16 [272][128]: row k = tap*64 + in_channel for the taps at t-dil, t, t+dil, then 192 + aux channel (tap-major K
+    order); column n' = pwg_gate_perm;  b0 fp32 [128] permuted the same way;  w1h fp16 [64][128] = conv1x1_out.weight^T.
+    The cast is round-to-nearest-even and saturates to +-65504."""
+    conv_w = torch.as_tensor(conv_w, dtype=torch.float32)
+    G, R, taps = conv_w.shape
+    aux_w = torch.as_tensor(aux_w, dtype=torch.float32).reshape(G, -1)
+    out_w = torch.as_tensor(out_w, dtype=torch.float32).reshape(-1, G // 2)
+    if (G, R, taps, aux_w.shape[1], out_w.shape[0]) != (128, 64, 3, 80, 128):
+        raise ValueError("pack_pwg_block_f16: the kernel is built for the v1 channel plan (64 / 128 / 64 / 80, kernel size 3)")
+    perm = torch.as_tensor(pwg_gate_perm(G), device=conv_w.device)
+    wk = conv_w.permute(0, 2, 1).reshape(G, taps * R)                       # [out][tap*64 + in]
+    w0 = torch.cat([wk, aux_w.to(conv_w.device)], dim=1)[perm]               # [n'][272]
+
+    def h(t):
+        return t.clamp(-F16_MAX, F16_MAX).to(torch.float16).contiguous()
+
+    b0 = torch.as_tensor(conv_b, dtype=torch.float32).to(conv_w.device)[perm].contiguous()
+    return h(w0.t()), b0, h(out_w.to(conv_w.device).t())
+
+
 class ParallelWaveGANGeneratorHIP:
+    """compute="f32" (default): exact fp32 products.  compute="f16": the residual blocks run on the 16-bit MFMA, one launch per
+    block (pwg_fused_f16.hip): the conv input, the upsampled mel, the gate output and the block weights are rounded to fp16
+    (nearest even, saturated), everything else stays fp32.  It needs the fused v1 channel plan."""
+
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", layers=30, stacks=3, residual_channels=64,
                  gate_channels=128, skip_channels=64, aux_channels=80, aux_context_window=2,
                  upsample_scales: Sequence[int] = (4, 5, 3, 5), stats: Optional[Dict[str, np.ndarray]] = None,
-                 fused: Optional[bool] = None):
+                 fused: Optional[bool] = None, compute: str = "f32"):
+        if compute not in ("f32", "f16"):
+            raise ValueError(f"compute must be 'f32' or 'f16', got {compute!r}")
+        if compute == "f16":
+            if (residual_channels, gate_channels, skip_channels, aux_channels) != (64, 128, 64, 80):
+                raise ValueError("compute='f16' needs the v1 channel plan: 64 residual / 128 gate / 64 skip / 80 aux channels")
+            if fused is not None and not fused:
+                raise ValueError("compute='f16' is a mode of the fused residual blocks: fused=False cannot be combined with it")
+            fused = True
+        self.compute = compute
         self.dev = torch.device(device)
         self.layers, self.stacks = layers, stacks
         self.R, self.G, self.S, self.A = residual_channels, gate_channels, skip_channels, aux_channels
@@ -97,6 +145,8 @@ class ParallelWaveGANGeneratorHIP:
                 blk["wt0"] = w0.t().contiguous()                                # [272][128] k-major
                 blk["b0"] = blk["b"][perm].contiguous()
                 blk["wt1"] = blk["out"].t().contiguous()                        # [64][128]
+            if compute == "f16":
+                blk["w0h"], blk["b0h"], blk["w1h"] = pack_pwg_block_f16(t(p + "conv.weight"), blk["b"], blk["aux"], blk["out"])
             self.blocks.append(blk)
         self.w_l1 = t("last_conv_layers.1.weight").reshape(self.S, self.S).contiguous()
         self.b_l1 = t("last_conv_layers.1.bias")
@@ -146,6 +196,21 @@ class ParallelWaveGANGeneratorHIP:
         x = torch.empty(B * Tw, self.R, device=dev)
         ops.linear_fwd(z, self.w_first, x, bias=self.b_first, compute=F32)
         skips = torch.zeros(B * Tw, self.S, device=dev)
+        if self.compute == "f16":
+            self._blocks_f16(x, cu, skips, None, B, Tw)
+        else:
+            self._blocks_f32(x, cu, skips, B, Tw)
+        ops.bias_act(skips, None, ACT_RELU, math.sqrt(1.0 / self.layers))
+        h = torch.empty(B * Tw, self.S, device=dev)
+        ops.linear_fwd(skips, self.w_l1, h, bias=self.b_l1, act=ACT_RELU, compute=F32)
+        wav = torch.empty(B * Tw, 1, device=dev)
+        ops.linear_fwd(h, self.w_l3, wav, bias=self.b_l3, compute=F32)
+        wav = wav.view(B, Tw, 1)
+        return wav[0] if single else wav
+
+    def _blocks_f32(self, x, cu, skips, B, Tw):
+        """The residual stack in fp32, rows of equal length: x and skips updated in place."""
+        dev = self.dev
         y = torch.empty(B * Tw, self.G, device=dev)
         ca = torch.empty(B * Tw, self.G, device=dev)
         g = torch.empty(B * Tw, self.G // 2, device=dev)
@@ -161,13 +226,17 @@ class ParallelWaveGANGeneratorHIP:
             ops.pwg_gate(y, ca, g)
             ops.linear_fwd(g, blk["out"], o, bias=blk["bout"], compute=F32)
             ops.pwg_res_skip(o, x, skips)
-        ops.bias_act(skips, None, ACT_RELU, math.sqrt(1.0 / self.layers))
-        h = torch.empty(B * Tw, self.S, device=dev)
-        ops.linear_fwd(skips, self.w_l1, h, bias=self.b_l1, act=ACT_RELU, compute=F32)
-        wav = torch.empty(B * Tw, 1, device=dev)
-        ops.linear_fwd(h, self.w_l3, wav, bias=self.b_l3, compute=F32)
-        wav = wav.view(B, Tw, 1)
-        return wav[0] if single else wav
+
+    def _blocks_f16(self, x, cu, skips, tiles, B, Tw):
+        """The residual stack on the 16-bit MFMA: cu is cast once, x ping-pongs between two buffers (a block must not
+        overwrite the x[t +- dil] that other tiles still read); skips is updated in place, x is left undefined."""
+        cu16 = torch.empty(B * Tw, self.A, dtype=torch.float16, device=self.dev)
+        ops.cast_f16_sat(cu, cu16)
+        x2 = torch.empty_like(x)
+        lps = self.layers // self.stacks
+        for l, blk in enumerate(self.blocks):
+            ops.pwg_block_f16(x, x2, cu16, blk["w0h"], blk["b0h"], blk["w1h"], blk["bout"], skips, tiles, B, Tw, 2 ** (l % lps))
+            x, x2 = x2, x
 
     @property
     def margin_frames(self) -> int:
@@ -212,7 +281,9 @@ class ParallelWaveGANGeneratorHIP:
         skips = torch.zeros(B * Tw, self.S, device=dev)
         g = torch.empty(B * Tw, self.G // 2, device=dev)
         lps = self.layers // self.stacks
-        if self.fused:
+        if self.compute == "f16":
+            self._blocks_f16(x, cu, skips, tiles, B, Tw)
+        elif self.fused:
             for l, blk in enumerate(self.blocks):
                 if tiles.shape[0]:
                     ops.pwg_block_ragged(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], g, skips, tiles, B, Tw,

@@ -440,6 +440,17 @@ int a3t_pwg_block(float* x, const float* cu, const float* wt0, const float* b0, 
  * ts is zero unless 0 <= ts < W_b; rows behind W_b are neither read nor written; tiles that are not listed cost nothing. */
 int a3t_pwg_block_ragged(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1,
                          float* g, float* skips, const int32_t* tiles, int ntiles, int B, int Tw, int dil, void* stream);
+/* The same block in ONE launch on the 16-bit MFMA (fp16 operands, fp32 accumulation): the conv input x, cu, the gate output
+ * and the weights are rounded to nearest even to fp16 and saturated to +-65504; biases, tanh / sigmoid, the residual stream and
+ * skips stay fp32.  x_in -> x_out, two buffers that must not overlap (a tile reads x[t +- dil] of tiles that may be finished
+ * already; the caller swaps them per layer); skips in place.  cu16 [B*Tw][80] fp16 (a3t_cast_f16_sat of cu); w0h [272][128] and
+ * w1h [64][128] fp16 with the rows and columns of wt0 / wt1 above; b0 / b1 fp32 as above.  tiles == NULL (and ntiles == 0):
+ * every row is Tw samples long; else the tile list of a3t_pwg_block_ragged, with its rules.  x_in, x_out, cu16, skips and tiles
+ * 16-byte aligned.  A sample's result does not depend on its tile or on the other rows of the batch. */
+int a3t_pwg_block_f16(const float* x_in, float* x_out, const void* cu16, const void* w0h, const float* b0, const void* w1h,
+                      const float* b1, float* skips, const int32_t* tiles, int ntiles, int B, int Tw, int dil, void* stream);
+/* dst[i] = fp16(src[i]), round to nearest even, saturated to +-65504; both 16-byte aligned. */
+int a3t_cast_f16_sat(const float* src, void* dst, int64_t n, void* stream);
 
 /* On-device half of MLMCollateFn (espnet2/train/collate_fn.py:330-385): masked_position, speech / text segment ids and the
  * two padding masks painted from integer span lists.  fs / fe [B][P] int32: frame span of phone j (floor(fs * t / hop) taken

@@ -15,7 +15,14 @@ model would cost.
   kernel  the 30 residual blocks alone, B x T frames: a3t_pwg_block, a3t_pwg_block_ragged with all lengths equal (the tile
           list's cost), and ragged lengths (expected near valid / padded samples of the padded run)
 
+  --vocoder-compute f32 f16: the request legs are run once per vocoder compute mode (keys `<model>.<compute>.n<N>` for f32,
+          `<model>.<compute>.voc_f16.n<N>` for f16), and --kernel adds `pwg_blocks_f16`: the 30 blocks through a3t_pwg_block_f16
+          (one launch per block, x ping-ponging between two buffers) next to the fp32 pair of launches, order f32, f16, f32,
+          median of --calls, on the padded 8 x 1000 frames and on the ragged lengths, with the bytes per second the f16 blocks
+          reach against their HBM model (x read and written, cu16 read, skips read and written: 1184 B per sample and block).
+
     python tools/sedit_batch_latency.py [--models c2] [--compute bf16 f32] [--n 1 4 8] [--calls 50] [--warmup 5] [--kernel]
+                                        [--vocoder-compute f32 f16]
 """
 import argparse
 import json
@@ -57,11 +64,12 @@ def vocoder_state():
     return state
 
 
-def editor(which, compute):
+def editor(which, compute, vocoder_compute="f32"):
     from a3t_amd.vocoder import ParallelWaveGANGeneratorHIP
     from dyneval_latency import editor as base
     ed, oc = base(which, compute)
-    ed.vocoder = ParallelWaveGANGeneratorHIP(vocoder_state(), device="cuda")
+    kw = {} if vocoder_compute == "f32" else dict(compute=vocoder_compute)
+    ed.vocoder = ParallelWaveGANGeneratorHIP(vocoder_state(), device="cuda", **kw)
     return ed, oc
 
 
@@ -177,23 +185,87 @@ def kernel_bench(frames, lengths_sets, reps=5):
     return out
 
 
+F16_BLOCK_BYTES = 64 * 4 + 64 * 4 + 80 * 2 + 2 * 64 * 4      # per sample and block: x in, x out, cu16, skips read + write
+
+
+def kernel_bench_f16(frames, lengths_sets, calls=50, warmup=3):
+    """The 30 residual blocks in fp32 (two launches per block) and on the 16-bit MFMA (one launch per block), B x frames x hop
+    samples: `8x1000`-like sets (all lengths equal) run the padded entry points, the others the tile list; order f32, f16, f32,
+    median / min / max of `calls` runs each, ms."""
+    from a3t_amd import ops
+    from a3t_amd.vocoder import ParallelWaveGANGeneratorHIP, pwg_tile_list
+    gen = ParallelWaveGANGeneratorHIP(vocoder_state(), device="cuda", compute="f16")
+    hop, out = gen.upsample_factor, {}
+    for name, lengths in lengths_sets.items():
+        B, Tw = len(lengths), frames * hop
+        x0 = 0.1 * torch.randn(B * Tw, 64, device="cuda")
+        cu = 1.5 * torch.randn(B * Tw, 80, device="cuda") - 4.0
+        cu16 = torch.empty(B * Tw, 80, dtype=torch.float16, device="cuda")
+        ops.cast_f16_sat(cu, cu16)
+        g = torch.empty(B * Tw, 64, device="cuda")
+        equal = all(n == frames for n in lengths)
+        tiles = None if equal else torch.from_numpy(pwg_tile_list(lengths, hop)).to("cuda")
+        fin = []
+
+        def run(f16):
+            x, sk = x0.clone(), torch.zeros(B * Tw, 64, device="cuda")
+            x2 = torch.empty_like(x)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for l, blk in enumerate(gen.blocks):
+                dil = 2 ** (l % 10)
+                if f16:
+                    ops.pwg_block_f16(x, x2, cu16, blk["w0h"], blk["b0h"], blk["w1h"], blk["bout"], sk, tiles, B, Tw, dil)
+                    x, x2 = x2, x
+                elif tiles is None:
+                    ops.pwg_block(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], g, sk, B, Tw, dil)
+                else:
+                    ops.pwg_block_ragged(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], g, sk, tiles, B, Tw, dil)
+            b.record()
+            torch.cuda.synchronize()
+            fin.append(bool(torch.isfinite(sk).all()))
+            return a.elapsed_time(b)
+
+        def series(f16):
+            for _ in range(warmup):
+                run(f16)
+            ts = [run(f16) for _ in range(calls)]
+            return dict(median_ms=round(float(np.median(ts)), 3), min_max_ms=[round(min(ts), 3), round(max(ts), 3)])
+
+        r = dict(lengths=list(lengths), f32_first=series(False), f16=series(True), f32_again=series(False))
+        f32 = 0.5 * (r["f32_first"]["median_ms"] + r["f32_again"]["median_ms"])
+        valid = sum(lengths) * hop
+        r["f16_over_f32"] = round(r["f16"]["median_ms"] / f32, 4)
+        r["f16_bytes_per_s_model"] = round(valid * len(gen.blocks) * F16_BLOCK_BYTES / (1e-3 * r["f16"]["median_ms"]), 0)
+        r["valid_samples"], r["finite"] = valid, all(fin)
+        out[name] = r
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--models", nargs="+", default=["c2"])
+    ap.add_argument("--models", nargs="*", default=["c2"])      # (none given: the --kernel leg alone)
     ap.add_argument("--compute", nargs="+", default=["bf16", "f32"])
     ap.add_argument("--n", type=int, nargs="+", default=[1, 4, 8])
     ap.add_argument("--frames-range", type=int, nargs=2, default=[300, 1000])
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--kernel", action="store_true")
+    ap.add_argument("--vocoder-compute", nargs="+", default=["f32"], choices=["f32", "f16"])
     a = ap.parse_args()
     prop = torch.cuda.get_device_properties(0)
     out = {"device": f"{prop.name} ({getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs)"}
     if a.kernel:
-        out["pwg_blocks"] = kernel_bench(1000, {"8x1000": [1000] * 8, "ragged": [1000, 700, 500, 300] * 2})
+        sets = {"8x1000": [1000] * 8, "ragged": [1000, 700, 500, 300] * 2}
+        if "f32" in a.vocoder_compute:
+            out["pwg_blocks"] = kernel_bench(1000, sets)
+        if "f16" in a.vocoder_compute:
+            out["pwg_blocks_f16"] = kernel_bench_f16(1000, sets, a.calls)
+            print(json.dumps({"pwg_blocks_f16": out["pwg_blocks_f16"]}), flush=True)
     for which in a.models:
-        for compute in a.compute:
-            ed, oc = editor(which, compute)
+        for compute, vc in [(c, v) for c in a.compute for v in a.vocoder_compute]:
+            ed, oc = editor(which, compute, vc)
+            tag = f"{which}.{compute}" + ("" if vc == "f32" else f".voc_{vc}")
             for n in a.n:
                 rs = np.random.RandomState(n)
                 lo, hi = a.frames_range
@@ -216,8 +288,8 @@ def main():
                 r["span_frames"] = [int(g["new_span_boundary"][1] - g["new_span_boundary"][0]) for g in got]
                 r["legs_full_ms"] = legs(ed, reqs, False, max(5, a.calls // 5), 2)
                 r["legs_span_only_ms"] = legs(ed, reqs, True, max(5, a.calls // 5), 2)
-                out[f"{which}.{compute}.n{n}"] = r
-                print(json.dumps({f"{which}.{compute}.n{n}": r}), flush=True)
+                out[f"{tag}.n{n}"] = r
+                print(json.dumps({f"{tag}.n{n}": r}), flush=True)
     print(json.dumps({"sedit_batch_latency": out}))
 
 
