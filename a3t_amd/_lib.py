@@ -111,6 +111,9 @@ _SIGS = {
     "a3t_cast_f16_sat": [_P, _P, c_int64, _P],
     "a3t_duration_head": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P],
     "a3t_l2_normalize": [_P, _P, c_int, c_int, c_float, _P],
+    "a3t_gst_conv_bn_relu": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P],
+    "a3t_gst_gru_stl": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
+    "a3t_gst_add_style": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_dropout": [_P, c_int, _P, c_int, c_int64, c_float, ctypes.c_uint32, c_float, _P],
     "a3t_collate_paint": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "a3t_segment_colsum": [_P, _P, c_int, c_int, c_int, _P],

@@ -11,6 +11,14 @@ fp32 compute, eval mode.  A single phone sequence runs as its own B = 1 forward 
 legacy rel-pos attention reads pe[:T] and the conv module does not mask padded frames, so plain padding would change the
 result.  Several sequences run as ONE padded forward with per-row lengths (forward_ids_batch): the engine's ragged block
 forward gives every row what it would get alone -- rel_shift at the row's own length, zeros behind it for every k-tap conv.
+
+A gst+xvector checkpoint (use_gst: true; the reference's VCTK and LibriTTS duration models) is loaded with gst=True: its
+durations depend on the prompt.  duration_predict (:413-418) takes the log-mel of the original waveform with the TTS model's own
+extractor, runs the StyleEncoder over it (espnet2/tts/gst/style_encoder.py: stride-2 Conv2d + BatchNorm2d + ReLU layers, a
+GRU, multi-head attention over learned style tokens) and adds the style embedding to every encoder output row in front of the
+x-vector integration.  Here that is style_embedding(_batch) (csrc/gst.hip: one launch per conv layer, one GEMM for the GRU's
+input projections, one launch for the recurrence and the token attention, whatever the number of prompts) and the style=
+argument of the forwards.
 """
 import math
 import os
@@ -34,7 +42,13 @@ _FS2_DEFAULTS = dict(adim=384, aheads=4, elayers=6, eunits=1536, positionwise_la
                      use_macaron_style_in_conformer=True, use_cnn_in_conformer=True, zero_triu=False,
                      conformer_enc_kernel_size=7, duration_predictor_layers=2, duration_predictor_chans=384,
                      duration_predictor_kernel_size=3, spk_embed_dim=None, spk_embed_integration_type="add",
-                     use_gst=False)
+                     use_gst=False, gst_tokens=10, gst_heads=4, gst_conv_layers=6,
+                     gst_conv_chans_list=(32, 32, 64, 64, 128, 128), gst_conv_kernel_size=3, gst_conv_stride=2, gst_gru_layers=1,
+                     gst_gru_units=128)
+# LogMelFbank.__init__ defaults (espnet2/tts/feats_extract/log_mel_fbank.py)
+_FBANK_DEFAULTS = dict(fs=16000, n_fft=1024, win_length=None, hop_length=256, window="hann", center=True, normalized=False,
+                       onesided=True, n_mels=80, fmin=80, fmax=7600, htk=False, log_base=10.0)
+GST_MAX_UNITS, GST_MAX_DIM, GST_MAX_SCORES = 128, 1024, 512      # csrc/gst.hip: GST_MAXH, GST_MAXD, GST_MAXS
 
 @dataclass
 class FS2DurationConfig(A3TConfig):
@@ -49,10 +63,29 @@ class FS2DurationConfig(A3TConfig):
     dp_offset: float = 1.0
     spk_integration: str = "add"
     token_list: List[str] = field(default_factory=list)
+    # the GST style encoder (use_gst; token dim = adim, input = n_mels) and the TTS model's own log-mel extractor
+    use_gst: bool = False
+    gst_tokens: int = 10
+    gst_heads: int = 4
+    gst_conv_chans: List[int] = field(default_factory=lambda: [32, 32, 64, 64, 128, 128])
+    gst_conv_kernel: int = 3
+    gst_conv_stride: int = 2
+    gst_gru_units: int = 128
+    gst_feats_conf: Dict[str, Any] = field(default_factory=dict)
+
+    def gst_plan(self):
+        """Per conv layer of the reference encoder (Cin, Cout, Fin, Fout); the GRU input is Fout * Cout of the last."""
+        k, s, F, cin, plan = self.gst_conv_kernel, self.gst_conv_stride, self.n_mels, 1, []
+        for cout in self.gst_conv_chans:
+            Fo = gst_out_len(F, k, s)
+            plan.append((cin, cout, F, Fo))
+            F, cin = Fo, cout
+        return plan
 
     @staticmethod
-    def from_espnet(conf: Dict[str, Any]) -> "FS2DurationConfig":
-        """Translate an ESPnet TTS config.yaml (tts: fastspeech2, tts_conf, token_list)."""
+    def from_espnet(conf: Dict[str, Any], gst: bool = False) -> "FS2DurationConfig":
+        """Translate an ESPnet TTS config.yaml (tts: fastspeech2, tts_conf, token_list).  A use_gst: true config needs
+        gst=True: the durations of such a model depend on a prompt waveform that every call then has to bring."""
         if conf.get("tts", "fastspeech2") != "fastspeech2":
             raise NotImplementedError(f"tts: {conf.get('tts')!r}: only fastspeech2 is implemented")
         tl = list(conf.get("token_list") or [])
@@ -60,8 +93,11 @@ class FS2DurationConfig(A3TConfig):
             raise ValueError("config has no token_list")
         t = dict(_FS2_DEFAULTS)
         t.update(conf.get("tts_conf") or {})
-        if t["use_gst"]:
-            raise NotImplementedError("use_gst: true (the GST style encoder) is not implemented")
+        if t["use_gst"] and not gst:
+            raise NotImplementedError("use_gst: true (the GST style encoder) makes the durations depend on a prompt: "
+                                      "load the checkpoint with gst=True and give the prompt with every call")
+        if gst and not t["use_gst"]:
+            raise ValueError("gst=True, but the config has use_gst: false")
         if t["encoder_type"] != "conformer":
             raise NotImplementedError(f"encoder_type: {t['encoder_type']!r}: only the conformer encoder is implemented")
         if t["conformer_rel_pos_type"] != "legacy":
@@ -85,12 +121,56 @@ class FS2DurationConfig(A3TConfig):
                                       "only add and concat are implemented")
         if t["positionwise_conv_kernel_size"] % 2 == 0 or t["duration_predictor_kernel_size"] % 2 == 0:
             raise NotImplementedError("even kernel sizes are not implemented")
-        return FS2DurationConfig(vocab=len(tl), adim=t["adim"], heads=t["aheads"], ff=t["eunits"],
+        g = _gst_fields(conf, t) if t["use_gst"] else {}
+        return FS2DurationConfig(**g, vocab=len(tl), adim=t["adim"], heads=t["aheads"], ff=t["eunits"],
                                  ff_kernel=t["positionwise_conv_kernel_size"], enc_blocks=t["elayers"],
                                  enc_kernel=t["conformer_enc_kernel_size"], dp_layers=t["duration_predictor_layers"],
                                  dp_chans=t["duration_predictor_chans"], dp_kernel=t["duration_predictor_kernel_size"],
                                  spk_embed_dim=spk, spk_integration=t["spk_embed_integration_type"], token_list=tl,
                                  dropout_rate=0.0, positional_dropout_rate=0.0, attention_dropout_rate=0.0)
+
+
+def gst_out_len(n: int, k: int, s: int) -> int:
+    """Output length of one conv layer of the reference encoder along either axis: padding (k - 1) // 2, stride s."""
+    return (n + 2 * ((k - 1) // 2) - k) // s + 1
+
+
+def _gst_fields(conf, t) -> Dict[str, Any]:
+    """The GST fields of FS2DurationConfig from tts_conf (defaults merged in `t`) and feats_extract(_conf)."""
+    if int(t["gst_gru_layers"]) != 1:
+        raise NotImplementedError(f"gst_gru_layers: {t['gst_gru_layers']!r}: only one GRU layer is implemented")
+    k, s = int(t["gst_conv_kernel_size"]), int(t["gst_conv_stride"])
+    if k < 1 or k % 2 == 0:
+        raise NotImplementedError(f"gst_conv_kernel_size: {k!r}: only odd kernel sizes are implemented")
+    if s < 1:
+        raise NotImplementedError(f"gst_conv_stride: {s!r} is not implemented")
+    chans = [int(x) for x in t["gst_conv_chans_list"]]
+    if int(t["gst_conv_layers"]) != len(chans) or not chans or min(chans) < 1:
+        raise ValueError(f"gst_conv_layers: {t['gst_conv_layers']!r} does not fit gst_conv_chans_list {chans}")
+    units, heads, tokens = int(t["gst_gru_units"]), int(t["gst_heads"]), int(t["gst_tokens"])
+    if not 1 <= units <= GST_MAX_UNITS:
+        raise NotImplementedError(f"gst_gru_units: {units!r}: 1..{GST_MAX_UNITS} are implemented")
+    if heads < 1 or t["adim"] % heads != 0:
+        raise ValueError(f"gst_heads: {heads!r} does not divide adim {t['adim']}")
+    if tokens < 1 or heads * tokens > GST_MAX_SCORES:
+        raise NotImplementedError(f"gst_tokens: {tokens!r}: gst_heads * gst_tokens up to {GST_MAX_SCORES} is implemented")
+    if t["adim"] > GST_MAX_DIM:
+        raise NotImplementedError(f"adim: {t['adim']!r}: a style token dimension up to {GST_MAX_DIM} is implemented")
+    fe = conf.get("feats_extract", "fbank")
+    if fe != "fbank":
+        raise NotImplementedError(f"feats_extract: {fe!r}: only fbank is implemented")
+    fc = dict(_FBANK_DEFAULTS)
+    given = dict(conf.get("feats_extract_conf") or {})
+    unknown = sorted(set(given) - set(fc))
+    if unknown:
+        raise NotImplementedError(f"feats_extract_conf: unknown keys {unknown}")
+    fc.update(given)
+    if fc["log_base"] is None or float(fc["log_base"]) != 10.0:
+        raise NotImplementedError(f"log_base: {fc['log_base']!r}: only 10 is implemented")
+    fc.pop("log_base")
+    fc["fs"] = int(fc["fs"])        # (a config may spell it "24000"; "24k" style strings are not translated)
+    return dict(use_gst=True, gst_tokens=tokens, gst_heads=heads, gst_conv_chans=chans, gst_conv_kernel=k, gst_conv_stride=s,
+                gst_gru_units=units, gst_feats_conf=fc, n_mels=int(fc["n_mels"]))
 
 
 def param_layout(c: FS2DurationConfig):
@@ -113,6 +193,21 @@ def param_layout(c: FS2DurationConfig):
         lay[f"dp.{l}.ln.b"] = (c.dp_chans,)
     lay["dp.lin.w"] = (c.dp_chans,)
     lay["dp.lin.b"] = (1,)
+    if c.use_gst:
+        k, H, dk = c.gst_conv_kernel, c.gst_gru_units, d // c.gst_heads
+        plan = c.gst_plan()
+        for i, (cin, cout, _, _) in enumerate(plan):
+            lay[f"gst.conv.{i}.w"] = (k, k, cin, cout)          # [time tap][frequency tap][Cin][Cout]: channels-last
+            lay[f"gst.conv.{i}.bn.g"] = (cout,)
+            lay[f"gst.conv.{i}.bn.b"] = (cout,)
+        lay["gst.gru.wih"] = (3 * H, plan[-1][3] * plan[-1][1])     # columns f * C + c: the conv output is channels-last
+        lay["gst.gru.whh"] = (3 * H, H)
+        lay["gst.gru.bih"] = (3 * H,)
+        lay["gst.gru.bhh"] = (3 * H,)
+        lay["gst.stl.embs"] = (c.gst_tokens, dk)
+        for n, kin in (("q", H), ("k", dk), ("v", dk), ("out", d)):
+            lay[f"gst.stl.{n}.w"] = (d, kin)
+            lay[f"gst.stl.{n}.b"] = (d,)
     return lay
 
 
@@ -121,11 +216,16 @@ def buffer_layout(c: FS2DurationConfig):
     for i in range(c.enc_blocks):
         lay[f"enc.{i}.cnv.bn.rm"] = (c.adim,)
         lay[f"enc.{i}.cnv.bn.rv"] = (c.adim,)
+    if c.use_gst:
+        for i, cout in enumerate(c.gst_conv_chans):
+            lay[f"gst.conv.{i}.bn.rm"] = (cout,)
+            lay[f"gst.conv.{i}.bn.rv"] = (cout,)
     return lay
 
 
 def key_map(c: FS2DurationConfig):
-    """(ESPnet TTS checkpoint key, store name, (column slice) | None, kind): ParamStore's kinds, plus "cols"."""
+    """(ESPnet TTS checkpoint key, store name, (column slice) | None, kind): ParamStore's kinds, plus "cols", "conv2d"
+    (Conv2d weight [Cout][Cin][kt][kf] -> [kt][kf][Cin][Cout]) and "gru_ih" (weight_ih columns c * F + f -> f * C + c, (C, F))."""
     d = c.adim
     m = [("tts.encoder.embed.0.weight", "temb", None, "reshape")]
     for i in range(c.enc_blocks):
@@ -145,6 +245,21 @@ def key_map(c: FS2DurationConfig):
               (p + "2.weight", f"dp.{l}.ln.g", None, "reshape"), (p + "2.bias", f"dp.{l}.ln.b", None, "reshape")]
     m += [("tts.duration_predictor.linear.weight", "dp.lin.w", None, "reshape"),
           ("tts.duration_predictor.linear.bias", "dp.lin.b", None, "reshape")]
+    if c.use_gst:
+        plan = c.gst_plan()
+        for i in range(len(plan)):
+            cv, bn = f"tts.gst.ref_enc.convs.{3 * i}.", f"tts.gst.ref_enc.convs.{3 * i + 1}."
+            m += [(cv + "weight", f"gst.conv.{i}.w", None, "conv2d"),
+                  (bn + "weight", f"gst.conv.{i}.bn.g", None, "reshape"), (bn + "bias", f"gst.conv.{i}.bn.b", None, "reshape"),
+                  (bn + "running_mean", f"gst.conv.{i}.bn.rm", None, "buffer"),
+                  (bn + "running_var", f"gst.conv.{i}.bn.rv", None, "buffer")]
+        g = "tts.gst.ref_enc.gru."
+        m += [(g + "weight_ih_l0", "gst.gru.wih", (plan[-1][1], plan[-1][3]), "gru_ih"),
+              (g + "weight_hh_l0", "gst.gru.whh", None, "reshape"), (g + "bias_ih_l0", "gst.gru.bih", None, "reshape"),
+              (g + "bias_hh_l0", "gst.gru.bhh", None, "reshape"), ("tts.gst.stl.gst_embs", "gst.stl.embs", None, "reshape")]
+        for n in ("q", "k", "v", "out"):
+            m += [(f"tts.gst.stl.mha.linear_{n}.weight", f"gst.stl.{n}.w", None, "reshape"),
+                  (f"tts.gst.stl.mha.linear_{n}.bias", f"gst.stl.{n}.b", None, "reshape")]
     return m
 
 
@@ -160,7 +275,8 @@ def load_into(store: ParamStore, c: FS2DurationConfig, sd) -> None:
         raise KeyError(f"FastSpeech2 checkpoint: missing keys {missing}")
     used = {k for k, _, _, _ in km}
     unexpected = sorted(k for k in keys - used
-                        if k.startswith(("tts.encoder.", "tts.duration_predictor.", "tts.projection.", "tts.gst.")))
+                        if k.startswith(("tts.encoder.", "tts.duration_predictor.", "tts.projection.", "tts.gst."))
+                        and not (k.startswith("tts.gst.") and k.endswith(".num_batches_tracked")))
     if unexpected:
         raise KeyError(f"FastSpeech2 checkpoint: unexpected keys {unexpected}")
     for key, name, sl, kind in km:
@@ -177,6 +293,10 @@ def load_into(store: ParamStore, c: FS2DurationConfig, sd) -> None:
             src = src[:, sl[0]:sl[1]]
         elif kind == "conv":
             src = src.permute(0, 2, 1)
+        elif kind == "conv2d":
+            src = src.permute(2, 3, 1, 0)
+        elif kind == "gru_ih":
+            src = src.reshape(src.shape[0], sl[0], sl[1]).permute(0, 2, 1)
         dst.copy_(src.reshape(dst.shape).to(device=store.device, dtype=torch.float32))
 
 
@@ -226,21 +346,29 @@ class FS2DurationModel:
         self._ids_host = torch.zeros(cfg.max_len, dtype=torch.int64, pin_memory=self.dev.type == "cuda")
         self._ids_dev = torch.zeros(cfg.max_len, dtype=torch.int64, device=self.dev)
         self._stage_host = self._stage_dev = None       # predict_frames_batch: ids and lengths of one call, grow-only
+        self.feats = None
+        self._gst = None        # what the style encoder derives from the weights alone (see _gst_derived)
+        self._gst_lens = None   # (pinned host, device, copy event): int32 length table of one style_embedding_batch call
+        if cfg.use_gst:
+            from .features import LogMelFbank
+            self.feats = LogMelFbank(**cfg.gst_feats_conf, device=self.dev)
 
     # ---- loading ---------------------------------------------------------------------------------------------------------
     def load_state_dict(self, sd):
         load_into(self.store, self.c, sd)
+        self._gst = None
         return self
 
     @staticmethod
-    def from_file(config_file: Optional[str], model_file: str, device="cuda") -> "FS2DurationModel":
-        """As espnet2's Text2Speech(train_config, model_file): config_file=None reads config.yaml next to model_file."""
+    def from_file(config_file: Optional[str], model_file: str, device="cuda", gst: bool = False) -> "FS2DurationModel":
+        """As espnet2's Text2Speech(train_config, model_file): config_file=None reads config.yaml next to model_file.
+        gst=True loads a use_gst: true checkpoint (FS2DurationConfig.from_espnet)."""
         import yaml
         if config_file is None:
             config_file = os.path.join(os.path.dirname(os.path.abspath(model_file)), "config.yaml")
         with open(config_file) as f:
             conf = yaml.safe_load(f)
-        model = FS2DurationModel(FS2DurationConfig.from_espnet(conf), device)
+        model = FS2DurationModel(FS2DurationConfig.from_espnet(conf, gst=gst), device)
         return model.load_state_dict(torch.load(model_file, map_location="cpu"))
 
     # ---- forward ---------------------------------------------------------------------------------------------------------
@@ -263,15 +391,122 @@ class FS2DurationModel:
         ops.linear_fwd(sn, self.store.p["spk.ws"], out, bias=self.store.p["spk.b"], compute=F32)
         return out
 
-    def forward_ids(self, ids, spk_bias=None):
-        """ids: device int64 [T] (eos included).  Returns device tensors (hs [T][d], logd [T], frames [T] int64) valid
-        until the next call."""
+    # ---- the style encoder -----------------------------------------------------------------------------------------------
+    def _gst_derived(self):
+        """What depends on the weights only, once per load: BatchNorm2d's running statistics folded into (scale, shift) per
+        conv layer, and the keys and values of the style tokens, linear_{k,v}(tanh(gst_embs)) [tokens][d] (fp64, then fp32)."""
+        if self._gst is None:
+            p, buf, out = self.store.p, self.store.buf, {}
+            for i in range(len(self.c.gst_conv_chans)):
+                n = f"gst.conv.{i}.bn."
+                sc = p[n + "g"].double() / torch.sqrt(buf[n + "rv"].double() + 1e-5)
+                out[f"scale.{i}"] = sc.float().contiguous()
+                out[f"shift.{i}"] = (p[n + "b"].double() - buf[n + "rm"].double() * sc).float().contiguous()
+            e = torch.tanh(p["gst.stl.embs"].double())
+            for n in ("k", "v"):
+                out[n] = (e @ p[f"gst.stl.{n}.w"].double().t() + p[f"gst.stl.{n}.b"].double()).float().contiguous()
+            self._gst = out
+        return self._gst
+
+    def style_from_mel(self, mel, lens=None, host_lens=None, keep=None):
+        """The StyleEncoder over log-mel frames: mel device fp32 [B][T][n_mels], row b valid for its own length and holding
+        anything behind it.  lens: device int32 [L + 1][B], row l the rows' time lengths in front of conv layer l (row L: the
+        GRU's steps), None when every row is T long.  Returns style [B][d] (a fresh tensor); keep: a dict that receives the last
+        conv output [B][T'][F'][C] and ref_embs [B][H] (views of the workspace, valid until the next call).
+        len(gst_conv_chans) + 2 launches whatever B is."""
+        c, p, ws = self.c, self.store.p, self.ws
+        if not c.use_gst:
+            raise ValueError("this checkpoint has no GST style encoder")
+        if mel.dim() != 3 or mel.shape[2] != c.n_mels or mel.dtype != torch.float32 or not mel.is_contiguous():
+            raise ValueError(f"mel must be a contiguous fp32 [B][T][{c.n_mels}] tensor")
+        g, plan = self._gst_derived(), c.gst_plan()
+        B, T = int(mel.shape[0]), int(mel.shape[1])
+        if T < 1:
+            raise ValueError("a prompt of no frames")
+        k, s, H, d = c.gst_conv_kernel, c.gst_conv_stride, c.gst_gru_units, c.adim
+        x = mel.view(B, T, c.n_mels, 1)
+        for i, (cin, cout, Fi, Fo) in enumerate(plan):
+            To = gst_out_len(T, k, s)
+            y = ws.get(f"gst.y{i}", (B, To, Fo, cout))
+            ops.gst_conv_bn_relu(x, p[f"gst.conv.{i}.w"], g[f"scale.{i}"], g[f"shift.{i}"], y,
+                                 None if lens is None else lens[i], k, s)
+            x, T = y, To
+        gi = ws.get("gst.gi", (B * T, 3 * H))
+        ops.linear_fwd(x.view(B * T, -1), p["gst.gru.wih"], gi, bias=p["gst.gru.bih"], compute=F32)
+        ref = ws.get("gst.ref", (B, H))
+        style = torch.empty(B, d, dtype=torch.float32, device=self.dev)
+        ops.gst_gru_stl(gi.view(B, T, 3 * H), p["gst.gru.whh"], p["gst.gru.bhh"], None if lens is None else lens[len(plan)],
+                        p["gst.stl.q.w"], p["gst.stl.q.b"], g["k"], g["v"], p["gst.stl.out.w"], p["gst.stl.out.b"], ref, style,
+                        c.gst_heads)
+        if keep is not None:
+            keep["conv"], keep["ref_embs"] = x, ref
+        return style
+
+    def _gst_len_table(self, frames):
+        """Device int32 [L + 1][B]: the time lengths of the rows in front of every conv layer and of the GRU, through one
+        pinned buffer in one copy that the host does not wait for."""
+        c, B = self.c, len(frames)
+        L1 = len(c.gst_conv_chans) + 1
+        tab = np.zeros((L1, B), np.int32)
+        tab[0] = frames
+        for l in range(1, L1):
+            tab[l] = [gst_out_len(int(n), c.gst_conv_kernel, c.gst_conv_stride) for n in tab[l - 1]]
+        if self._gst_lens is None or self._gst_lens[0].numel() < tab.size:
+            self._gst_lens = (torch.zeros(2 * tab.size, dtype=torch.int32, pin_memory=True),
+                              torch.zeros(2 * tab.size, dtype=torch.int32, device=self.dev), torch.cuda.Event())
+        else:       # the previous table must have left the pinned buffer (usually long ago: its style has been used since)
+            self._gst_lens[2].synchronize()
+        host, dev, copied = self._gst_lens
+        host[:tab.size].copy_(torch.from_numpy(tab.reshape(-1)))
+        dev[:tab.size].copy_(host[:tab.size], non_blocking=True)
+        copied.record()
+        return dev[:tab.size].view(L1, B)
+
+    def _prompt_mel(self, wav):
+        """(log-mel [1][F][n_mels] on the device, F) of one prompt at its exact length, by the TTS model's own extractor,
+        unnormalised, as duration_predict feeds it to the style encoder."""
+        w = torch.as_tensor(np.asarray(wav, dtype=np.float32)).reshape(1, -1)
+        if w.shape[1] <= self.feats.n_fft // 2:
+            raise ValueError(f"a prompt of {w.shape[1]} samples is too short for the extractor's reflect padding")
+        mel, _ = self.feats(w)
+        return mel, int(mel.shape[1])
+
+    def style_embedding(self, wav):
+        """Style embedding of one prompt waveform (1-D, at the extractor's sampling rate): device [1][d]."""
+        if not self.c.use_gst:
+            raise ValueError("this checkpoint has no GST style encoder")
+        mel, _ = self._prompt_mel(wav)
+        return self.style_from_mel(mel.contiguous())
+
+    def style_embedding_batch(self, wavs):
+        """Style embeddings of several prompts: device [B][d].  Every prompt's log-mel is taken at its exact length (a padded
+        batch would reflect at the padded end); the conv layers, the GRU and the token attention then run as ONE ragged pass
+        over the mels padded to the longest, row b computed as style_embedding computes it alone."""
+        if not self.c.use_gst:
+            raise ValueError("this checkpoint has no GST style encoder")
+        wavs = list(wavs)
+        if not wavs:
+            raise ValueError("no prompts")
+        if len(wavs) == 1:
+            return self.style_embedding(wavs[0])
+        mels = [self._prompt_mel(w) for w in wavs]
+        frames = [F for _, F in mels]
+        x = self.ws.get("gst.mel", (len(wavs), max(frames), self.c.n_mels))
+        for b, (m, F) in enumerate(mels):
+            x[b, :F].copy_(m[0])
+        return self.style_from_mel(x, self._gst_len_table(frames))
+
+    def forward_ids(self, ids, spk_bias=None, style=None):
+        """ids: device int64 [T] (eos included); style: device [1][d] from style_embedding (a GST model needs it, another
+        model refuses it), added to every encoder output row in front of the x-vector integration.  Returns device tensors
+        (hs [T][d], logd [T], frames [T] int64) valid until the next call."""
         c, p, ws = self.c, self.store.p, self.ws
         T, d = int(ids.shape[0]), c.adim
         if not 1 <= T <= c.max_len:
             raise ValueError(f"sequence length {T} outside 1..{c.max_len}")
         if spk_bias is not None and c.spk_embed_dim <= 0:
             raise ValueError("spk_bias given but the checkpoint has no x-vector projection")
+        self._check_style(style, 1, None)
         eng = self.eng
         # Embedding * sqrt(d) (+ pe: legacy rel-pos only scales) -- the MLM prologue kernel with no speech frames
         xs = ws.get("emb.xs", (T, d))
@@ -282,6 +517,8 @@ class FS2DurationModel:
         for i in range(c.enc_blocks):
             x = eng.block_fwd(f"enc.{i}", x, pos, keymask, 1, T)
         hs = eng._ln_fwd("enc.after", x, "enc.after", out_dtype=torch.float32)
+        if style is not None:
+            ops.gst_add_style(hs, style, 1, T)
         if spk_bias is not None:
             if c.spk_integration == "add":
                 ops.bias_act(hs, spk_bias, ACT_NONE)
@@ -302,12 +539,26 @@ class FS2DurationModel:
                           eps=1e-12, offset=c.dp_offset)
         return hs, logd, frames
 
-    def forward_ids_batch(self, ids, lens, spk_bias=None):
+    def _check_style(self, style, B, rows):
+        if not self.c.use_gst:
+            if style is not None:
+                raise ValueError("style given but the checkpoint has no GST style encoder")
+            return
+        if style is None:
+            raise ValueError("a GST model needs style= (style_embedding of the prompt) with every forward")
+        if style.dim() != 2 or style.shape[1] != self.c.adim or style.dtype != torch.float32 or not style.is_contiguous():
+            raise ValueError(f"style must be a contiguous fp32 [rows][{self.c.adim}] tensor")
+        if rows is None and style.shape[0] not in (1, B):
+            raise ValueError(f"style has {style.shape[0]} rows for {B} sequences")
+
+    def forward_ids_batch(self, ids, lens, spk_bias=None, style=None, style_rows=None):
         """ids: device int64 [B][Tmax] (eos included; entries behind a row's length: any valid id), lens: device int32 [B],
         1 <= lens[b] <= Tmax.  One padded forward whose row b is computed as forward_ids computes it alone at lens[b]
         (MLMEngine.block_fwd with lens); one speaker bias for the whole call.  Returns device tensors (hs [B][Tmax][d],
         logd [B][Tmax], frames [B][Tmax] int64) valid until the next call; entries behind lens[b] are finite and mean nothing
         (hs is 0 there when the predictor's convs have more than one tap).
+        style: device [B][d] (row b for sequence b), [1][d] (one prompt for all), or any [S][d] with style_rows, device int32 [B]:
+        sequence b takes style row style_rows[b].
         The number of launches does not depend on B."""
         c, p, ws = self.c, self.store.p, self.ws
         if ids.dim() != 2 or ids.dtype != torch.int64 or not ids.is_contiguous():
@@ -317,6 +568,7 @@ class FS2DurationModel:
             raise ValueError(f"sequence length {T} outside 1..{c.max_len}")
         if spk_bias is not None and c.spk_embed_dim <= 0:
             raise ValueError("spk_bias given but the checkpoint has no x-vector projection")
+        self._check_style(style, B, style_rows)
         eng, M = self.eng, B * T
         if self._tpos0.numel() < M:
             self._tpos0 = torch.zeros(M, dtype=torch.int64, device=self.dev)
@@ -328,6 +580,8 @@ class FS2DurationModel:
         for i in range(c.enc_blocks):
             x = eng.block_fwd(f"enc.{i}", x, pos, None, B, T, lens=lens)
         hs = eng._ln_fwd("enc.after", x, "enc.after", out_dtype=torch.float32)
+        if style is not None:
+            ops.gst_add_style(hs, style, B, T, rows=style_rows)
         if spk_bias is not None:
             if c.spk_integration == "add":
                 ops.bias_act(hs, spk_bias, ACT_NONE)
@@ -365,7 +619,8 @@ class FS2DurationModel:
             out.append(cur)
         return out
 
-    def predict_frames_batch(self, phn_lists, spk_bias=None, max_score_elems: int = 1 << 24) -> List[np.ndarray]:
+    def predict_frames_batch(self, phn_lists, spk_bias=None, max_score_elems: int = 1 << 24, style=None,
+                             style_rows=None) -> List[np.ndarray]:
         """predict_frames for several phone lists: one int64 array per list (eos entry included), in the order given.
         The ids of all lists go up through one pinned buffer in one copy and all frames come down in one: one host
         synchronisation per call.  The lists are sorted by length and cut into chunks of B rows padded to the chunk's longest,
@@ -373,22 +628,34 @@ class FS2DurationModel:
         score-sized fp32 tensors of the materialised attention (content scores, position scores, probabilities): the default
         2^24 holds them to 192 MiB together, and e.g. 90 lists of 300 phones at H = 2 still make one chunk.  A list longer
         than the cap allows runs alone.  A chunk of one list, and so a call with one list, takes the B = 1 path of
-        predict_frames; every row of a larger chunk is computed as if alone, so the frames do not depend on the chunking."""
+        predict_frames; every row of a larger chunk is computed as if alone, so the frames do not depend on the chunking.
+        style (a GST model): device [len(phn_lists)][d], or [1][d] for one prompt behind all lists, or [S][d] with style_rows, a
+        host list naming the style row of every list; the row indices travel with the ids, so a list keeps its style wherever
+        the sorting and chunking put it."""
         lists = [self.tokens_to_ids(list(ph)) for ph in phn_lists]
         if not lists:
             return []
+        srow = None
+        if style is not None:
+            self._check_style(style, len(lists), style_rows)
+            srow = [0] * len(lists) if style_rows is None and style.shape[0] == 1 else \
+                list(range(len(lists))) if style_rows is None else [int(r) for r in style_rows]
+            if len(srow) != len(lists) or min(srow) < 0 or max(srow) >= style.shape[0]:
+                raise ValueError("style_rows does not fit the phone lists and the style rows")
+        one = lambda i: None if style is None else style[srow[i]:srow[i] + 1]
         if len(lists) == 1:
-            return [self.predict_frames(list(phn_lists[0]), spk_bias)]
+            return [self.predict_frames(list(phn_lists[0]), spk_bias, one(0))]
         lengths = [len(x) for x in lists]
         if max(lengths) > self.c.max_len:
             raise ValueError(f"{max(lengths)} tokens: more than max_len {self.c.max_len}")
         chunks = self._chunks(lengths, int(max_score_elems))
-        # staging layout (int64 words): per chunk its padded ids [B][Tmax], then all lengths as int32 pairs
+        # staging layout (int64 words): per chunk its padded ids [B][Tmax], then all lengths as int32 pairs (with a style:
+        # the style rows as int32 behind the lengths, in the same order)
         offs, n_ids = [], 0
         for ch in chunks:
             offs.append(n_ids)
             n_ids += len(ch) * lengths[ch[-1]]
-        n_len = (len(lists) + 1) // 2
+        n_len = (len(lists) + 1) // 2 if style is None else len(lists)
         total = n_ids + n_len
         if self._stage_host is None or self._stage_host.numel() < total:
             cap = max(total, 2 * (self._stage_host.numel() if self._stage_host is not None else 0))
@@ -404,6 +671,8 @@ class FS2DurationModel:
             for k, i in enumerate(ch):
                 blk[k, :lengths[i]] = lists[i]
                 hl[r + k] = lengths[i]
+                if style is not None:
+                    hl[len(lists) + r + k] = srow[i]
             r += len(ch)
         self._stage_host[:total].copy_(torch.from_numpy(host))
         dev = self._stage_dev[:total]
@@ -414,9 +683,10 @@ class FS2DurationModel:
         for ch, o in zip(chunks, offs):
             B, T = len(ch), lengths[ch[-1]]
             if B == 1:
-                _, _, frames = self.forward_ids(dev[o:o + T], spk_bias)
+                _, _, frames = self.forward_ids(dev[o:o + T], spk_bias, one(ch[0]))
             else:
-                _, _, frames = self.forward_ids_batch(dev[o:o + B * T].view(B, T), dev_lens[r:r + B], spk_bias)
+                rows = None if style is None else dev_lens[len(lists) + r:len(lists) + r + B]
+                _, _, frames = self.forward_ids_batch(dev[o:o + B * T].view(B, T), dev_lens[r:r + B], spk_bias, style, rows)
             out[o:o + B * T].copy_(frames.reshape(-1))
             r += B
         got = out.cpu().numpy()
@@ -427,7 +697,7 @@ class FS2DurationModel:
                 res[i] = got[o + k * T:o + k * T + lengths[i]].copy()
         return res
 
-    def predict_frames(self, phns, spk_bias=None) -> np.ndarray:
+    def predict_frames(self, phns, spk_bias=None, style=None) -> np.ndarray:
         """Frames per phone of `phns` plus the eos entry (int64, host).  One host synchronisation."""
         ids = self.tokens_to_ids(phns)
         T = len(ids)
@@ -437,7 +707,7 @@ class FS2DurationModel:
         self._ids_host[:T].copy_(torch.as_tensor(ids, dtype=torch.int64))
         dev_ids = self._ids_dev[:T]
         dev_ids.copy_(self._ids_host[:T], non_blocking=True)
-        _, _, frames = self.forward_ids(dev_ids, spk_bias)
+        _, _, frames = self.forward_ids(dev_ids, spk_bias, style)
         return frames.cpu().numpy()
 
     def duration_fn(self, fs: int, hop_length: int, spembs=None):
@@ -445,12 +715,61 @@ class FS2DurationModel:
         SpeechEditor(duration_fn=...): seconds per phone, frames * hop_length / fs in float32 as the reference computes it,
         eos dropped.  spembs=None runs without the x-vector integration, as duration_predict does with sid=None.
         The callable's .batch(list of phone lists) answers several lists from one batched forward (SpeechEditor.plan_batch
-        uses it when it is there)."""
+        uses it when it is there).
+
+        A GST model's durations depend on the prompt (duration_predict's wav_org), so its callable has needs_prompt = True and
+        refuses a bare fn(phns): fn.with_prompt(wav) computes the prompt's style embedding once and returns a plain
+        phns -> seconds callable (with .batch) bound to it; fn.batch(phn_lists, prompts=[...]) takes one prompt per list and
+        computes one style embedding per distinct prompt OBJECT, all of them in one ragged pass.  fs must be the sampling rate
+        of the model's own log-mel extractor."""
         bias = self.speaker_bias(spembs) if spembs is not None else None
         hop, fs32 = int(hop_length), np.float32(fs)
 
         def seconds(frames):
             return ((frames * hop).astype(np.float32) / fs32)[:-1].tolist()
+
+        if self.c.use_gst:
+            if int(fs) != self.feats.fs:
+                raise ValueError(f"fs {fs} is not the sampling rate of the checkpoint's log-mel extractor ({self.feats.fs})")
+
+            def with_prompt(wav):
+                cache = []
+
+                def style():        # on the first query: a plan that asks for no durations costs no style embedding
+                    if not cache:
+                        cache.append(self.style_embedding(wav))
+                    return cache[0]
+
+                def fn(phns):
+                    return seconds(self.predict_frames(list(phns), bias, style()))
+
+                def batch(phn_lists, max_score_elems: int = 1 << 24):
+                    return [seconds(f) for f in self.predict_frames_batch(list(phn_lists), bias, max_score_elems, style())]
+                fn.batch = batch
+                return fn
+
+            def fn(phns):
+                raise ValueError("the durations of a GST model depend on the prompt: use with_prompt(wav)(phns) or "
+                                 "batch(phn_lists, prompts=[...])")
+
+            def batch(phn_lists, prompts=None, max_score_elems: int = 1 << 24):
+                """One list of seconds per phone list; prompts: one waveform per list (the same object may repeat)."""
+                phn_lists = list(phn_lists)
+                if prompts is None or len(prompts) != len(phn_lists):
+                    raise ValueError("a GST model needs prompts=[...], one prompt waveform per phone list")
+                if not phn_lists:
+                    return []
+                first = {}
+                rows = [first.setdefault(id(w), len(first)) for w in prompts]
+                distinct = [None] * len(first)
+                for w, r in zip(prompts, rows):
+                    distinct[r] = w
+                style = self.style_embedding_batch(distinct)
+                return [seconds(f) for f in self.predict_frames_batch(phn_lists, bias, max_score_elems, style, rows)]
+            fn.needs_prompt = True
+            fn.with_prompt = with_prompt
+            fn.batch = batch
+            return fn
 
         def fn(phns):
             return seconds(self.predict_frames(list(phns), bias))

@@ -700,6 +700,47 @@ def l2_normalize(x, y, eps=1e-12):
     L.check(L.load().a3t_l2_normalize(_ptr(x), _ptr(y), B, n, eps, _stream()), "l2_normalize")
 
 
+def gst_conv_bn_relu(x, w, scale, shift, y, lens, k, s):
+    """One GST reference-encoder layer: x [B][Tin][Fin][Cin] -> y [B][Tout][Fout][Cout] = relu(conv2d * scale + shift),
+    w [k][k][Cin][Cout], stride s, padding (k - 1) // 2; lens: device int32 [B] (time lengths of x's rows) or None."""
+    _ragged_f32("gst_conv_bn_relu", x, w, scale, shift, y)
+    B, Tin, Fin, Cin = x.shape
+    Cout, p = w.shape[3], (k - 1) // 2
+    want = (B, (Tin + 2 * p - k) // s + 1, (Fin + 2 * p - k) // s + 1, Cout)
+    if tuple(w.shape) != (k, k, Cin, Cout) or tuple(y.shape) != want or scale.numel() != Cout or shift.numel() != Cout or \
+            (lens is not None and lens.numel() != B):
+        raise ValueError("gst_conv_bn_relu: shapes do not fit")
+    L.check(L.load().a3t_gst_conv_bn_relu(_ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(y),
+                                          _ptr(_i32(lens, "lens")) if lens is not None else None, B, Tin, Fin, Cin, Cout, k, s,
+                                          _stream()), "gst_conv_bn_relu")
+
+
+def gst_gru_stl(gi, w_hh, b_hh, lens, w_q, b_q, k_tok, v_tok, w_out, b_out, ref_embs, style, heads):
+    """gi [B][T][3H] (input projections of every step) -> ref_embs [B][H] (or None) and style [B][d]: the GRU over each row's
+    own lens[b] steps and the style-token attention (k_tok / v_tok [tokens][d])."""
+    _ragged_f32("gst_gru_stl", gi, w_hh, b_hh, w_q, b_q, k_tok, v_tok, w_out, b_out, ref_embs, style)
+    B, T, H3 = gi.shape
+    H, (tokens, d) = H3 // 3, k_tok.shape
+    if tuple(w_hh.shape) != (H3, H) or b_hh.numel() != H3 or tuple(w_q.shape) != (d, H) or tuple(v_tok.shape) != (tokens, d) \
+            or tuple(w_out.shape) != (d, d) or tuple(style.shape) != (B, d) or \
+            (ref_embs is not None and tuple(ref_embs.shape) != (B, H)) or (lens is not None and lens.numel() != B):
+        raise ValueError("gst_gru_stl: shapes do not fit")
+    L.check(L.load().a3t_gst_gru_stl(_ptr(gi), _ptr(w_hh), _ptr(b_hh), _ptr(_i32(lens, "lens")) if lens is not None else None,
+                                     _ptr(w_q), _ptr(b_q), _ptr(k_tok), _ptr(v_tok), _ptr(w_out), _ptr(b_out), _ptr(ref_embs),
+                                     _ptr(style), B, T, H, d, heads, tokens, _stream()), "gst_gru_stl")
+
+
+def gst_add_style(hs, style, B, T, rows=None):
+    """hs [B*T][d] (or [B][T][d]) += style [S][d]: row b takes style row rows[b] (device int32 [B]); without rows its own
+    (S == B) or the only one (S == 1)."""
+    _ragged_f32("gst_add_style", hs, style)
+    d = hs.shape[-1]
+    if hs.numel() != B * T * d or style.dim() != 2 or style.shape[1] != d or (rows is not None and rows.numel() != B):
+        raise ValueError("gst_add_style: shapes do not fit")
+    L.check(L.load().a3t_gst_add_style(_ptr(hs), _ptr(style), _ptr(_i32(rows, "rows")) if rows is not None else None, B, T, d,
+                                       style.shape[0], _stream()), "gst_add_style")
+
+
 def dropout(x, y, p, key, scale=1.0):
     L.check(L.load().a3t_dropout(_ptr(x), _dt(x), _ptr(y), _dt(y), x.numel(), p, key, scale, _stream()), "dropout")
 

@@ -418,6 +418,29 @@ int a3t_duration_head(const float* z, const float* gamma, const float* beta, con
  * fastspeech2.py:797-805). */
 int a3t_l2_normalize(const float* x, float* y, int B, int n, float eps, void* stream);
 
+/* GST style encoder of a gst+xvector FastSpeech2 (espnet2/tts/gst/style_encoder.py; csrc/gst.hip): fp32, eval mode, forward
+ * only.  A batch of prompts is padded to the longest; lens [B] int32 on the device (NULL: every row is full) and row b gets
+ * what it would get alone at its own length.
+ * a3t_gst_conv_bn_relu: one ReferenceEncoder layer, y = relu(conv2d(x) * scale + shift).  x [B][Tin][Fin][Cin] and
+ *   y [B][Tout][Fout][Cout] channels-last, w [k][k][Cin][Cout] (time tap, frequency tap), k odd, stride s, padding
+ *   p = (k - 1) / 2, Xout = (Xin + 2p - k) / s + 1, no conv bias; scale / shift [Cout] are BatchNorm2d's running statistics
+ *   folded (scale = gamma / sqrt(var + eps), shift = beta - mean * scale).  Row b reads zeros at t >= n = lens[b] whatever x
+ *   holds there, and t' >= n' = (n + 2p - k) / s + 1 is stored as 0 (BatchNorm's shift would make it non-zero).
+ * a3t_gst_gru_stl: one workgroup per prompt.  gi [B][T][3H] = W_ih x_t + b_ih of every step; the GRU (gate order r, z, n;
+ *   n = tanh(gi_n + r * (W_hn h + b_hn)), h' = (1 - z) * n + z * h; w_hh [3H][H], b_hh [3H]) runs lens[b] steps from h = 0,
+ *   then the style-token attention: q = w_q h + b_q (w_q [d][H]), per head softmax over the tokens of
+ *   q_h . k_tok[:, h] / sqrt(d / heads) times v_tok[:, h], then w_out [d][d], b_out.  k_tok / v_tok [tokens][d] are
+ *   linear_k / linear_v of tanh(gst_embs), which depend on weights only.  ref_embs [B][H] (the last h; may be NULL),
+ *   style [B][d].  H <= 128, d <= 1024, d % heads == 0, heads * tokens <= 512; A3T_EINVAL otherwise.
+ * a3t_gst_add_style: hs [B][T][d] += style [S][d], row b taking style row rows[b] (int32 [B] on the device, clamped to
+ *   0..S-1), or with rows NULL row b (S == B) or the one row (S == 1); A3T_EINVAL for another S. */
+int a3t_gst_conv_bn_relu(const float* x, const float* w, const float* scale, const float* shift, float* y,
+                         const int32_t* lens, int B, int Tin, int Fin, int Cin, int Cout, int k, int s, void* stream);
+int a3t_gst_gru_stl(const float* gi, const float* w_hh, const float* b_hh, const int32_t* lens, const float* w_q,
+                    const float* b_q, const float* k_tok, const float* v_tok, const float* w_out, const float* b_out,
+                    float* ref_embs, float* style, int B, int T, int H, int d, int heads, int tokens, void* stream);
+int a3t_gst_add_style(float* hs, const float* style, const int32_t* rows, int B, int T, int d, int S, void* stream);
+
 /* Dropout (torch.nn.Dropout sites of the path).  Counter-based: keep = f(key, element index), so the
  * same key reproduces the mask in the backward pass and inside GEMM epilogues; no mask tensors.
  * y = scale * x * keep/(1-p); in place allowed; x / y may be fp32 or bf16. */
