@@ -23,22 +23,37 @@ __device__ __forceinline__ float wmax(float v) {
 // ------------------------------------------------------------------------------------------
 // GLU + depthwise conv.  Block = 64 channels (lanes) x 4 row lanes; time tile TT rows of one
 // utterance; the GLU'd window [t0-pad, t0+TT+pad) x 64 channels lives in LDS (<= 94x64 floats).
+// RAGGED (fp32, forward only): row b of the padded [B][Tseq] batch has n = lens[b] frames and is computed as if it had been
+// passed alone: a tap reads 0 for t >= n, glu and z are stored as 0 for n <= t < Tseq.
 // ------------------------------------------------------------------------------------------
 #define DW_TT 64
 #define DW_KMAX 31
 
-template <int KT>
+template <int KT, bool RAGGED>
 __global__ __launch_bounds__(256) void glu_dwconv_fwd_kernel(const void* __restrict__ g, int g_dt,
                                                              const float* __restrict__ wdw,
                                                              const float* __restrict__ bdw, void* __restrict__ glu,
                                                              int glu_dt, float* __restrict__ z, int C, int K, int Tseq,
-                                                             int tiles_t) {
+                                                             int tiles_t, const int32_t* __restrict__ lens) {
     __shared__ float win[DW_TT + DW_KMAX - 1][64];
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + tx;
     const int b = blockIdx.y / tiles_t, t0 = (blockIdx.y % tiles_t) * DW_TT;
     const int pad = (K - 1) / 2;
     const int64_t mbase = (int64_t)b * Tseq;
+    int n = Tseq;      // what a tap may read
+    if constexpr (RAGGED) {
+        g_dt = glu_dt = A3T_F32;
+        n = ragged_len(lens, b, Tseq);
+        if (t0 >= n) {      // (block-uniform) a tile wholly behind the row's length only stores zeros
+            if (c < C)
+                for (int r = ty; r < DW_TT && t0 + r < Tseq; r += 4) {
+                    ((float*)glu)[(mbase + t0 + r) * (int64_t)C + c] = 0.f;
+                    z[(mbase + t0 + r) * (int64_t)C + c] = 0.f;
+                }
+            return;
+        }
+    }
     const int rows = DW_TT + K - 1;
     // (batches of 8 rows per thread, loads issued back to back -- see the backward kernel)
     for (int rb = ty; rb < rows; rb += 32) {
@@ -46,7 +61,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_fwd_kernel(const void* __restr
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int r = rb + 4 * u, t = t0 - pad + r;
-            const bool ok = (c < C) && (r < rows) && (t >= 0) && (t < Tseq);
+            const bool ok = (c < C) && (r < rows) && (t >= 0) && (t < n);
             const int64_t gi = ok ? (mbase + t) * (int64_t)(2 * C) + c : 0;
             ga[u] = ldx(g, g_dt, gi);
             gb[u] = ldx(g, g_dt, gi + (ok ? C : 0));
@@ -54,9 +69,10 @@ __global__ __launch_bounds__(256) void glu_dwconv_fwd_kernel(const void* __restr
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int r = rb + 4 * u, t = t0 - pad + r;
-            const bool ok = (c < C) && (r < rows) && (t >= 0) && (t < Tseq);
+            const bool ok = (c < C) && (r < rows) && (t >= 0) && (t < n);
             const float v = ok ? ga[u] * sigm(gb[u]) : 0.f;
-            if (ok && r >= pad && r < pad + DW_TT) stx(glu, glu_dt, (mbase + t) * (int64_t)C + c, v);
+            const bool st = RAGGED ? (c < C) && (t < Tseq) : ok;      // what is stored is bounded by Tseq
+            if (st && r >= pad && r < pad + DW_TT) stx(glu, glu_dt, (mbase + t) * (int64_t)C + c, v);
             if (r < rows) win[r][tx] = v;
         }
     }
@@ -77,7 +93,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_fwd_kernel(const void* __restr
 #pragma unroll
                 for (int k = 0; k < KT; ++k) acc += w[k] * v[tt + k];
                 int t = t0 + r0 + tt;
-                if (t < Tseq) z[(mbase + t) * (int64_t)C + c] = acc;
+                if (t < Tseq) z[(mbase + t) * (int64_t)C + c] = (!RAGGED || t < n) ? acc : 0.f;
             }
         }
         return;
@@ -89,7 +105,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_fwd_kernel(const void* __restr
 #pragma unroll
         for (int k = 0; k < KT; ++k)
             if (k < K) acc += w[k] * win[r + k][tx];
-        z[(mbase + t) * (int64_t)C + c] = acc;
+        z[(mbase + t) * (int64_t)C + c] = (!RAGGED || t < n) ? acc : 0.f;
     }
 }
 
@@ -100,23 +116,36 @@ int a3t_glu_dwconv_bwd_vec(const float* dz, const void* g, const void* glu, cons
                            float* dbdw, float* dg_colsum, int M, int C, int K, int Tseq, hipStream_t stream);
 static inline bool dw_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// one launcher for the plain entry point (lens == nullptr) and the ragged one
+template <bool RAGGED>
+static int glu_dwconv_fwd_launch(const void* g, int g_dtype, const float* wdw, const float* bdw, void* glu, int glu_dtype,
+                                 float* z, int B, int C, int K, int Tseq, const int32_t* lens, hipStream_t stream) {
+    const int tiles_t = (Tseq + DW_TT - 1) / DW_TT;
+    dim3 grid((C + 63) / 64, B * tiles_t);
+#define CALL(KT)                                                                                                         \
+    hipLaunchKernelGGL((glu_dwconv_fwd_kernel<KT, RAGGED>), grid, dim3(256), 0, stream, g, g_dtype, wdw, bdw, glu, glu_dtype, \
+                       z, C, K, Tseq, tiles_t, lens)
+    if (K <= 7) CALL(7);
+    else if (K <= 15) CALL(15);
+    else CALL(DW_KMAX);
+#undef CALL
+    return (int)hipGetLastError();
+}
+
 extern "C" int a3t_glu_dwconv_fwd(const void* g, int g_dtype, const float* wdw, const float* bdw, void* glu,
                                   int glu_dtype, float* z, int M, int C, int K, int Tseq, void* stream) {
     if (K > DW_KMAX || (K & 1) == 0 || Tseq <= 0 || M % Tseq) return A3T_EINVAL;
     if (g_dtype == A3T_BF16 && glu_dtype == A3T_BF16 && C % 64 == 0 && dw_al16(g) && dw_al16(glu) && dw_al16(z))
         return a3t_glu_dwconv_fwd_vec(g, wdw, bdw, glu, z, M, C, K, Tseq, (hipStream_t)stream);
-    int B = M / Tseq, tiles_t = (Tseq + DW_TT - 1) / DW_TT;
-    dim3 grid((C + 63) / 64, B * tiles_t);
-    if (K <= 7)
-        hipLaunchKernelGGL(glu_dwconv_fwd_kernel<7>, grid, dim3(256), 0, (hipStream_t)stream, g, g_dtype, wdw, bdw, glu,
-                           glu_dtype, z, C, K, Tseq, tiles_t);
-    else if (K <= 15)
-        hipLaunchKernelGGL(glu_dwconv_fwd_kernel<15>, grid, dim3(256), 0, (hipStream_t)stream, g, g_dtype, wdw, bdw, glu,
-                           glu_dtype, z, C, K, Tseq, tiles_t);
-    else
-        hipLaunchKernelGGL(glu_dwconv_fwd_kernel<DW_KMAX>, grid, dim3(256), 0, (hipStream_t)stream, g, g_dtype, wdw, bdw,
-                           glu, glu_dtype, z, C, K, Tseq, tiles_t);
-    return (int)hipGetLastError();
+    return glu_dwconv_fwd_launch<false>(g, g_dtype, wdw, bdw, glu, glu_dtype, z, M / Tseq, C, K, Tseq, nullptr,
+                                        (hipStream_t)stream);
+}
+
+extern "C" int a3t_glu_dwconv_fwd_ragged(const float* g, const float* wdw, const float* bdw, float* glu, float* z,
+                                         const int32_t* lens, int B, int Tseq, int C, int K, void* stream) {
+    if (K > DW_KMAX || K <= 0 || (K & 1) == 0 || Tseq <= 0 || B <= 0 || C <= 0 || !lens) return A3T_EINVAL;
+    if ((int64_t)B * ((Tseq + DW_TT - 1) / DW_TT) > 65535) return A3T_EINVAL;      // grid.y
+    return glu_dwconv_fwd_launch<true>(g, A3T_F32, wdw, bdw, glu, A3T_F32, z, B, C, K, Tseq, lens, (hipStream_t)stream);
 }
 
 // One block = 64 channels x `tiles_per_block` consecutive time tiles of one utterance: the weight
@@ -415,32 +444,51 @@ extern "C" int a3t_add_pos_bias_bwd(const void* dqu, const void* dqv, void* dqkv
 // i.e. each shifted row is two contiguous segments of BD -> coalesced reads, no padded copy.
 // (Equivalently BD[r][c] <-> flat score index r*(T+1) + c - (T-1): consecutive BD rows are consecutive flat windows
 //  of the score matrix separated by the one skipped element S[r][r+1].)
-__device__ __forceinline__ float bd_shift(const void* __restrict__ BDz, int dt, int T, int i, int j) {
-    if (j <= i) return ldx(BDz, dt, (int64_t)i * T + (T - 1 - i + j));
+// T is the row stride of BD and n the length the shift is taken at (n == T unless the row is one of a ragged batch).
+__device__ __forceinline__ float bd_shift(const void* __restrict__ BDz, int dt, int T, int n, int i, int j) {
+    if (j <= i) return ldx(BDz, dt, (int64_t)i * T + (n - 1 - i + j));
     if (j == i + 1) return 0.f;
     return ldx(BDz, dt, (int64_t)(i + 1) * T + (j - i - 2));
 }
 
 // one wave per (z, i) row.  NV > 0: the row is read ONCE and kept in NV registers per lane
 // (T <= 64*NV); NV == 0: generic three-pass fallback for very long rows.
-template <int NV>
+// RAGGED (fp32, no dropout): row b of the padded batch has n = lens[b] frames and is computed as if it had been passed alone:
+// the keys are j < n (keymask is not read), the shift is taken at n, and the query rows i >= n are stored as 0 (probs @ V
+// must read zeros there).
+template <int NV, bool RAGGED>
 __global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(const void* __restrict__ ac,
                                                                  const void* __restrict__ bd, int s_dt,
                                                                  const uint8_t* __restrict__ keymask,
                                                                  void* __restrict__ probs, int p_dt, int H, int T,
                                                                  int64_t ac_bs, int64_t bd_bs, int64_t p_bs,
                                                                  float scale, int64_t nrows, void* __restrict__ pdrop,
-                                                                 unsigned int thr, float inv, unsigned int key) {
+                                                                 unsigned int thr, float inv, unsigned int key,
+                                                                 const int32_t* __restrict__ lens) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= nrows) return;
     const int64_t zz = row / T;
     const int i = (int)(row - zz * T);
     const int b = (int)(zz / H);
+    int n = T;
+    if constexpr (RAGGED) {
+        s_dt = p_dt = A3T_F32;
+        pdrop = nullptr;
+        n = ragged_len(lens, b, T);
+        if (i >= n) {      // (wave-uniform)
+            for (int j = lane; j < T; j += 64) ((float*)probs)[zz * p_bs + (int64_t)i * T + j] = 0.f;
+            return;
+        }
+    }
     const int64_t ao = zz * ac_bs + (int64_t)i * T;
     const void* bz = (s_dt == A3T_BF16) ? (const void*)((const unsigned short*)bd + zz * bd_bs)
                                         : (const void*)((const float*)bd + zz * bd_bs);
     const uint8_t* mk = keymask + (int64_t)b * T;
+    auto valid = [&](const int j) -> bool {
+        if constexpr (RAGGED) return j < n;
+        else return mk[j];
+    };
     const int64_t po = zz * p_bs + (int64_t)i * T;
     const float NEG = -3.4028235e38f;
     if (NV > 0) {
@@ -450,7 +498,7 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(const void* __r
         for (int q = 0; q < NV; ++q) {
             int j = lane + q * 64;
             v[q] = NEG;
-            if (j < T && mk[j]) v[q] = (ldx(ac, s_dt, ao + j) + bd_shift(bz, s_dt, T, i, j)) * scale;
+            if (j < T && valid(j)) v[q] = (ldx(ac, s_dt, ao + j) + bd_shift(bz, s_dt, T, n, i, j)) * scale;
             mx = fmaxf(mx, v[q]);
         }
         mx = wmax(mx);
@@ -476,8 +524,8 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(const void* __r
     float mx = NEG;
     int any = 0;
     for (int j = lane; j < T; j += 64)
-        if (mk[j]) {
-            mx = fmaxf(mx, (ldx(ac, s_dt, ao + j) + bd_shift(bz, s_dt, T, i, j)) * scale);
+        if (valid(j)) {
+            mx = fmaxf(mx, (ldx(ac, s_dt, ao + j) + bd_shift(bz, s_dt, T, n, i, j)) * scale);
             any = 1;
         }
     mx = wmax(mx);
@@ -491,11 +539,11 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(const void* __r
     }
     float s = 0.f;
     for (int j = lane; j < T; j += 64)
-        if (mk[j]) s += expf((ldx(ac, s_dt, ao + j) + bd_shift(bz, s_dt, T, i, j)) * scale - mx);
+        if (valid(j)) s += expf((ldx(ac, s_dt, ao + j) + bd_shift(bz, s_dt, T, n, i, j)) * scale - mx);
     s = wsum(s);
     const float inv_s = 1.f / s;
     for (int j = lane; j < T; j += 64) {
-        const float pj = mk[j] ? expf((ldx(ac, s_dt, ao + j) + bd_shift(bz, s_dt, T, i, j)) * scale - mx) * inv_s : 0.f;
+        const float pj = valid(j) ? expf((ldx(ac, s_dt, ao + j) + bd_shift(bz, s_dt, T, n, i, j)) * scale - mx) * inv_s : 0.f;
         stx(probs, p_dt, po + j, pj);
         if (pdrop) stx(pdrop, p_dt, po + j, rng_keep(key, (unsigned int)(po + j), thr) ? pj * inv : 0.f);
     }
@@ -617,6 +665,21 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_bf16_kernel(
     } while (0)
 static inline bool sm_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// one launcher for the plain entry point (lens == nullptr) and the ragged one (keymask == nullptr, no dropout)
+template <bool RAGGED>
+static int relpos_softmax_fwd_launch(const void* ac, const void* bd, int scores_dtype, const uint8_t* keymask, void* probs,
+                                     int probs_dtype, int H, int T, int64_t ac_bs, int64_t bd_bs, int64_t p_bs, float scale,
+                                     int64_t nrows, void* probs_drop, unsigned int thr, float dinv, uint32_t drop_key,
+                                     const int32_t* lens, hipStream_t stream) {
+#define CALL(NV)                                                                                                       \
+    hipLaunchKernelGGL((relpos_softmax_fwd_kernel<NV, RAGGED>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, stream, ac, \
+                       bd, scores_dtype, keymask, probs, probs_dtype, H, T, ac_bs, bd_bs, p_bs, scale, nrows, probs_drop,  \
+                       thr, dinv, drop_key, lens)
+    SM_DISPATCH(T, CALL);
+#undef CALL
+    return (int)hipGetLastError();
+}
+
 extern "C" int a3t_relpos_softmax_fwd(const void* ac, const void* bd, int scores_dtype, const uint8_t* keymask,
                                       void* probs, int probs_dtype, int B, int H, int T, int64_t ac_bs, int64_t bd_bs,
                                       int64_t p_bs, float scale, void* probs_drop, float drop_p, uint32_t drop_key,
@@ -637,13 +700,20 @@ extern "C" int a3t_relpos_softmax_fwd(const void* ac, const void* bd, int scores
 #undef CALLV
         return (int)hipGetLastError();
     }
-#define CALL(NV)                                                                                                 \
-    hipLaunchKernelGGL(relpos_softmax_fwd_kernel<NV>, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0,           \
-                       (hipStream_t)stream, ac, bd, scores_dtype, keymask, probs, probs_dtype, H, T, ac_bs, bd_bs, p_bs, \
-                       scale, nrows, probs_drop, thr, dinv, drop_key)
-    SM_DISPATCH(T, CALL);
-#undef CALL
-    return (int)hipGetLastError();
+    return relpos_softmax_fwd_launch<false>(ac, bd, scores_dtype, keymask, probs, probs_dtype, H, T, ac_bs, bd_bs, p_bs, scale,
+                                            nrows, probs_drop, thr, dinv, drop_key, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int a3t_relpos_softmax_fwd_ragged(const void* ac, const void* bd, int scores_dtype, const int32_t* lens,
+                                             void* probs, int probs_dtype, int B, int H, int T, int64_t ac_bs,
+                                             int64_t bd_bs, int64_t p_bs, float scale, void* stream) {
+    if (scores_dtype != A3T_F32 || probs_dtype != A3T_F32 || !lens || B <= 0 || H <= 0 || T <= 0) return A3T_EINVAL;
+    const int64_t tt = (int64_t)T * T;
+    if (ac_bs < tt || bd_bs < tt || p_bs < tt) return A3T_EINVAL;
+    const int64_t nrows = (int64_t)B * H * T;
+    if ((nrows + 3) / 4 > 0x7fffffff) return A3T_EINVAL;
+    return relpos_softmax_fwd_launch<true>(ac, bd, A3T_F32, nullptr, probs, A3T_F32, H, T, ac_bs, bd_bs, p_bs, scale, nrows,
+                                           nullptr, 0u, 0.f, 0u, lens, (hipStream_t)stream);
 }
 
 // ds = probs*(dprobs - sum_j dprobs*probs)*scale: written to ds (same dtype as dbd; may alias dprobs

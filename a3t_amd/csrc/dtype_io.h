@@ -1,5 +1,7 @@
 // dtype_io.h -- runtime-typed element access (fp32 | bf16 storage) for the HBM-bound kernels.
 // The dtype flag is wave-uniform, so the branch costs one scalar compare per access.
+// Also what else the row kernels of norm_reduce.hip and convmod_attn.hip share: the counter-based dropout RNG and ragged_len,
+// the clamped row length of a padded batch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,6 +50,13 @@ __device__ __forceinline__ void rng_keep4(unsigned int key, unsigned int i0, uns
     k[0] = (h0 & 0xffffu) >= t, k[1] = (h0 >> 16) >= t, k[2] = (h1 & 0xffffu) >= t, k[3] = (h1 >> 16) >= t;
 }
 __device__ __forceinline__ unsigned int rng_thr(float p) { return (unsigned int)((double)p * 4294967296.0); }
+
+// Length of row b of a padded [B][T] batch (the RAGGED instantiations of the row kernels): a length outside 0..T cannot push
+// an index out of the row.
+__device__ __forceinline__ int ragged_len(const int32_t* __restrict__ lens, int b, int T) {
+    const int n = lens[b];
+    return n < 0 ? 0 : (n > T ? T : n);
+}
 
 __device__ __forceinline__ float ldx(const void* p, int dt, int64_t i) {
     return dt == A3T_BF16 ? io_bf2f(((const unsigned short*)p)[i]) : ((const float*)p)[i];

@@ -18,17 +18,28 @@ __device__ __forceinline__ float wave_sum(float v) {
 // ------------------------------------------------------------------------------------------
 // LayerNorm: one wave64 per row, the row lives in V registers per lane (V = ceil(D/64), chosen at
 // launch so the d=384 rows of the Conformer use exactly 6), __shfl_xor butterflies for the stats.
+// RAGGED (fp32 y, forward only): the M = B * T rows are a padded batch whose row b has lens[b] frames; a row t >= lens[b] is
+// stored as 0 (what the k-tap convolution behind it must read there) without x being read, and mean / rstd may be null.
 // ------------------------------------------------------------------------------------------
 #define LN_MAXV 24  // D <= 1536
 
-template <int V>
+template <int V, bool RAGGED>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                      const float* __restrict__ b, void* __restrict__ y, int y_dt,
                                                      float* __restrict__ mean, float* __restrict__ rstd, int M,
-                                                     int D, float eps) {
+                                                     int D, float eps, const int32_t* __restrict__ lens, int T) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wv;
     if (row >= M) return;
+    if constexpr (RAGGED) {
+        y_dt = A3T_F32;
+        const int bb = row / T;
+        if (row - bb * T >= ragged_len(lens, bb, T)) {      // (wave-uniform)
+            for (int c = lane; c < D; c += 64) ((float*)y)[(int64_t)row * D + c] = 0.f;
+            if (lane == 0 && mean) mean[row] = 0.f, rstd[row] = 0.f;
+            return;
+        }
+    }
     const float* xr = x + (int64_t)row * D;
     float v[V];
     float s = 0.f;
@@ -53,7 +64,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
         int c = lane + i * 64;
         if (c < D) stx(y, y_dt, (int64_t)row * D + c, (v[i] - mu) * rs * g[c] + b[c]);
     }
-    if (lane == 0) {
+    if (lane == 0 && (!RAGGED || mean)) {
         mean[row] = mu;
         rstd[row] = rs;
     }
@@ -61,20 +72,27 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 
 // D % 128 == 0 fast path: half a wave (32 lanes) per row, NQ float4 per lane (D = 128*NQ): 16-byte loads, 8-byte
 // (bf16) / 16-byte stores, two rows in flight per wave.
-template <int NQ>
+template <int NQ, bool RAGGED>
 __global__ __launch_bounds__(256) void ln_fwd_vec_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                          const float* __restrict__ b, void* __restrict__ y, int y_dt,
                                                          float* __restrict__ mean, float* __restrict__ rstd, int M,
-                                                         int D, float eps) {
+                                                         int D, float eps, const int32_t* __restrict__ lens, int T) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, hl = lane & 31, half = lane >> 5;
     const int row = (blockIdx.x * 4 + wv) * 2 + half;
     const bool ok = row < M;
     const int64_t ro = (int64_t)(ok ? row : 0) * D;
+    bool live = true;      // RAGGED: the row lies in front of its batch row's length
+    if constexpr (RAGGED) {
+        y_dt = A3T_F32;
+        const int rr = ok ? row : 0, bb = rr / T;
+        live = rr - bb * T < ragged_len(lens, bb, T);
+    }
     float4 v[NQ];
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
-        v[i] = *(const float4*)(x + ro + (hl + 32 * i) * 4);
+        if constexpr (RAGGED) v[i] = live ? *(const float4*)(x + ro + (hl + 32 * i) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        else v[i] = *(const float4*)(x + ro + (hl + 32 * i) * 4);
         s += v[i].x + v[i].y + v[i].z + v[i].w;
     }
 #pragma unroll
@@ -93,6 +111,10 @@ __global__ __launch_bounds__(256) void ln_fwd_vec_kernel(const float* __restrict
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
         const int c = (hl + 32 * i) * 4;
+        if (!live) {
+            *(float4*)((float*)y + ro + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
         const float4 gg = *(const float4*)(g + c), bb = *(const float4*)(b + c);
         const float o0 = (v[i].x - mu) * rs * gg.x + bb.x, o1 = (v[i].y - mu) * rs * gg.y + bb.y;
         const float o2 = (v[i].z - mu) * rs * gg.z + bb.z, o3 = (v[i].w - mu) * rs * gg.w + bb.w;
@@ -104,9 +126,9 @@ __global__ __launch_bounds__(256) void ln_fwd_vec_kernel(const float* __restrict
             *(float4*)((float*)y + ro + c) = make_float4(o0, o1, o2, o3);
         }
     }
-    if (hl == 0) {
-        mean[row] = mu;
-        rstd[row] = rs;
+    if (hl == 0 && (!RAGGED || mean)) {
+        mean[row] = live ? mu : 0.f;
+        rstd[row] = live ? rs : 0.f;
     }
 }
 
@@ -294,14 +316,15 @@ __global__ __attribute__((amdgpu_num_vgpr(80))) __launch_bounds__(512) void ln_b
         else { CALL(LN_MAXV); }           \
     } while (0)
 
-extern "C" int a3t_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, int y_dtype,
-                                 float* mean, float* rstd, int M, int D, float eps, void* stream) {
-    if (D > 64 * LN_MAXV || M <= 0) return A3T_EINVAL;
+// one launcher for the plain entry point (lens == nullptr) and the ragged one
+template <bool RAGGED>
+static int ln_fwd_launch(const float* x, const float* gamma, const float* beta, void* y, int y_dtype, float* mean,
+                         float* rstd, int M, int D, float eps, const int32_t* lens, int T, hipStream_t stream) {
     if (D % 128 == 0 && D <= 512 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) && ((uintptr_t)gamma % 16 == 0) &&
         ((uintptr_t)beta % 16 == 0)) {
-#define VCALL(NQ)                                                                                                     \
-    hipLaunchKernelGGL(ln_fwd_vec_kernel<NQ>, dim3((M + 7) / 8), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, \
-                       y_dtype, mean, rstd, M, D, eps)
+#define VCALL(NQ)                                                                                                      \
+    hipLaunchKernelGGL((ln_fwd_vec_kernel<NQ, RAGGED>), dim3((M + 7) / 8), dim3(256), 0, stream, x, gamma, beta, y, y_dtype, \
+                       mean, rstd, M, D, eps, lens, T)
         if (D == 128) VCALL(1);
         else if (D == 256) VCALL(2);
         else if (D == 384) VCALL(3);
@@ -309,12 +332,26 @@ extern "C" int a3t_layernorm_fwd(const float* x, const float* gamma, const float
 #undef VCALL
         return (int)hipGetLastError();
     }
-#define CALL(V)                                                                                                  \
-    hipLaunchKernelGGL(ln_fwd_kernel<V>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, \
-                       y_dtype, mean, rstd, M, D, eps)
+#define CALL(V)                                                                                                          \
+    hipLaunchKernelGGL((ln_fwd_kernel<V, RAGGED>), dim3((M + 3) / 4), dim3(256), 0, stream, x, gamma, beta, y, y_dtype, mean, \
+                       rstd, M, D, eps, lens, T)
     LN_DISPATCH(D, CALL);
 #undef CALL
     return (int)hipGetLastError();
+}
+
+extern "C" int a3t_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, int y_dtype,
+                                 float* mean, float* rstd, int M, int D, float eps, void* stream) {
+    if (D > 64 * LN_MAXV || M <= 0) return A3T_EINVAL;
+    return ln_fwd_launch<false>(x, gamma, beta, y, y_dtype, mean, rstd, M, D, eps, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int a3t_layernorm_fwd_ragged(const float* x, const float* gamma, const float* beta, float* y, float* mean,
+                                        float* rstd, const int32_t* lens, int B, int T, int D, float eps, void* stream) {
+    if (B <= 0 || T <= 0 || D <= 0 || D > 64 * LN_MAXV || !lens || (mean == nullptr) != (rstd == nullptr) ||
+        (int64_t)B * T > 0x7fffffff)
+        return A3T_EINVAL;
+    return ln_fwd_launch<true>(x, gamma, beta, y, A3T_F32, mean, rstd, B * T, D, eps, lens, T, (hipStream_t)stream);
 }
 
 extern "C" int a3t_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float* gamma,

@@ -500,44 +500,13 @@ class FS2DurationModel:
         """ids: device int64 [T] (eos included); style: device [1][d] from style_embedding (a GST model needs it, another
         model refuses it), added to every encoder output row in front of the x-vector integration.  Returns device tensors
         (hs [T][d], logd [T], frames [T] int64) valid until the next call."""
-        c, p, ws = self.c, self.store.p, self.ws
-        T, d = int(ids.shape[0]), c.adim
+        c, T = self.c, int(ids.shape[0])
         if not 1 <= T <= c.max_len:
             raise ValueError(f"sequence length {T} outside 1..{c.max_len}")
         if spk_bias is not None and c.spk_embed_dim <= 0:
             raise ValueError("spk_bias given but the checkpoint has no x-vector projection")
         self._check_style(style, 1, None)
-        eng = self.eng
-        # Embedding * sqrt(d) (+ pe: legacy rel-pos only scales) -- the MLM prologue kernel with no speech frames
-        xs = ws.get("emb.xs", (T, d))
-        ops.embed_finish_fwd(None, p["temb"], self._seg0, ids, None, self._tpos0, xs, 1, 0, T, d, math.sqrt(d))
-        keymask = self._keys1[:T].view(1, T)
-        pos = eng.pe[:T]
-        x = xs
-        for i in range(c.enc_blocks):
-            x = eng.block_fwd(f"enc.{i}", x, pos, keymask, 1, T)
-        hs = eng._ln_fwd("enc.after", x, "enc.after", out_dtype=torch.float32)
-        if style is not None:
-            ops.gst_add_style(hs, style, 1, T)
-        if spk_bias is not None:
-            if c.spk_integration == "add":
-                ops.bias_act(hs, spk_bias, ACT_NONE)
-            else:
-                hc = ws.get("spk.hs", (T, d))
-                ops.linear_fwd(hs, p["spk.wh"], hc, bias=spk_bias.view(-1), compute=F32)
-                hs = hc
-        y, pad = hs, (c.dp_kernel - 1) // 2
-        for l in range(c.dp_layers):
-            z = ws.get(f"dp.{l}.z", (T, c.dp_chans))
-            ops.conv_fwd(y, p[f"dp.{l}.w"], z, T, pad, bias=p[f"dp.{l}.b"], act=ACT_RELU, compute=F32)
-            if l < c.dp_layers - 1:
-                y = eng._ln_fwd(f"dp.{l}.ln", z, f"dp.{l}.ln", out_dtype=torch.float32)
-        logd = ws.get("dp.logd", (T,))
-        frames = ws.get("dp.frames", (T,), torch.int64)
-        l = c.dp_layers - 1
-        ops.duration_head(z, p[f"dp.{l}.ln.g"], p[f"dp.{l}.ln.b"], p["dp.lin.w"], p["dp.lin.b"], logd, frames,
-                          eps=1e-12, offset=c.dp_offset)
-        return hs, logd, frames
+        return self._forward(ids, 1, T, None, spk_bias, style, None)
 
     def _check_style(self, style, B, rows):
         if not self.c.use_gst:
@@ -560,7 +529,7 @@ class FS2DurationModel:
         style: device [B][d] (row b for sequence b), [1][d] (one prompt for all), or any [S][d] with style_rows, device int32 [B]:
         sequence b takes style row style_rows[b].
         The number of launches does not depend on B."""
-        c, p, ws = self.c, self.store.p, self.ws
+        c = self.c
         if ids.dim() != 2 or ids.dtype != torch.int64 or not ids.is_contiguous():
             raise ValueError("ids must be a contiguous int64 [B][Tmax] tensor")
         B, T, d = int(ids.shape[0]), int(ids.shape[1]), c.adim
@@ -569,16 +538,24 @@ class FS2DurationModel:
         if spk_bias is not None and c.spk_embed_dim <= 0:
             raise ValueError("spk_bias given but the checkpoint has no x-vector projection")
         self._check_style(style, B, style_rows)
-        eng, M = self.eng, B * T
+        hs, logd, frames = self._forward(ids, B, T, lens, spk_bias, style, style_rows)
+        return hs.view(B, T, d), logd.view(B, T), frames.view(B, T)
+
+    def _forward(self, ids, B, T, lens, spk_bias, style, style_rows):
+        """The body of forward_ids (lens None, B = 1: no padded keys, the plain kernels) and of forward_ids_batch (lens: row b
+        as if alone at lens[b]).  Returns (hs [B*T][d], logd [B*T], frames [B*T])."""
+        c, p, ws = self.c, self.store.p, self.ws
+        eng, M, d = self.eng, B * T, c.adim
         if self._tpos0.numel() < M:
             self._tpos0 = torch.zeros(M, dtype=torch.int64, device=self.dev)
-        tpos = self._tpos0[:M]
+        # Embedding * sqrt(d) (+ pe: legacy rel-pos only scales) -- the MLM prologue kernel with no speech frames
         xs = ws.get("emb.xs", (M, d))
-        ops.embed_finish_fwd(None, p["temb"], self._seg0, ids, None, tpos, xs, B, 0, T, d, math.sqrt(d))
+        ops.embed_finish_fwd(None, p["temb"], self._seg0, ids, None, self._tpos0[:M], xs, B, 0, T, d, math.sqrt(d))
+        keymask = self._keys1[:T].view(1, T) if lens is None else None
         pos = eng.pe[:T]
         x = xs
         for i in range(c.enc_blocks):
-            x = eng.block_fwd(f"enc.{i}", x, pos, None, B, T, lens=lens)
+            x = eng.block_fwd(f"enc.{i}", x, pos, keymask, B, T, lens=lens)
         hs = eng._ln_fwd("enc.after", x, "enc.after", out_dtype=torch.float32)
         if style is not None:
             ops.gst_add_style(hs, style, B, T, rows=style_rows)
@@ -590,20 +567,20 @@ class FS2DurationModel:
                 ops.linear_fwd(hs, p["spk.wh"], hc, bias=spk_bias.view(-1), compute=F32)
                 hs = hc
         y, pad = hs, (c.dp_kernel - 1) // 2
-        if pad > 0:      # the predictor's first conv reads zeros behind every row's length
+        tail = lens if pad > 0 else None      # the predictor's convs read zeros behind every row's length
+        if tail is not None:
             ops.zero_tail(hs, lens, 1, B, T)
         for l in range(c.dp_layers):
             z = ws.get(f"dp.{l}.z", (M, c.dp_chans))
             ops.conv_fwd(y, p[f"dp.{l}.w"], z, T, pad, bias=p[f"dp.{l}.b"], act=ACT_RELU, compute=F32)
             if l < c.dp_layers - 1:
-                y = eng._ln_fwd(f"dp.{l}.ln", z, f"dp.{l}.ln", out_dtype=torch.float32,
-                                lens=lens if pad > 0 else None, T=T)
+                y = eng._ln_fwd(f"dp.{l}.ln", z, f"dp.{l}.ln", out_dtype=torch.float32, lens=tail, T=T)
         logd = ws.get("dp.logd", (M,))
         frames = ws.get("dp.frames", (M,), torch.int64)
         l = c.dp_layers - 1
         ops.duration_head(z, p[f"dp.{l}.ln.g"], p[f"dp.{l}.ln.b"], p["dp.lin.w"], p["dp.lin.b"], logd, frames,
                           eps=1e-12, offset=c.dp_offset)
-        return hs.view(B, T, d), logd.view(B, T), frames.view(B, T)
+        return hs, logd, frames
 
     def _chunks(self, lengths, max_score_elems):
         """Indices of `lengths` sorted by length and cut into consecutive chunks with B * H * Tmax^2 <= max_score_elems

@@ -625,19 +625,22 @@ class MLMEngine:
         y = self._ln_fwd(tag + ".ln", x, pre + ".ln")
         qkv = self._act(tag + ".qkv", (M, 3 * d))
         ops.linear_fwd(y, self.W(pre + ".wqkv"), qkv, bias=p[pre + ".bqkv"], compute=cmp)
-        if lens is not None:
-            return self._mha_fwd_ragged(tag, pre, x, qkv, pos, lens, B, T)
         # q + pos_bias_u / q + pos_bias_v (attention.py:190-194): the fused kernels add the biases as they load their query
         # fragments (bit for bit what a3t_add_pos_bias stores); the two [M][d] tensors only exist for the materialised forward and,
         # in the backward, as operands of the dK / d linear_pos products (made there, off the main stream)
-        fused = (self._fused_now or self._fused_train_now) and ops.attn_fused_supported(dk, T)
+        # lens (a ragged batch, _check_ragged: fp32, eval mode, forward only) takes the materialised forward with the key mask
+        # j < lens[b] and the legacy rel_shift taken at lens[b] (a3t_relpos_softmax_fwd_ragged).  P = linear_pos(pe[:T]) serves every
+        # row: its first n rows are pe[:n] projected.  Query rows behind a row's length come out as 0 from the softmax, so the
+        # probs @ V product and what follows stay finite there; no valid row reads them.
+        ragged = lens is not None
+        fused = (self._fused_now or self._fused_train_now) and ops.attn_fused_supported(dk, T) and not ragged
         pbias = (p[pre + ".u"], p[pre + ".v"])
         qu = qv = None
         if not fused:
             qu = self._act(tag + ".qu", (M, d))
             qv = self._act(tag + ".qv", (M, d))
             ops.add_pos_bias(qkv, pbias[0], pbias[1], qu, qv)
-        P = getattr(self, "_P_ahead", {}).get(tag)
+        P = None if ragged else getattr(self, "_P_ahead", {}).get(tag)
         if P is not None:       # projected ahead on the side stream (forward())
             ev = self._pos_ev.get(tag[:3]) if self._pos_ev else None
             if ev is not None:
@@ -646,7 +649,7 @@ class MLMEngine:
         else:
             P = self._act(tag + ".P", (T, d))
             ops.linear_fwd(pos, self.W(pre + ".wpos"), P, compute=cmp)
-        if self._fused_now and ops.attn_fused_supported(dk, T):
+        if self._fused_now and fused:
             adr = self._drop(c.attention_dropout_rate, tag + ".att")
             ctx = self._act(tag + ".ctx", (M, d))
             lse = self.ws.get(tag + ".lse", (B, H, T))
@@ -658,10 +661,11 @@ class MLMEngine:
             self.sv[tag] = None          # forward-only pass: nothing is kept for a backward
             self.sv[tag + ".fused"] = True
             return xo
+        # (the stale markers of an earlier fused pass under this tag go for a ragged pass too: sv[tag] is None after it anyway)
         self.sv.pop(tag + ".fused", None)
         self.sv.pop(tag + ".rs", None)
         self.sv.pop(tag + ".signed", None)
-        if self._fused_train_now and ops.attn_fused_supported(dk, T):
+        if self._fused_train_now and fused:
             # fused forward, materialised backward: probabilities stay un-normalised (1 / row sum in `rs`)
             adr = self._drop(c.attention_dropout_rate, tag + ".att")
             probs = self._act(tag + ".probs", (B, H, T, T))
@@ -693,10 +697,13 @@ class MLMEngine:
         ops.gemm(qv, P, bd, T, T, dk, d, 1, d, 1, T, batch=B * H, batch_inner=H, a_bs=(T * d, dk), b_bs=(0, dk),
                  c_bs=(H * T * T, T * T), compute=cmp)
         probs = self._act(tag + ".probs", (B, H, T, T))
-        adr = self._drop(c.attention_dropout_rate, tag + ".att")
+        adr = self._drop(c.attention_dropout_rate, tag + ".att")      # (None in eval mode, so with lens)
         pdrop = self._act(tag + ".pdrop", (B, H, T, T)) if adr else None
-        ops.relpos_softmax_fwd(ac, bd, keymask, probs, B, H, T, 1.0 / math.sqrt(dk), probs_drop=pdrop,
-                               drop=adr or (0.0, 0))
+        if ragged:
+            ops.relpos_softmax_fwd_ragged(ac, bd, lens, probs, B, H, T, 1.0 / math.sqrt(dk))
+        else:
+            ops.relpos_softmax_fwd(ac, bd, keymask, probs, B, H, T, 1.0 / math.sqrt(dk), probs_drop=pdrop,
+                                   drop=adr or (0.0, 0))
         ctx = self._act(tag + ".ctx", (M, d))
         # ctx[b,:,h,:] = dropout(probs[b,h]) V[b,h]
         ops.gemm(pdrop if adr else probs, vv, ctx, T, dk, T, T, 1, 1, 3 * d, d, batch=B * H, batch_inner=H,
@@ -704,39 +711,7 @@ class MLMEngine:
         xo = self.ws.get(tag + ".xo", (M, d))
         ops.linear_fwd(ctx, self.W(pre + ".wo"), xo, bias=p[pre + ".bo"], R=x, compute=cmp,
                        drop=self._drop(c.dropout_rate, tag + ".o"))
-        self.sv[tag] = (y, qkv, qu, qv, P, probs, ctx, pos, pdrop)
-        return xo
-
-    def _mha_fwd_ragged(self, tag, pre, x, qkv, pos, lens, B, T):
-        """The materialised forward over rows of their own length (fp32, forward only): the key mask is j < lens[b] and the
-        legacy rel_shift is taken at lens[b] (a3t_relpos_softmax_fwd_ragged).  P = linear_pos(pe[:T]) serves every row: its
-        first n rows are pe[:n] projected.  Query rows behind a row's length come out as 0 from the softmax, so the probs @ V
-        product and what follows stay finite there; no valid row reads them."""
-        p, c = self.store.p, self.c
-        d, H, dk = c.adim, c.heads, c.dk
-        M = B * T
-        cmp = self.cmp
-        qu = self._act(tag + ".qu", (M, d))
-        qv = self._act(tag + ".qv", (M, d))
-        ops.add_pos_bias(qkv, p[pre + ".u"], p[pre + ".v"], qu, qv)
-        P = self._act(tag + ".P", (T, d))
-        ops.linear_fwd(pos, self.W(pre + ".wpos"), P, compute=cmp)
-        ac = self.ws.get("tmp.ac", (B, H, T, T))
-        bd = self.ws.get("tmp.bd", (B, H, T, T))
-        kk = qkv.view(-1)[d:]
-        vv = qkv.view(-1)[2 * d:]
-        ops.gemm(qu, kk, ac, T, T, dk, d, 1, 3 * d, 1, T, batch=B * H, batch_inner=H, a_bs=(T * d, dk),
-                 b_bs=(T * 3 * d, dk), c_bs=(H * T * T, T * T), compute=cmp)
-        ops.gemm(qv, P, bd, T, T, dk, d, 1, d, 1, T, batch=B * H, batch_inner=H, a_bs=(T * d, dk), b_bs=(0, dk),
-                 c_bs=(H * T * T, T * T), compute=cmp)
-        probs = self._act(tag + ".probs", (B, H, T, T))
-        ops.relpos_softmax_fwd_ragged(ac, bd, lens, probs, B, H, T, 1.0 / math.sqrt(dk))
-        ctx = self._act(tag + ".ctx", (M, d))
-        ops.gemm(probs, vv, ctx, T, dk, T, T, 1, 1, 3 * d, d, batch=B * H, batch_inner=H,
-                 a_bs=(H * T * T, T * T), b_bs=(T * 3 * d, dk), c_bs=(T * d, dk), compute=cmp)
-        xo = self.ws.get(tag + ".xo", (M, d))
-        ops.linear_fwd(ctx, self.W(pre + ".wo"), xo, bias=p[pre + ".bo"], R=x, compute=cmp)
-        self.sv[tag] = None          # forward only: nothing is kept for a backward
+        self.sv[tag] = None if ragged else (y, qkv, qu, qv, P, probs, ctx, pos, pdrop)      # ragged is forward only
         return xo
 
     def _mha_bwd(self, tag, pre, g, B, T, nb=None, nxt=None):

@@ -384,8 +384,9 @@ int a3t_replicate_pad_ragged(const float* x, float* y, const int32_t* lens, int6
 int a3t_pwg_upsample_ragged(const float* c, const float* w, float* out, const int32_t* lens, int mul, int64_t B,
                             int64_t Tin, int C, int scale, void* stream);
 int a3t_zero_tail(float* x, const int32_t* lens, int mul, int64_t B, int64_t T, int C, void* stream);
-/* Length-aware twins of three row kernels for the batched duration model (csrc/ragged_rows.hip): fp32, forward only, padded
- * [B][T] rows with lens [B] int32 on the device, n = lens[b] (clamped to 0..T); row b gets what it would get alone at length n.
+/* Length-aware forms of three row kernels for the batched duration model (the RAGGED instantiations in csrc/norm_reduce.hip and
+ * csrc/convmod_attn.hip): fp32, forward only, padded [B][T] rows with lens [B] int32 on the device, n = lens[b] (clamped to
+ * 0..T); row b gets what it would get alone at length n.
  * a3t_layernorm_fwd_ragged: a3t_layernorm_fwd over x [B*T][D] (same arithmetic) whose rows t >= n are stored as 0 -- what a
  *   k-tap convolution behind it has to read there; mean / rstd [B*T] optional (both or neither; 0 for the rows behind n).
  * a3t_glu_dwconv_fwd_ragged: a3t_glu_dwconv_fwd (g [B*Tseq][2C] -> glu, z [B*Tseq][C]) whose taps read 0 for t >= n and across

@@ -1,4 +1,5 @@
-"""The batched duration model on the MI355X: the length-aware row kernels (csrc/ragged_rows.hip), the engine's ragged block
+"""The batched duration model on the MI355X: the length-aware row kernels (the RAGGED instantiations in
+csrc/norm_reduce.hip and csrc/convmod_attn.hip), the engine's ragged block
 forward and FS2DurationModel.forward_ids_batch / predict_frames_batch / duration_fn(...).batch against the reference's own
 outputs in tests/golden/fs2_duration.{npz,json} and the CPU restatement tests/fs2_ragged_ref.py."""
 import json
@@ -72,6 +73,20 @@ def test_ragged_softmax_of_a_full_row_is_the_plain_kernel():
     assert torch.equal(a, b)
 
 
+def test_ragged_softmax_of_a_full_long_row_is_the_plain_kernel():
+    """The same on the three-pass path of very long rows (T > 2048, NV == 0)."""
+    from a3t_amd import ops
+    B, H, T = 1, 1, 2100
+    g = torch.Generator().manual_seed(4)
+    ac = (torch.randn(B, H, T, T, generator=g) * 3.0).to(DEV)
+    bd = (torch.randn(B, H, T, T, generator=g) * 3.0).to(DEV)
+    a, b = torch.empty_like(ac), torch.empty_like(ac)
+    ops.relpos_softmax_fwd(ac, bd, torch.ones(B, T, dtype=torch.uint8, device=DEV), a, B, H, T, 0.125)
+    ops.relpos_softmax_fwd_ragged(ac, bd, _lens([T]), b, B, H, T, 0.125)
+    torch.cuda.synchronize()
+    assert torch.equal(a, b)
+
+
 def test_ragged_softmax_refuses_bf16():
     from a3t_amd import _lib, ops
     B, H, T = 1, 1, 16
@@ -109,6 +124,26 @@ def test_ragged_glu_dwconv_against_torch(K, C):
             assert torch.all(err <= 2e-5 + 1e-4 * want.abs()), (b, n, err.max().item())
 
 
+@pytest.mark.parametrize("C", [384, 80])
+@pytest.mark.parametrize("K", [5, 7])
+def test_ragged_glu_dwconv_at_full_length_is_the_plain_kernel(K, C):
+    """lens[b] = T: bit for bit a3t_glu_dwconv_fwd.  T = 70 is one whole 64-row tile and a partial one, C a whole and a
+    partial 64-channel block, K the generic tap loop (5) and the register-blocked K == KT path (7)."""
+    from a3t_amd import ops
+    B, T = 2, 70
+    g = torch.Generator().manual_seed(K * 1000 + C + 1)
+    x = torch.randn(B * T, 2 * C, generator=g).to(DEV)
+    w = (torch.randn(C, K, generator=g) / K ** 0.5).to(DEV)
+    bias = torch.randn(C, generator=g).to(DEV)
+    glu0, z0 = torch.empty(B * T, C, device=DEV), torch.empty(B * T, C, device=DEV)
+    glu1, z1 = torch.full_like(glu0, float("nan")), torch.full_like(z0, float("nan"))
+    ops.glu_dwconv_fwd(x, w, bias, glu0, z0, T)
+    ops.glu_dwconv_fwd_ragged(x, w, bias, glu1, z1, _lens([T, T]), B, T)
+    torch.cuda.synchronize()
+    assert torch.equal(glu0, glu1)
+    assert torch.equal(z0, z1)
+
+
 @pytest.mark.parametrize("D", [384, 256, 100, 640])
 def test_ragged_layernorm(D):
     """Valid rows against fp64 (atol 2e-5, rtol 1e-5) and bit for bit the plain kernel's; exact zeros behind a length."""
@@ -136,6 +171,35 @@ def test_ragged_layernorm(D):
         err = (got[b, :n].double() - want[b, :n]).abs()
         assert torch.all(err <= 2e-5 + 1e-5 * want[b, :n].abs()), (b, n, err.max().item())
         assert torch.equal(got[b, :n], plain[b, :n])
+
+
+@pytest.mark.parametrize("D", [384, 256, 100, 640])
+def test_ragged_layernorm_does_not_read_behind_a_length(D):
+    """x is NaN behind every row's length: exact zeros there, finite valid rows, and the bits that finite padding gives."""
+    from a3t_amd import ops
+    T, lens = 37, [37, 1, 20, 36]
+    B = len(lens)
+    g = torch.Generator().manual_seed(D)
+    x = torch.randn(B, T, D, generator=g) * 2.0 + 0.5
+    gd = (1.0 + 0.2 * torch.rand(D, generator=g)).to(DEV)
+    bd = (0.1 * torch.randn(D, generator=g)).to(DEV)
+    xn = x.clone()
+    for b, n in enumerate(lens):
+        xn[b, n:] = float("nan")
+    out = []
+    for src in (x, xn):
+        y = torch.full((B * T, D), float("nan"), device=DEV)
+        mean, rstd = torch.full((B * T,), float("nan"), device=DEV), torch.full((B * T,), float("nan"), device=DEV)
+        ops.layernorm_fwd_ragged(src.view(B * T, D).to(DEV), gd, bd, y, mean, rstd, _lens(lens), B, T, 1e-12)
+        out.append((y.view(B, T, D), mean.view(B, T), rstd.view(B, T)))
+    torch.cuda.synchronize()
+    for fin, nan in zip(*out):
+        assert torch.isfinite(nan).all()
+        assert torch.equal(fin, nan)
+    y = out[1][0]
+    for b, n in enumerate(lens):
+        assert torch.all(y[b, n:] == 0), (b, n)
+        assert torch.all(out[1][1][b, n:] == 0) and torch.all(out[1][2][b, n:] == 0), (b, n)
 
 
 # ---------------------------------------------------------------------------------------------------------- the engine
