@@ -57,7 +57,8 @@ def build(force=False, verbose=True):
         src = os.path.join(CSRC, s)
         obj = os.path.join(LIBDIR, s.replace(".hip", ".o"))
         objs.append(obj)
-        if force or _stale(obj, [src, hdr, os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "dtype_io.h")]):
+        if force or _stale(obj, [src, hdr, os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "dtype_io.h"),
+                                os.path.join(CSRC, "device_cus.h")]):
             jobs.append([_hipcc(), *FLAGS, "-c", src, "-o", obj] + (RES_FLAG if s in RES_SOURCES else []))
 
     def run(cmd):

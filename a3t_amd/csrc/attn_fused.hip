@@ -32,6 +32,7 @@
 #include <type_traits>
 #include "../../include/a3t_hip.h"
 #include "dtype_io.h"
+#include "device_cus.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -1445,17 +1446,6 @@ static float* attn_split_ws(size_t floats) {
     }
     return ws[dev];
 }
-static int attn_cus() {
-    static int n[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!n[dev]) {
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-        n[dev] = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-    }
-    return n[dev];
-}
 // A3T_ATTN_SPLIT=0 / a3t_attn_split_mode(0): no key-split of the tail blocks
 static int g_attn_split = -1;
 static int attn_split_on() {
@@ -1490,7 +1480,7 @@ static int launch_fwd16(const AttnArgs& a, hipStream_t s) {
         // empty (configs[1]: 576 blocks = 2.25 rounds on 256 CUs -> the time of 3).  The blocks of a last round that fills at most
         // half the chip go to the END of the grid, each split into 2..4 key ranges (one short round instead of a full one); the parts
         // share the block's reference maximum (every part evaluates the first valid key tile), so their un-normalised sums add.
-        const int cus = attn_cus();
+        const int cus = device_cus();
         const unsigned nfull = (grid / (unsigned)cus) * (unsigned)cus, ntail = grid - nfull;
         int nparts = ntail ? (int)((unsigned)cus / ntail) : 1;
         if (nparts > 4) nparts = 4;
@@ -1570,7 +1560,7 @@ extern "C" int a3t_attn_bwd_ds(const void* dctx, const void* ctx, const void* v,
     constexpr int KT = 5;
     const int NS = (T + 31) / 32;
     const int64_t ntasks = (int64_t)B * H * ((T + 127) / 128) * ((NS + KT - 1) / KT);
-    int64_t grid = (int64_t)attn_cus() * 2;
+    int64_t grid = (int64_t)device_cus() * 2;
     if (grid > ntasks) grid = ntasks;
     hipStream_t s = (hipStream_t)stream;
 #define A3T_DS2(NDB, DR, WD)                                                                                                         \

@@ -422,20 +422,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GP p) {
 }
 
 // =============================================================================================
-// host: what the GEMM files share (CU count, switches), the plan (route table) and the launch
+// host: what the GEMM files share (switches), the plan (route table) and the launch
 // =============================================================================================
-int gemm_cus() {          // per device (a process may drive several GPUs)
-    static int n[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!n[dev]) {
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-        n[dev] = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-    }
-    return n[dev];
-}
-
 // Kernel-selection switches, read from the environment on first use.  8P / PN / TT / 8P_TN / 8P_TN3: 0 never, 1 whenever legal,
 // 2 (default) the kernel's cost model (PN 3: the cost model for N = 384 only).  STAGES: LDS stages of the 128-row kernel, 1 / 2
 // forced (unset: by grid size).  WN3: its 192-column tiles, 0 never, 2 always (unset: where they waste fewer padded columns).

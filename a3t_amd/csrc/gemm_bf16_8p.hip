@@ -1150,7 +1150,7 @@ extern "C" int64_t a3t_gemm_keep_bytes(int M, int N) { return (int64_t)((M + 255
 // K splits of a token-reduction grid of `tiles` output tiles over nkt 64-wide K-tiles: fill the chip, >= 16 K-tiles per workgroup.
 // folds: the splits that get K-tiles as the kernels deal them out (an even number each; later splits write nothing) = the fold's splitk.
 static void g8_split_k(long tiles, int nkt, int& splits, int& folds) {
-    splits = (int)(gemm_cus() / tiles);
+    splits = (int)(device_cus() / tiles);
     if (splits < 1) splits = 1;
     if (splits > nkt / 16) splits = nkt / 16 > 0 ? nkt / 16 : 1;
     int per = (nkt + splits - 1) / splits;
@@ -1179,7 +1179,7 @@ bool g8_plan(const GP& p, int batch, int ly, GemmPlan* pl) {
     if (a_bytes >= (1ll << 31) || b_bytes >= (1ll << 31) || (int64_t)p.M * p.c_rs >= (1ll << 32)) return false;
     if (keep && (p.N % 256 != 0)) return false;
     const long tm = (p.M + 255) / 256, tn = (p.N + 255) / 256, tiles = tm * tn;
-    const int cus = gemm_cus();
+    const int cus = device_cus();
     if (mode == 2) {
         // Cost model fitted on MI355X (round 3: profiles/r03_g8_check.txt, r03_g8_c4_shapes.txt): one 128-KiB workgroup per CU runs its K loop
         // at ~1.65 us per 64-wide K-tile (1.3 PFLOP/s) but nothing overlaps a tile's fixed costs -- pipeline refill and

@@ -364,7 +364,7 @@ bool pn_plan(const GP& p, int batch, int ly, GemmPlan* pl) {
     const int64_t a_bytes = ((int64_t)p.M * p.a_rs) * 2, b_bytes = ((int64_t)p.N * p.b_rs) * 2;
     if (a_bytes >= (1ll << 31) || b_bytes >= (1ll << 31) || (int64_t)p.M * p.c_rs >= (1ll << 32)) return false;
     if (mode == 3 && p.N != PN_COLS) return false;
-    const int panels = (p.M + PN_ROWS - 1) / PN_ROWS, cus = gemm_cus();
+    const int panels = (p.M + PN_ROWS - 1) / PN_ROWS, cus = device_cus();
     if (mode >= 2) {
         // Cost model fitted on MI355X (tools/probes/gemm_pn.hip, profiles/r03_pn_check.txt): a tile (panel x 384-column chunk) costs ~1.55 us per
         // 64-wide K-tile plus ~8 us of pipeline fill and epilogue (dropout hashes and an fp32 residual add ~3 more; the later

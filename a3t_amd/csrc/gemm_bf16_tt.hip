@@ -308,7 +308,7 @@ static void launch_tt(const GP& pv, int TR, int grid, hipStream_t stream) {
 // elements) -> 4 tiles of 288 rows = 256 workgroups = one round; configs[3] (M = 1800) -> 8 tiles of 256 rows = two full rounds
 // (6 tiles of 320 would be 1.5 rounds for the price of two).  A last tile with a few rows is cheap (its A pieces are zeros).
 static bool tt_tiling(int M, int N, int K, int batch, int mode, int& tiles, int& TR) {
-    const int cus = gemm_cus();
+    const int cus = device_cus();
     tiles = 0, TR = 0;
     long best = 0;
     for (int t = (M + TT_MAX_ROWS - 1) / TT_MAX_ROWS, n = 0; n < 6; ++t, ++n) {

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include "../../include/a3t_hip.h"
 #include "dtype_io.h"
+#include "device_cus.h"
 
 // Introspection for bench.py / profilers: a3t_gemm records the name (as rocprofv3 prints it) of the kernel variant
 // its dispatcher picked for the calling thread's last launch; read back with a3t_gemm_last_kernel().
@@ -237,7 +238,6 @@ struct GemmPlan {
     char name[96];                            // as a3t_gemm_last_kernel reports it
 };
 
-int gemm_cus();                      // compute units of the current device (256 without one), cached per device
 // kernel-selection switches A3T_GEMM_8P, _PN, _TT, _8P_TN, _8P_TN3, _STAGES, _WN3 (gemm.hip: meanings, defaults)
 enum GemmSwitch { SW_8P, SW_PN, SW_TT, SW_8P_TN, SW_8P_TN3, SW_STAGES, SW_WN3 };
 int gemm_switch(int s);

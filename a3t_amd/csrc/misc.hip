@@ -540,61 +540,23 @@ extern "C" int a3t_pwg_res_skip(const float* o, float* x, float* skips, int64_t 
     hipLaunchKernelGGL(pwg_res_skip_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, o, x, skips, T, R, S);
     return (int)hipGetLastError();
 }
+// The padded [B][Tmax] layout of a batch.  RAGGED: row b is valid for lens[b] * mul rows and is computed exactly as if it had been
+// passed alone; nothing behind a row's length is read into a valid output.
 // out[b][t][c] = sum_j w[j] * c_stretched[b][t + j - scale][c], c_stretched[b][u] = c[b][u / scale], zero outside the utterance
+// (RAGGED: outside [0, lens[b] * mul * scale), and out is zero there)
+template <bool RAGGED>
 __global__ void pwg_upsample_kernel(const float* __restrict__ c, const float* __restrict__ w, float* __restrict__ out,
-                                    int64_t B, int64_t Tin, int C, int scale) {
+                                    const int32_t* __restrict__ lens, int mul, int64_t B, int64_t Tin, int C, int scale) {
     const int64_t Tout = Tin * scale;
     const int64_t n = B * Tout * C;
     GRID_STRIDE(i, n) {
         const int64_t ta = i / C;
         const int ch = (int)(i - ta * C);
         const int64_t b = ta / Tout, t = ta - b * Tout;
+        const int64_t Lout = RAGGED ? (int64_t)lens[b] * mul * scale : Tout;
         const float* cb = c + b * Tin * C;
         float acc = 0.f;
-        for (int j = 0; j <= 2 * scale; ++j) {
-            int64_t u = t + j - scale;
-            if (u >= 0 && u < Tout) acc += w[j] * cb[(u / scale) * C + ch];
-        }
-        out[i] = acc;
-    }
-}
-extern "C" int a3t_pwg_upsample(const float* c, const float* w, float* out, int64_t B, int64_t Tin, int C, int scale,
-                                void* stream) {
-    int64_t n = B * Tin * scale * C;
-    hipLaunchKernelGGL(pwg_upsample_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, c, w, out, B, Tin, C,
-                       scale);
-    return (int)hipGetLastError();
-}
-__global__ void replicate_pad_kernel(const float* x, float* y, int64_t B, int64_t T, int C, int pad) {
-    const int64_t Tp = T + 2 * pad, n = B * Tp * C;
-    GRID_STRIDE(i, n) {
-        const int64_t ta = i / C;
-        const int c = (int)(i - ta * C);
-        const int64_t b = ta / Tp;
-        int64_t t = ta - b * Tp - pad;
-        t = t < 0 ? 0 : (t >= T ? T - 1 : t);
-        y[i] = x[(b * T + t) * C + c];
-    }
-}
-extern "C" int a3t_replicate_pad(const float* x, float* y, int64_t B, int64_t T, int C, int pad, void* stream) {
-    int64_t n = B * (T + 2 * pad) * C;
-    hipLaunchKernelGGL(replicate_pad_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, x, y, B, T, C, pad);
-    return (int)hipGetLastError();
-}
-// ---- ragged twins: the padded [B][Tmax] layout stays, row b is valid for lens[b] * mul rows and is computed exactly as if it
-// had been passed alone; nothing behind a row's length is read into a valid output.
-__global__ void pwg_upsample_ragged_kernel(const float* __restrict__ c, const float* __restrict__ w, float* __restrict__ out,
-                                           const int32_t* __restrict__ lens, int mul, int64_t B, int64_t Tin, int C, int scale) {
-    const int64_t Tout = Tin * scale;
-    const int64_t n = B * Tout * C;
-    GRID_STRIDE(i, n) {
-        const int64_t ta = i / C;
-        const int ch = (int)(i - ta * C);
-        const int64_t b = ta / Tout, t = ta - b * Tout;
-        const int64_t Lout = (int64_t)lens[b] * mul * scale;      // the stretched signal is zero outside [0, Lout)
-        const float* cb = c + b * Tin * C;
-        float acc = 0.f;
-        if (t < Lout)
+        if (!RAGGED || t < Lout)
             for (int j = 0; j <= 2 * scale; ++j) {
                 int64_t u = t + j - scale;
                 if (u >= 0 && u < Lout) acc += w[j] * cb[(u / scale) * C + ch];
@@ -602,34 +564,52 @@ __global__ void pwg_upsample_ragged_kernel(const float* __restrict__ c, const fl
         out[i] = acc;
     }
 }
-extern "C" int a3t_pwg_upsample_ragged(const float* c, const float* w, float* out, const int32_t* lens, int mul, int64_t B,
-                                       int64_t Tin, int C, int scale, void* stream) {
+template <bool RAGGED>
+static int pwg_upsample(const float* c, const float* w, float* out, const int32_t* lens, int mul, int64_t B, int64_t Tin, int C,
+                        int scale, void* stream) {
     if (B <= 0 || Tin <= 0 || C <= 0 || scale <= 0 || mul <= 0) return A3T_EINVAL;
     int64_t n = B * Tin * scale * C;
-    hipLaunchKernelGGL(pwg_upsample_ragged_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, c, w, out, lens, mul,
+    hipLaunchKernelGGL(pwg_upsample_kernel<RAGGED>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, c, w, out, lens, mul,
                        B, Tin, C, scale);
     return (int)hipGetLastError();
 }
-__global__ void replicate_pad_ragged_kernel(const float* x, float* y, const int32_t* __restrict__ lens, int64_t B, int64_t T,
-                                            int C, int pad) {
+extern "C" int a3t_pwg_upsample(const float* c, const float* w, float* out, int64_t B, int64_t Tin, int C, int scale,
+                                void* stream) {
+    return pwg_upsample<false>(c, w, out, nullptr, 1, B, Tin, C, scale, stream);
+}
+extern "C" int a3t_pwg_upsample_ragged(const float* c, const float* w, float* out, const int32_t* lens, int mul, int64_t B,
+                                       int64_t Tin, int C, int scale, void* stream) {
+    return pwg_upsample<true>(c, w, out, lens, mul, B, Tin, C, scale, stream);
+}
+// y[b][u] = x[b][clamp(u - pad, 0, T - 1)] (RAGGED: clamped to the row's own [0, lens[b] - 1], zero for an empty row)
+template <bool RAGGED>
+__global__ void replicate_pad_kernel(const float* x, float* y, const int32_t* __restrict__ lens, int64_t B, int64_t T, int C,
+                                     int pad) {
     const int64_t Tp = T + 2 * pad, n = B * Tp * C;
     GRID_STRIDE(i, n) {
         const int64_t ta = i / C;
         const int c = (int)(i - ta * C);
         const int64_t b = ta / Tp;
-        const int64_t L = lens[b];
+        const int64_t L = RAGGED ? (int64_t)lens[b] : T;
         int64_t t = ta - b * Tp - pad;
         t = t < 0 ? 0 : (t >= L ? L - 1 : t);
-        y[i] = L > 0 ? x[(b * T + t) * C + c] : 0.f;
+        y[i] = !RAGGED || L > 0 ? x[(b * T + t) * C + c] : 0.f;
     }
+}
+template <bool RAGGED>
+static int replicate_pad(const float* x, float* y, const int32_t* lens, int64_t B, int64_t T, int C, int pad, void* stream) {
+    if (B <= 0 || T <= 0 || C <= 0 || pad < 0) return A3T_EINVAL;
+    int64_t n = B * (T + 2 * pad) * C;
+    hipLaunchKernelGGL(replicate_pad_kernel<RAGGED>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, x, y, lens, B, T, C,
+                       pad);
+    return (int)hipGetLastError();
+}
+extern "C" int a3t_replicate_pad(const float* x, float* y, int64_t B, int64_t T, int C, int pad, void* stream) {
+    return replicate_pad<false>(x, y, nullptr, B, T, C, pad, stream);
 }
 extern "C" int a3t_replicate_pad_ragged(const float* x, float* y, const int32_t* lens, int64_t B, int64_t T, int C, int pad,
                                         void* stream) {
-    if (B <= 0 || T <= 0 || C <= 0 || pad < 0) return A3T_EINVAL;
-    int64_t n = B * (T + 2 * pad) * C;
-    hipLaunchKernelGGL(replicate_pad_ragged_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, x, y, lens, B, T, C,
-                       pad);
-    return (int)hipGetLastError();
+    return replicate_pad<true>(x, y, lens, B, T, C, pad, stream);
 }
 // x[b][t][:] = 0 for t >= lens[b] * mul (stores only: whatever the tail held, NaN included, is gone)
 __global__ void zero_tail_kernel(float* __restrict__ x, const int32_t* __restrict__ lens, int mul, int64_t B, int64_t T, int C) {

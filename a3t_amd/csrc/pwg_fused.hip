@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/a3t_hip.h"
+#include "device_cus.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -41,15 +42,15 @@ __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
     // epilogue / LDS latency is covered by its partner's MFMAs (the weights leave room for ONE workgroup per CU only)
     // stage 0: K-chunks of 8 (weights 136 KiB + 16 KiB activation double buffer = 152 KiB of LDS; chunks of 16 with the
     // last weight rows left in global memory measured 13 % slower); stage 1 (32 KiB of weights): chunks of 16.
-    constexpr int K = STAGE == 0 ? 272 : 64, KL = K, BK = STAGE == 0 ? 8 : 16, NCH = K / BK, TILE = 256, LD = TILE + 4;
+    constexpr int K = STAGE == 0 ? 272 : 64, BK = STAGE == 0 ? 8 : 16, NCH = K / BK, TILE = 256, LD = TILE + 4;
     constexpr int NF = BK / 8;           // float4 per thread and chunk
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* Wt = lds;                                              // [KL][128]
-    float(*As)[BK][LD] = (float(*)[BK][LD])(lds + KL * 128);      // [2][BK][LD]
+    float* Wt = lds;                                              // [K][128]
+    float(*As)[BK][LD] = (float(*)[BK][LD])(lds + K * 128);       // [2][BK][LD]
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = (w >> 1) * 64, wn = (w & 1) * 64, lr = lane & 31, lk = lane >> 5;
-    for (int i = tid; i < KL * 128 / 4; i += 512) ((float4*)Wt)[i] = ((const float4*)a.wt)[i];
+    for (int i = tid; i < K * 128 / 4; i += 512) ((float4*)Wt)[i] = ((const float4*)a.wt)[i];
 
     const int ntiles = RAGGED ? a.ntiles : a.B * a.tiles_t;
     // tile index -> row, first sample and the row's valid length.  RAGGED: the list entry is fetched when the tile index
@@ -149,14 +150,8 @@ __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
         for (int kk = 0; kk < BK / 2; ++kk) {
             const float a0 = As[buf][kk * 2 + lk][wm + lr], a1 = As[buf][kk * 2 + lk][wm + 32 + lr];
             const int kg = kc * BK + kk * 2 + lk;
-            float b0, b1;
-            if (K > KL && kc * BK >= KL) {      // (uniform) weight rows that did not fit the LDS: L1 / L2 hits
-                const float* wr = a.wt + kg * 128 + wn + lr;
-                b0 = wr[0], b1 = wr[32];
-            } else {
-                const float* wr = Wt + kg * 128 + wn + lr;
-                b0 = wr[0], b1 = wr[32];
-            }
+            const float* wr = Wt + kg * 128 + wn + lr;
+            const float b0 = wr[0], b1 = wr[32];
             acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
             acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
             acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
@@ -201,17 +196,6 @@ __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
     }
 }
 
-static int pwg_blocks() {
-    static int n = 0;
-    if (!n) {
-        hipDeviceProp_t prop;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-        n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return n;
-}
-
 template <bool RAGGED>
 static int pwg_launch(PwgArgs a, const float* wt0, const float* b0, const float* wt1, const float* b1, int ntiles, void* stream) {
     constexpr int lds0 = (272 * 128 + 2 * 8 * 260) * 4, lds1 = (64 * 128 + 2 * 16 * 260) * 4;
@@ -221,7 +205,7 @@ static int pwg_launch(PwgArgs a, const float* wt0, const float* b0, const float*
         (void)hipFuncSetAttribute((const void*)pwg_stage_kernel<1, RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1);
         attr = true;
     }
-    const int cus = pwg_blocks();
+    const int cus = device_cus();
     a.wt = wt0, a.bias = b0;
     int g0 = ntiles < cus ? ntiles : cus;                 // stage 0: 153 KiB of LDS -> one persistent workgroup per CU
     hipLaunchKernelGGL((pwg_stage_kernel<0, RAGGED>), dim3(g0), dim3(512), lds0, (hipStream_t)stream, a);
@@ -231,17 +215,24 @@ static int pwg_launch(PwgArgs a, const float* wt0, const float* b0, const float*
     return (int)hipGetLastError();
 }
 
+// Both entry points: tiles == nullptr is the dense form, all B rows Tw samples long.
+static int pwg_block(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1, float* g,
+                     float* skips, const int32_t* tiles, int ntiles, int B, int Tw, int dil, void* stream) {
+    if (B <= 0 || Tw <= 0 || dil <= 0 || ntiles < 0 || ((uintptr_t)tiles & 15)) return A3T_EINVAL;
+    PwgArgs a;
+    a.x_in = x, a.cu = cu, a.gin = g, a.g = g, a.x_out = x, a.skips = skips;
+    a.B = B, a.Tw = Tw, a.dil = dil, a.tiles_t = (Tw + 255) / 256;
+    a.tiles = (const int4*)tiles, a.ntiles = ntiles;
+    if (tiles) return ntiles ? pwg_launch<true>(a, wt0, b0, wt1, b1, ntiles, stream) : 0;
+    return pwg_launch<false>(a, wt0, b0, wt1, b1, B * a.tiles_t, stream);
+}
+
 // One residual block, in place on x and skips.  wt0: [272][128] (k = tap*64 + ch | 192 + aux ch; column n' = permuted
 // gate channel: see a3t_amd/vocoder.py), b0: [128] permuted the same way; wt1: [64][128] = conv1x1_out.weight^T, b1: [128].
 // g: scratch [B*Tw][64].
 extern "C" int a3t_pwg_block(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1,
                              const float* b1, float* g, float* skips, int B, int Tw, int dil, void* stream) {
-    if (B <= 0 || Tw <= 0 || dil <= 0) return A3T_EINVAL;
-    PwgArgs a;
-    a.x_in = x, a.cu = cu, a.gin = g, a.g = g, a.x_out = x, a.skips = skips;
-    a.B = B, a.Tw = Tw, a.dil = dil, a.tiles_t = (Tw + 255) / 256;
-    a.tiles = nullptr, a.ntiles = 0;
-    return pwg_launch<false>(a, wt0, b0, wt1, b1, B * a.tiles_t, stream);
+    return pwg_block(x, cu, wt0, b0, wt1, b1, g, skips, nullptr, 0, B, Tw, dil, stream);
 }
 
 // The same block over rows of different length in the padded [B][Tw] layout.  tiles: device int32 [ntiles][4] =
@@ -250,11 +241,6 @@ extern "C" int a3t_pwg_block(float* x, const float* cu, const float* wt0, const 
 extern "C" int a3t_pwg_block_ragged(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1,
                                     const float* b1, float* g, float* skips, const int32_t* tiles, int ntiles, int B, int Tw,
                                     int dil, void* stream) {
-    if (B <= 0 || Tw <= 0 || dil <= 0 || ntiles < 0 || !tiles || ((uintptr_t)tiles & 15)) return A3T_EINVAL;
-    if (ntiles == 0) return 0;
-    PwgArgs a;
-    a.x_in = x, a.cu = cu, a.gin = g, a.g = g, a.x_out = x, a.skips = skips;
-    a.B = B, a.Tw = Tw, a.dil = dil, a.tiles_t = (Tw + 255) / 256;
-    a.tiles = (const int4*)tiles, a.ntiles = ntiles;
-    return pwg_launch<true>(a, wt0, b0, wt1, b1, ntiles, stream);
+    if (!tiles) return A3T_EINVAL;
+    return pwg_block(x, cu, wt0, b0, wt1, b1, g, skips, tiles, ntiles, B, Tw, dil, stream);
 }

@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/a3t_hip.h"
+#include "device_cus.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -205,17 +206,6 @@ __global__ __launch_bounds__(512) void pwg_f16_kernel(PwgF16Args a) {
     }
 }
 
-static int pwg_f16_blocks() {
-    static int n = 0;
-    if (!n) {
-        hipDeviceProp_t prop;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-        n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return n;
-}
-
 template <bool RAGGED>
 static int pwg_f16_launch(const PwgF16Args& a, int ntiles, void* stream) {
     constexpr int lds = (4 * 17 + 4 * 4) * 64 * 16 + 256 * 4;      // 87 040 B
@@ -224,7 +214,7 @@ static int pwg_f16_launch(const PwgF16Args& a, int ntiles, void* stream) {
         (void)hipFuncSetAttribute((const void*)pwg_f16_kernel<RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr = true;
     }
-    const int cus = pwg_f16_blocks();
+    const int cus = device_cus();
     hipLaunchKernelGGL((pwg_f16_kernel<RAGGED>), dim3(ntiles < cus ? ntiles : cus), dim3(512), lds, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

@@ -529,29 +529,9 @@ def pwg_gate(y, c, out):
     L.check(L.load().a3t_pwg_gate(_ptr(y), _ptr(c), _ptr(out), T, H, _stream()), "pwg_gate")
 
 
-def pwg_block(x, cu, wt0, b0, wt1, b1, g, skips, B, Tw, dil):
-    """Fused residual block (a3t_pwg_block): x, skips updated in place."""
-    L.check(L.load().a3t_pwg_block(_ptr(x), _ptr(cu), _ptr(wt0), _ptr(b0), _ptr(wt1), _ptr(b1), _ptr(g), _ptr(skips),
-                                   B, Tw, dil, _stream()), "pwg_block")
-
-
 def pwg_res_skip(o, x, skips):
     T, R = x.shape
     L.check(L.load().a3t_pwg_res_skip(_ptr(o), _ptr(x), _ptr(skips), T, R, skips.shape[1], _stream()), "pwg_res_skip")
-
-
-def pwg_upsample(c, w, out, scale_):
-    """c [Tin][C] or [B][Tin][C] (contiguous) -> out [.., Tin*scale, C]"""
-    B = c.shape[0] if c.dim() == 3 else 1
-    Tin, C = c.shape[-2:]
-    L.check(L.load().a3t_pwg_upsample(_ptr(c), _ptr(w), _ptr(out), B, Tin, C, scale_, _stream()), "pwg_upsample")
-
-
-def replicate_pad(x, y, pad):
-    """x [T][C] or [B][T][C] (contiguous) -> y [.., T + 2 pad, C]"""
-    B = x.shape[0] if x.dim() == 3 else 1
-    T, C = x.shape[-2:]
-    L.check(L.load().a3t_replicate_pad(_ptr(x), _ptr(y), B, T, C, pad, _stream()), "replicate_pad")
 
 
 def _i32(t, what):
@@ -560,18 +540,34 @@ def _i32(t, what):
     return t
 
 
-def replicate_pad_ragged(x, y, lens, pad):
-    """x [B][T][C] -> y [B][T + 2 pad][C], row b clamped to its own [0, lens[b] - 1] (lens: device int32 [B])."""
-    B, T, C = x.shape
-    L.check(L.load().a3t_replicate_pad_ragged(_ptr(x), _ptr(y), _ptr(_i32(lens, "lens")), B, T, C, pad, _stream()),
-            "replicate_pad_ragged")
+def _rows_lens(what, x, lens):
+    """B, T, C of x [T][C] or [B][T][C]; lens (None or device int32 [B]) checked against B."""
+    B = x.shape[0] if x.dim() == 3 else 1
+    if lens is not None and _i32(lens, "lens").numel() != B:
+        raise ValueError(f"{what}: {lens.numel()} lengths for {B} rows")
+    return (B, *x.shape[-2:])
 
 
-def pwg_upsample_ragged(c, w, out, scale_, lens, mul):
-    """c [B][Tin][C] -> out [B][Tin*scale][C]; row b is valid for lens[b] * mul input rows, zero behind."""
-    B, Tin, C = c.shape
-    L.check(L.load().a3t_pwg_upsample_ragged(_ptr(c), _ptr(w), _ptr(out), _ptr(_i32(lens, "lens")), mul, B, Tin, C, scale_,
-                                             _stream()), "pwg_upsample_ragged")
+def pwg_upsample(c, w, out, scale_, lens=None, mul=1):
+    """c [Tin][C] or [B][Tin][C] (contiguous) -> out [.., Tin*scale, C].  lens (device int32 [B]): row b is valid for
+    lens[b] * mul input rows and zero behind."""
+    B, Tin, C = _rows_lens("pwg_upsample", c, lens)
+    if lens is None:
+        rc = L.load().a3t_pwg_upsample(_ptr(c), _ptr(w), _ptr(out), B, Tin, C, scale_, _stream())
+    else:
+        rc = L.load().a3t_pwg_upsample_ragged(_ptr(c), _ptr(w), _ptr(out), _ptr(lens), mul, B, Tin, C, scale_, _stream())
+    L.check(rc, "pwg_upsample")
+
+
+def replicate_pad(x, y, pad, lens=None):
+    """x [T][C] or [B][T][C] (contiguous) -> y [.., T + 2 pad, C].  lens (device int32 [B]): row b is clamped to its own
+    [0, lens[b] - 1]."""
+    B, T, C = _rows_lens("replicate_pad", x, lens)
+    if lens is None:
+        rc = L.load().a3t_replicate_pad(_ptr(x), _ptr(y), B, T, C, pad, _stream())
+    else:
+        rc = L.load().a3t_replicate_pad_ragged(_ptr(x), _ptr(y), _ptr(lens), B, T, C, pad, _stream())
+    L.check(rc, "replicate_pad")
 
 
 def zero_tail(x, lens, mul, B, T):
@@ -616,20 +612,25 @@ def relpos_softmax_fwd_ragged(ac, bd, lens, probs, B, H, T, scale):
             "softmax_fwd_ragged")
 
 
-def pwg_block_ragged(x, cu, wt0, b0, wt1, b1, g, skips, tiles, B, Tw, dil):
-    """Fused residual block over rows of different length (a3t_pwg_block_ragged); tiles: device int32 [ntiles][4] =
-    {row b, first sample t0, valid samples W_b, 0} (vocoder.pwg_tile_list).  The kernel indexes x / cu / g / skips with the list's
-    entries unchecked: 0 <= b < B, t0 < W_b <= Tw are the caller's to guarantee; what can be checked on the host is."""
-    if tiles.dim() != 2 or tiles.shape[1] != 4:
-        raise ValueError(f"pwg_block_ragged: tiles must be (ntiles, 4), got {tuple(tiles.shape)}")
-    if tiles.shape[0] > B * ((Tw + 255) // 256):
-        raise ValueError(f"pwg_block_ragged: {tiles.shape[0]} tiles do not fit {B} rows of {Tw} samples")
+def pwg_block(x, cu, wt0, b0, wt1, b1, g, skips, B, Tw, dil, tiles=None):
+    """Fused residual block, x and skips updated in place.  tiles None: all rows Tw samples long (a3t_pwg_block); else rows of
+    different length (a3t_pwg_block_ragged), tiles: device int32 [ntiles][4] = {row b, first sample t0, valid samples W_b, 0}
+    (vocoder.pwg_tile_list).  The kernel indexes x / cu / g / skips with the list's entries unchecked: 0 <= b < B, t0 < W_b <= Tw
+    are the caller's to guarantee; what can be checked on the host is."""
     for name, t, C in (("x", x, 64), ("cu", cu, 80), ("g", g, 64), ("skips", skips, 64)):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != B * Tw * C:
-            raise ValueError(f"pwg_block_ragged: {name} must be a contiguous fp32 [{B * Tw}][{C}] tensor")
-    L.check(L.load().a3t_pwg_block_ragged(_ptr(x), _ptr(cu), _ptr(wt0), _ptr(b0), _ptr(wt1), _ptr(b1), _ptr(g), _ptr(skips),
-                                          _ptr(_i32(tiles, "tiles")), tiles.shape[0], B, Tw, dil, _stream()),
-            "pwg_block_ragged")
+            raise ValueError(f"pwg_block: {name} must be a contiguous fp32 [{B * Tw}][{C}] tensor")
+    args = (_ptr(x), _ptr(cu), _ptr(wt0), _ptr(b0), _ptr(wt1), _ptr(b1), _ptr(g), _ptr(skips))
+    if tiles is None:
+        L.check(L.load().a3t_pwg_block(*args, B, Tw, dil, _stream()), "pwg_block")
+        return
+    if tiles.dim() != 2 or tiles.shape[1] != 4:
+        raise ValueError(f"pwg_block: tiles must be (ntiles, 4), got {tuple(tiles.shape)}")
+    if tiles.shape[0] > B * ((Tw + 255) // 256):
+        raise ValueError(f"pwg_block: {tiles.shape[0]} tiles do not fit {B} rows of {Tw} samples")
+    _i32(tiles, "tiles")
+    if tiles.shape[0]:      # (an empty tensor has no address)
+        L.check(L.load().a3t_pwg_block_ragged(*args, _ptr(tiles), tiles.shape[0], B, Tw, dil, _stream()), "pwg_block")
 
 
 def cast_f16_sat(src, dst):
@@ -643,7 +644,7 @@ def cast_f16_sat(src, dst):
 def pwg_block_f16(x_in, x_out, cu16, w0h, b0, w1h, b1, skips, tiles, B, Tw, dil):
     """Fused residual block in one launch on the 16-bit MFMA (a3t_pwg_block_f16): x_in -> x_out (two different buffers), skips in
     place.  cu16 / w0h / w1h fp16 (cast_f16_sat, vocoder.pack_pwg_block_f16); tiles: None = all rows Tw samples long, else the
-    list of pwg_block_ragged."""
+    list of pwg_block."""
     for name, t, C, dt in (("x_in", x_in, 64, torch.float32), ("x_out", x_out, 64, torch.float32), ("cu16", cu16, 80, torch.float16),
                            ("skips", skips, 64, torch.float32)):
         if t.dtype != dt or not t.is_contiguous() or t.numel() != B * Tw * C:

@@ -169,145 +169,103 @@ class ParallelWaveGANGeneratorHIP:
         B, Tf, A = c.shape
         if normalize_before and self.stats is not None:
             c = (c - self.stats[0]) / self.stats[1]
-        if lengths is not None:
-            if single:
-                raise ValueError("lengths= goes with a (B, Tmax, aux) batch")
-            return self._inference_ragged(c, z, lengths)
-        Tw = Tf * self.upsample_factor
-        if z is None:
-            z = torch.randn(B, Tw, 1, device=self.dev)
-        z = z.to(self.dev, torch.float32).reshape(B * Tw, 1).contiguous()
+        if lengths is not None and single:
+            raise ValueError("lengths= goes with a (B, Tmax, aux) batch")
+        hop = self.upsample_factor
+        Tw = Tf * hop
         dev = self.dev
+        lens = tiles = None
+        if lengths is not None:
+            lengths = [int(x) for x in lengths]
+            if len(lengths) != B or any(n < 0 or n > Tf for n in lengths):
+                raise ValueError(f"lengths {lengths} do not fit a batch of {B} rows of {Tf} frames")
+            # one H2D copy: lens [B] | tile list [ntiles][4] = {b, t0, W_b, 0} for the fused blocks (offset kept 16-byte aligned)
+            tl = pwg_tile_list(lengths, hop)
+            off = (B + 3) // 4 * 4
+            host = np.zeros(off + tl.size, dtype=np.int32)
+            host[:B] = lengths
+            host[off:] = tl.reshape(-1)
+            meta = torch.from_numpy(host).to(dev)
+            lens, tiles = meta[:B], meta[off:].view(len(tl), 4)
+        if z is None:
+            z = torch.randn(B, Tw, 1, device=dev)
+        z = z.to(dev, torch.float32).reshape(B * Tw, 1).contiguous()
         # ---- ConvInUpsampleNetwork: replication pad, conv_in (k = 2*ctx+1, no bias), stretch+smooth per scale
         w = self.ctx
         Tp = Tf + 2 * w
         cp = torch.empty(B * Tp, A, device=dev)
-        ops.replicate_pad(c.contiguous(), cp, w)
-        ci = torch.empty(B * Tp, A, device=dev)
-        ops.conv_fwd(cp, self.w_in, ci, Tp, w, compute=F32)
-        cu = ci.view(B, Tp, A)[:, w:w + Tf].contiguous()
-        T = Tf
-        for sc, wk in zip(self.scales, self.w_up):
-            out = torch.empty(B, T * sc, A, device=dev)
-            ops.pwg_upsample(cu, wk, out, sc)
-            cu, T = out, T * sc
-        cu = cu.view(B * Tw, A)
-        # ---- first conv (1 -> R), residual stack
-        x = torch.empty(B * Tw, self.R, device=dev)
-        ops.linear_fwd(z, self.w_first, x, bias=self.b_first, compute=F32)
-        skips = torch.zeros(B * Tw, self.S, device=dev)
-        if self.compute == "f16":
-            self._blocks_f16(x, cu, skips, None, B, Tw)
-        else:
-            self._blocks_f32(x, cu, skips, B, Tw)
-        ops.bias_act(skips, None, ACT_RELU, math.sqrt(1.0 / self.layers))
-        h = torch.empty(B * Tw, self.S, device=dev)
-        ops.linear_fwd(skips, self.w_l1, h, bias=self.b_l1, act=ACT_RELU, compute=F32)
-        wav = torch.empty(B * Tw, 1, device=dev)
-        ops.linear_fwd(h, self.w_l3, wav, bias=self.b_l3, compute=F32)
-        wav = wav.view(B, Tw, 1)
-        return wav[0] if single else wav
-
-    def _blocks_f32(self, x, cu, skips, B, Tw):
-        """The residual stack in fp32, rows of equal length: x and skips updated in place."""
-        dev = self.dev
-        y = torch.empty(B * Tw, self.G, device=dev)
-        ca = torch.empty(B * Tw, self.G, device=dev)
-        g = torch.empty(B * Tw, self.G // 2, device=dev)
-        o = torch.empty(B * Tw, self.R + self.S, device=dev)
-        lps = self.layers // self.stacks
-        for l, blk in enumerate(self.blocks):
-            dil = 2 ** (l % lps)
-            if self.fused:
-                ops.pwg_block(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], g, skips, B, Tw, dil)
-                continue
-            ops.conv_fwd(x, blk["w"], y, Tw, 1, dil, bias=blk["b"], compute=F32)
-            ops.linear_fwd(cu, blk["aux"], ca, compute=F32)
-            ops.pwg_gate(y, ca, g)
-            ops.linear_fwd(g, blk["out"], o, bias=blk["bout"], compute=F32)
-            ops.pwg_res_skip(o, x, skips)
-
-    def _blocks_f16(self, x, cu, skips, tiles, B, Tw):
-        """The residual stack on the 16-bit MFMA: cu is cast once, x ping-pongs between two buffers (a block must not
-        overwrite the x[t +- dil] that other tiles still read); skips is updated in place, x is left undefined."""
-        cu16 = torch.empty(B * Tw, self.A, dtype=torch.float16, device=self.dev)
-        ops.cast_f16_sat(cu, cu16)
-        x2 = torch.empty_like(x)
-        lps = self.layers // self.stacks
-        for l, blk in enumerate(self.blocks):
-            ops.pwg_block_f16(x, x2, cu16, blk["w0h"], blk["b0h"], blk["w1h"], blk["bout"], skips, tiles, B, Tw, 2 ** (l % lps))
-            x, x2 = x2, x
-
-    @property
-    def margin_frames(self) -> int:
-        """pwg_margin_frames of this generator's configuration (kernel size 3: the only one the class builds)."""
-        return pwg_margin_frames(self.layers, self.stacks, 3, self.scales, self.ctx)
-
-    def _inference_ragged(self, c, z, lengths):
-        """Rows of different length in the padded (B, Tmax) layout; lens on the device, nothing is repacked."""
-        B, Tf, A = c.shape
-        hop = self.upsample_factor
-        lengths = [int(x) for x in lengths]
-        if len(lengths) != B or any(n < 0 or n > Tf for n in lengths):
-            raise ValueError(f"lengths {lengths} do not fit a batch of {B} rows of {Tf} frames")
-        Tw = Tf * hop
-        dev = self.dev
-        # one H2D copy: lens [B] | tile list [ntiles][4] = {b, t0, W_b, 0} for the fused blocks (offset kept 16-byte aligned)
-        tl = pwg_tile_list(lengths, hop)
-        off = (B + 3) // 4 * 4
-        host = np.zeros(off + tl.size, dtype=np.int32)
-        host[:B] = lengths
-        host[off:] = tl.reshape(-1)
-        meta = torch.from_numpy(host).to(dev)
-        lens, tiles = meta[:B], meta[off:].view(len(tl), 4)
-        if z is None:
-            z = torch.randn(B, Tw, 1, device=dev)
-        z = z.to(dev, torch.float32).reshape(B * Tw, 1).contiguous()
-        w = self.ctx
-        Tp = Tf + 2 * w
-        cp = torch.empty(B * Tp, A, device=dev)
-        ops.replicate_pad_ragged(c.contiguous(), cp.view(B, Tp, A), lens, w)
+        ops.replicate_pad(c.contiguous(), cp, w, lens)
         ci = torch.empty(B * Tp, A, device=dev)
         ops.conv_fwd(cp, self.w_in, ci, Tp, w, compute=F32)
         cu = ci.view(B, Tp, A)[:, w:w + Tf].contiguous()
         T, mul = Tf, 1
         for sc, wk in zip(self.scales, self.w_up):
             out = torch.empty(B, T * sc, A, device=dev)
-            ops.pwg_upsample_ragged(cu, wk, out, sc, lens, mul)
+            ops.pwg_upsample(cu, wk, out, sc, lens, mul)
             cu, T, mul = out, T * sc, mul * sc
         cu = cu.view(B * Tw, A)
+        # ---- first conv (1 -> R), residual stack
         x = torch.empty(B * Tw, self.R, device=dev)
         ops.linear_fwd(z, self.w_first, x, bias=self.b_first, compute=F32)
         skips = torch.zeros(B * Tw, self.S, device=dev)
-        g = torch.empty(B * Tw, self.G // 2, device=dev)
-        lps = self.layers // self.stacks
         if self.compute == "f16":
-            self._blocks_f16(x, cu, skips, tiles, B, Tw)
-        elif self.fused:
-            for l, blk in enumerate(self.blocks):
-                if tiles.shape[0]:
-                    ops.pwg_block_ragged(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], g, skips, tiles, B, Tw,
-                                         2 ** (l % lps))
-        else:
-            # layer by layer: the rows behind W_b of x are zeroed after every block, so that the convolution's taps beyond a
-            # row's end read zeros like those beyond Tmax; what the tail of y / g / o / skips holds never reaches a valid row
-            y = torch.empty(B * Tw, self.G, device=dev)
-            ca = torch.empty(B * Tw, self.G, device=dev)
-            o = torch.empty(B * Tw, self.R + self.S, device=dev)
-            ops.zero_tail(x, lens, hop, B, Tw)
-            for l, blk in enumerate(self.blocks):
-                ops.conv_fwd(x, blk["w"], y, Tw, 1, 2 ** (l % lps), bias=blk["b"], compute=F32)
-                ops.linear_fwd(cu, blk["aux"], ca, compute=F32)
-                ops.pwg_gate(y, ca, g)
-                ops.linear_fwd(g, blk["out"], o, bias=blk["bout"], compute=F32)
-                ops.pwg_res_skip(o, x, skips)
-                ops.zero_tail(x, lens, hop, B, Tw)
+            cu16 = torch.empty(B * Tw, A, dtype=torch.float16, device=dev)
+            ops.cast_f16_sat(cu, cu16)
+            cu = cu16
+        self._blocks(x, cu, skips, B, Tw, lens, tiles)
         ops.bias_act(skips, None, ACT_RELU, math.sqrt(1.0 / self.layers))
         h = torch.empty(B * Tw, self.S, device=dev)
         ops.linear_fwd(skips, self.w_l1, h, bias=self.b_l1, act=ACT_RELU, compute=F32)
         wav = torch.empty(B * Tw, 1, device=dev)
         ops.linear_fwd(h, self.w_l3, wav, bias=self.b_l3, compute=F32)
-        ops.zero_tail(wav, lens, hop, B, Tw)
-        return wav.view(B, Tw, 1)
+        if lens is not None:
+            ops.zero_tail(wav, lens, hop, B, Tw)
+        wav = wav.view(B, Tw, 1)
+        return wav[0] if single else wav
+
+    def _scratch(self, n):
+        """The buffers of n = B * Tw samples that _blocks needs beside its arguments."""
+        def e(C):
+            return torch.empty(n, C, device=self.dev)
+        if self.compute == "f16":
+            return dict(x2=e(self.R))
+        if self.fused:
+            return dict(g=e(self.G // 2))
+        return dict(y=e(self.G), ca=e(self.G), g=e(self.G // 2), o=e(self.R + self.S))
+
+    def _blocks(self, x, cu, skips, B, Tw, lens=None, tiles=None, scratch=None):
+        """The residual stack: skips is updated in place, and so is x except with compute="f16", which leaves it undefined.
+        lens / tiles: rows of different length (lens [B] frames, tiles = pwg_tile_list of them, both on the device), else all
+        rows are Tw samples long.  scratch: _scratch(B * Tw), for a caller that wants no allocation in here.
+
+        compute="f16": cu is the fp16 cast (ops.cast_f16_sat) and x ping-pongs between two buffers (a block must not overwrite
+        the x[t +- dil] that other tiles still read).  Layer by layer: the rows behind W_b of x are zeroed after every block,
+        so that the convolution's taps beyond a row's end read zeros like those beyond Tmax; what the tail of y / g / o / skips
+        holds never reaches a valid row."""
+        s = scratch if scratch is not None else self._scratch(B * Tw)
+        hop, lps = self.upsample_factor, self.layers // self.stacks
+        if not self.fused and lens is not None:
+            ops.zero_tail(x, lens, hop, B, Tw)
+        x2 = s.get("x2")
+        for l, blk in enumerate(self.blocks):
+            dil = 2 ** (l % lps)
+            if self.compute == "f16":
+                ops.pwg_block_f16(x, x2, cu, blk["w0h"], blk["b0h"], blk["w1h"], blk["bout"], skips, tiles, B, Tw, dil)
+                x, x2 = x2, x
+            elif self.fused:
+                ops.pwg_block(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], s["g"], skips, B, Tw, dil, tiles)
+            else:
+                ops.conv_fwd(x, blk["w"], s["y"], Tw, 1, dil, bias=blk["b"], compute=F32)
+                ops.linear_fwd(cu, blk["aux"], s["ca"], compute=F32)
+                ops.pwg_gate(s["y"], s["ca"], s["g"])
+                ops.linear_fwd(s["g"], blk["out"], s["o"], bias=blk["bout"], compute=F32)
+                ops.pwg_res_skip(s["o"], x, skips)
+                if lens is not None:
+                    ops.zero_tail(x, lens, hop, B, Tw)
+
+    @property
+    def margin_frames(self) -> int:
+        """pwg_margin_frames of this generator's configuration (kernel size 3: the only one the class builds)."""
+        return pwg_margin_frames(self.layers, self.stacks, 3, self.scales, self.ctx)
 
     __call__ = inference

@@ -201,6 +201,65 @@ def test_ragged_vocoder_refuses_lengths_that_do_not_fit():
     assert not out[0].any() and not out[1, 600:].any() and out[1, :600].any()
 
 
+def test_replicate_pad_and_upsample_rows_end_at_their_own_length():
+    """ops.replicate_pad and ops.pwg_upsample alone, B = 3 rows of C = 3 channels with NaN behind each row's length, bit for bit
+    against a float32 restatement (taps added in the kernel's order, product and sum rounded separately), nothing NaN, and
+    full lengths give the bits of lens=None.  replicate_pad: T = 5, pad = 2, lens (5, 1, 0): the row of one frame is shorter
+    than the pad and clamps to that frame on both sides, the empty row is zero.  pwg_upsample: scale 3, mul 2, Tin = 6, lens
+    (3, 1, 0): rows valid for 6, 2 and 0 input frames."""
+    from a3t_amd import ops
+    rs = np.random.RandomState(7)
+    B, C = 3, 3
+
+    def dev(a, dtype=None):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(DEV, dtype)
+
+    # ---- replicate_pad
+    T, pad, lens = 5, 2, (5, 1, 0)
+    x = rs.standard_normal((B, T, C)).astype(np.float32)
+    xn = x.copy()
+    ref = np.zeros((B, T + 2 * pad, C), np.float32)
+    for b, n in enumerate(lens):
+        xn[b, n:] = np.nan
+        for u in range(T + 2 * pad):
+            if n > 0:
+                ref[b, u] = x[b, min(max(u - pad, 0), n - 1)]
+    y = torch.full((B, T + 2 * pad, C), float("nan"), device=DEV)
+    ops.replicate_pad(dev(xn), y, pad, dev(lens, torch.int32))
+    assert not torch.isnan(y).any()
+    assert torch.equal(y.cpu(), torch.from_numpy(ref))
+    y_full, y_dense = torch.empty_like(y), torch.empty_like(y)
+    ops.replicate_pad(dev(x), y_full, pad, dev((T,) * B, torch.int32))
+    ops.replicate_pad(dev(x), y_dense, pad)
+    assert torch.equal(y_full, y_dense)
+
+    # ---- pwg_upsample
+    scale, mul, Tin, lens = 3, 2, 6, (3, 1, 0)
+    w = rs.standard_normal(2 * scale + 1).astype(np.float32)
+    c = rs.standard_normal((B, Tin, C)).astype(np.float32)
+    cn = c.copy()
+    ref = np.zeros((B, Tin * scale, C), np.float32)
+    for b, n in enumerate(lens):
+        cn[b, n * mul:] = np.nan
+        Lout = n * mul * scale
+        for t in range(Lout):
+            acc = np.zeros(C, np.float32)
+            for j in range(2 * scale + 1):
+                u = t + j - scale
+                if 0 <= u < Lout:
+                    acc = acc + w[j] * c[b, u // scale]      # float32 product, then float32 sum
+            ref[b, t] = acc
+    assert ref.dtype == np.float32
+    out = torch.full((B, Tin * scale, C), float("nan"), device=DEV)
+    ops.pwg_upsample(dev(cn), dev(w), out, scale, dev(lens, torch.int32), mul)
+    assert not torch.isnan(out).any()
+    assert torch.equal(out.cpu(), torch.from_numpy(ref))
+    o_full, o_dense = torch.empty_like(out), torch.empty_like(out)
+    ops.pwg_upsample(dev(c), dev(w), o_full, scale, dev((Tin // mul,) * B, torch.int32), mul)
+    ops.pwg_upsample(dev(c), dev(w), o_dense, scale)
+    assert torch.equal(o_full, o_dense)
+
+
 # ---------------------------------------------------------------------------------------------------------------- infill
 def test_inference_batch_against_oracle():
     """Four requests of different kind and length in one batch, fp32: per row the oracle's forward on the oracle's collate

@@ -142,7 +142,6 @@ def legs(ed, reqs, span_only, calls, warmup):
 
 def kernel_bench(frames, lengths_sets, reps=5):
     """30 fused residual blocks on B x frames x hop samples: padded, ragged with equal lengths, ragged lengths; ms."""
-    from a3t_amd import ops
     from a3t_amd.vocoder import ParallelWaveGANGeneratorHIP, pwg_tile_list
     gen = ParallelWaveGANGeneratorHIP(vocoder_state(), device="cuda")
     hop, out = gen.upsample_factor, {}
@@ -152,7 +151,7 @@ def kernel_bench(frames, lengths_sets, reps=5):
         # every run and the result is checked to be finite, so the gate's exp / rcp work on ordinary numbers
         x0 = 0.1 * torch.randn(B * Tw, 64, device="cuda")
         cu = 1.5 * torch.randn(B * Tw, 80, device="cuda") - 4.0
-        g = torch.empty(B * Tw, 64, device="cuda")
+        scratch = gen._scratch(B * Tw)
         tiles = torch.from_numpy(pwg_tile_list(lengths, hop)).to("cuda")
         equal = all(n == frames for n in lengths)
 
@@ -160,11 +159,7 @@ def kernel_bench(frames, lengths_sets, reps=5):
             x, sk = x0.clone(), torch.zeros(B * Tw, 64, device="cuda")
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            for l, blk in enumerate(gen.blocks):
-                if ragged:
-                    ops.pwg_block_ragged(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], g, sk, tiles, B, Tw, 2 ** (l % 10))
-                else:
-                    ops.pwg_block(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], g, sk, B, Tw, 2 ** (l % 10))
+            gen._blocks(x, cu, sk, B, Tw, tiles=tiles if ragged else None, scratch=scratch)
             b.record()
             torch.cuda.synchronize()
             fin.append(bool(torch.isfinite(x).all()) and bool(torch.isfinite(sk).all()))
@@ -195,6 +190,7 @@ def kernel_bench_f16(frames, lengths_sets, calls=50, warmup=3):
     from a3t_amd import ops
     from a3t_amd.vocoder import ParallelWaveGANGeneratorHIP, pwg_tile_list
     gen = ParallelWaveGANGeneratorHIP(vocoder_state(), device="cuda", compute="f16")
+    gen32 = ParallelWaveGANGeneratorHIP(vocoder_state(), device="cuda")
     hop, out = gen.upsample_factor, {}
     for name, lengths in lengths_sets.items():
         B, Tw = len(lengths), frames * hop
@@ -202,25 +198,20 @@ def kernel_bench_f16(frames, lengths_sets, calls=50, warmup=3):
         cu = 1.5 * torch.randn(B * Tw, 80, device="cuda") - 4.0
         cu16 = torch.empty(B * Tw, 80, dtype=torch.float16, device="cuda")
         ops.cast_f16_sat(cu, cu16)
-        g = torch.empty(B * Tw, 64, device="cuda")
+        scratch32 = gen32._scratch(B * Tw)
         equal = all(n == frames for n in lengths)
         tiles = None if equal else torch.from_numpy(pwg_tile_list(lengths, hop)).to("cuda")
         fin = []
 
         def run(f16):
             x, sk = x0.clone(), torch.zeros(B * Tw, 64, device="cuda")
-            x2 = torch.empty_like(x)
+            scratch16 = gen._scratch(B * Tw)
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            for l, blk in enumerate(gen.blocks):
-                dil = 2 ** (l % 10)
-                if f16:
-                    ops.pwg_block_f16(x, x2, cu16, blk["w0h"], blk["b0h"], blk["w1h"], blk["bout"], sk, tiles, B, Tw, dil)
-                    x, x2 = x2, x
-                elif tiles is None:
-                    ops.pwg_block(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], g, sk, B, Tw, dil)
-                else:
-                    ops.pwg_block_ragged(x, cu, blk["wt0"], blk["b0"], blk["wt1"], blk["bout"], g, sk, tiles, B, Tw, dil)
+            if f16:
+                gen._blocks(x, cu16, sk, B, Tw, tiles=tiles, scratch=scratch16)
+            else:
+                gen32._blocks(x, cu, sk, B, Tw, tiles=tiles, scratch=scratch32)
             b.record()
             torch.cuda.synchronize()
             fin.append(bool(torch.isfinite(sk).all()))
