@@ -8,14 +8,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "liba3t_hip.so")
-SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_bf16_8p.hip", "gemm_bf16_pn.hip", "gemm_bf16_tt.hip", "attn_fused.hip", "norm_reduce.hip", "convmod_attn.hip", "dwconv_vec.hip", "misc.hip", "pwg_fused.hip", "pwg_fused_f16.hip", "features.hip", "duration.hip", "gst.hip"]
+SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_bf16_8p.hip", "gemm_bf16_tn.hip", "gemm_bf16_pn.hip", "gemm_bf16_tt.hip", "attn_fused.hip", "norm_reduce.hip", "convmod_attn.hip", "dwconv_vec.hip", "misc.hip", "pwg_fused.hip", "pwg_fused_f16.hip", "features.hip", "duration.hip", "gst.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"] + os.environ.get("A3T_EXTRA_FLAGS", "").split()
 
 
 # The direct-to-LDS GEMM variants are tuned to a register budget (<= 128 VGPRs = 4 workgroups per CU); a harmless
 # looking edit can push one over the edge and cost 30-50 % on that GEMM class.  The build records what the compiler
 # allocated; tests/test_host_logic.py::test_gemm_register_budget checks it.
-RES_SOURCES = ("gemm_bf16.hip", "gemm_bf16_8p.hip", "gemm_bf16_pn.hip", "gemm_bf16_tt.hip", "attn_fused.hip", "norm_reduce.hip")
+RES_SOURCES = ("gemm_bf16.hip", "gemm_bf16_8p.hip", "gemm_bf16_tn.hip", "gemm_bf16_pn.hip", "gemm_bf16_tt.hip", "attn_fused.hip", "norm_reduce.hip")
 RES_FLAG = ["-Rpass-analysis=kernel-resource-usage"]
 
 
@@ -51,14 +51,14 @@ def _stale(out, deps):
 
 def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
-    hdr = os.path.join(os.path.dirname(HERE), "include", "a3t_hip.h")
+    hdrs = [os.path.join(os.path.dirname(HERE), "include", "a3t_hip.h")]
+    hdrs += sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h"))
     objs, jobs = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(LIBDIR, s.replace(".hip", ".o"))
         objs.append(obj)
-        if force or _stale(obj, [src, hdr, os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "dtype_io.h"),
-                                os.path.join(CSRC, "device_cus.h")]):
+        if force or _stale(obj, [src] + hdrs):
             jobs.append([_hipcc(), *FLAGS, "-c", src, "-o", obj] + (RES_FLAG if s in RES_SOURCES else []))
 
     def run(cmd):

@@ -33,14 +33,13 @@
 #include "../../include/a3t_hip.h"
 #include "dtype_io.h"
 #include "device_cus.h"
+#include "mfma_kit.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16;
 
-#define LDS_AS(p) ((__attribute__((address_space(3))) void*)(p))
 
 struct AttnArgs {
     const u16* qu;        // (q + pos_bias_u)  [B*T][ldq], head h at column h*dk
@@ -211,7 +210,6 @@ __device__ __forceinline__ void mfma_drain() { asm volatile("s_nop 15\n\ts_nop 7
 // permutation is legal as long as A and B agree; {0,2,1,3} keeps the four 16-lane groups of a ds_read_b128 on distinct
 // bank slots).  C layout: column = query, rows 4*lg + r.
 // =====================================================================================================================
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define SC16_LD 68
 
 __device__ __forceinline__ void mfma16_cacc(f32x4& acc, const bf16x8& a, const bf16x8& b) {
@@ -279,11 +277,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd16_kernel(AttnArgs p) {
     const int PI = ((lg & 1) << 1) | (lg >> 1);          // k-chunk of this lane group inside a 32-deep MFMA step
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int T = p.T, NQB = (T + 127) / 128, NS = (T + 31) / 32;
-    int wi = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wi & 7;
-        wi = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (wi >> 3);
-    }
+    const int wi = xcd_contiguous(blockIdx.x, gridDim.x);
     if (p.use_redo && attn_redo[wi & 0xffff] == 0) return;
     const int bh = wi / NQB, qb = wi - bh * NQB;
     const int b = bh / p.H, h = bh - b * p.H;
@@ -531,8 +525,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
         titem = t / p.nparts, part = t - titem * p.nparts;
         wi = p.item0 + titem;
     } else {
-        const int nwg = SPLIT ? p.item0 : (int)gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wi & 7;
-        wi = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (wi >> 3);
+        wi = xcd_contiguous(wi, SPLIT ? p.item0 : (int)gridDim.x);
     }
     if (TWOPASS && attn_redo[wi & 0xffff] == 0) return;     // fixup launch: only the blocks whose row sums overflowed
     const int bh = wi / NQB, qb = wi - bh * NQB;
@@ -1181,11 +1174,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_ds_kernel(DsArgs p) {
     // take neighbouring task ranges = the query blocks of the same few (b, h) and share their V tiles there.  (Round 6 measured
     // what that is worth: FETCH_SIZE 514 MB against 538 MB per launch with workgroup id = range index, 182 against 184 us --
     // profiles/r06_ds_map_ab.txt.  The V tiles were never the kernel's problem; the mapping stays because it costs nothing.)
-    int vb = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = vb & 7;
-        vb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
-    }
+    const int vb = xcd_contiguous(blockIdx.x, gridDim.x);
     const int64_t tper = (ntasks + gridDim.x - 1) / gridDim.x;
     int64_t task = (int64_t)vb * tper;
     const int64_t tend = task + tper < ntasks ? task + tper : ntasks;
@@ -1421,7 +1410,7 @@ static inline bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 // like the overflow flags it serves ONE attention launch at a time per device (the engine issues them on one stream)
 static float* attn_ws_ptr[64];
 static size_t attn_ws_cap[64];
-void attn_release_split_ws() {      // a3t_release_workspaces (gemm_bf16_8p.hip); the caller has drained the attention stream
+void attn_release_split_ws() {      // a3t_release_workspaces (gemm_bf16_tn.hip); the caller has drained the attention stream
     int cur = 0;
     (void)hipGetDevice(&cur);
     for (int dev = 0; dev < 64; ++dev)

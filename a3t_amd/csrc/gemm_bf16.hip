@@ -22,16 +22,15 @@
 #include <type_traits>
 #include "../../include/a3t_hip.h"
 #include "gemm_common.h"
+#include "mfma_kit.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16;
 
 __device__ __attribute__((aligned(16))) unsigned int a3t_zero_page[16];
 
-#define LDS_AS(p) ((__attribute__((address_space(3))) void*)(p))
 #define GLB_AS(p) ((const __attribute__((address_space(1))) void*)(p))
 
 // -DGLDS_TIMING (A3T_EXTRA_FLAGS): per-workgroup phase times of the single-buffer K loop (round-2 tool, see profiles/NOTEBOOK_r01_r03.md)
@@ -69,11 +68,7 @@ __global__ __launch_bounds__(128 * WM, (WN == 3 ? (STAGES == 2 ? 2 : 3) : (STAGE
     // CONTIGUOUS run of work items (bijective remap), ordered slice-major / tile-minor: the tiles of one batch element
     // or of one K-split -- which read the same operand slabs -- stay inside one XCD's private L2 instead of being
     // fetched by all eight (the 2-D grid did that: 5x the algorithmic HBM traffic on the split-K weight gradients).
-    int wi = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wi & 7;
-        wi = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (wi >> 3);
-    }
+    const int wi = xcd_contiguous(blockIdx.x, gridDim.x);
     const int bid = wi % p.ntiles, zy = wi / p.ntiles;
     const int tn = bid % p.tiles_n, tm = bid / p.tiles_n;      // (an L2-blocked tile order -- column groups -- was ruled out in round 3)
     const int ks = zy % p.splitk, bz = zy / p.splitk;

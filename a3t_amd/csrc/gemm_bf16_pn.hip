@@ -41,36 +41,15 @@
 #include <stdlib.h>
 #include "../../include/a3t_hip.h"
 #include "gemm_common.h"
+#include "mfma_kit.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16;
-
-#define LDS_AS(p) ((__attribute__((address_space(3))) void*)(p))
-#define SB() __builtin_amdgcn_sched_barrier(0)
-#define BAR()                                   \
-    do {                                        \
-        SB();                                   \
-        asm volatile("s_barrier" ::: "memory"); \
-        SB();                                   \
-    } while (0)
-#define WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define WAIT_LGKM(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
 
 namespace {
 constexpr int PN_ROWS = 160, PN_COLS = 384;
 constexpr int A_BYTES = PN_ROWS * 128, BH_BYTES = 192 * 128, BUF_BYTES = A_BYTES + 2 * BH_BYTES;   // 20 + 24 + 24 KiB
 constexpr int LDS_CSUM = 2 * BUF_BYTES;        // 384 fp32 column sums of the tile in flight
 constexpr int LDS_TOTAL = LDS_CSUM + PN_COLS * 4;                                                   // 140 800 B
-constexpr unsigned OOB = 0x80000000u;         // voffset beyond every descriptor (host contract: operands < 2 GiB)
-
-__device__ __forceinline__ float row16_sum(float v) {   // sum over the 16 lanes of a DPP row, result in every lane
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));  // row_half_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));  // row_mirror
-    return v;
-}
 }   // namespace
 
 template <bool CONV>

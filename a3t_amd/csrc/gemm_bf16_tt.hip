@@ -29,45 +29,16 @@
 #include <stdlib.h>
 #include "../../include/a3t_hip.h"
 #include "gemm_common.h"
+#include "mfma_kit.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16;
-
-#define LDS_AS(p) ((__attribute__((address_space(3))) void*)(p))
-#define SB() __builtin_amdgcn_sched_barrier(0)
-#define BAR()                                   \
-    do {                                        \
-        SB();                                   \
-        asm volatile("s_barrier" ::: "memory"); \
-        SB();                                   \
-    } while (0)
-#define WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "buffer_load_dwordx4 ... lds (16-byte LDS-DMA) exists on gfx950 only: build with --offload-arch=gfx950"
-#endif
 
 namespace {
 constexpr int TT_MAX_ROWS = 320, TT_BK = 32, TT_STAGES = 4;
 constexpr int TT_A_BYTES = TT_MAX_ROWS * TT_BK * 2, TT_B_BYTES = 192 * TT_BK * 2, TT_STAGE = TT_A_BYTES + TT_B_BYTES;   // 20 + 12 KiB
 constexpr int TT_LDS = TT_STAGES * TT_STAGE;                                                                            // 128 KiB
-constexpr unsigned OOB = 0x80000000u;         // voffset beyond every descriptor (operands of one batch element < 2 GiB)
-
-// (asm: in front of __builtin_amdgcn_ds_read_tr16_b64 hipcc drains every LDS-DMA it has seen issued through the builtin;
-//  see gemm_bf16_8p.hip)
-__device__ __forceinline__ void tt_dma16(const __amdgpu_buffer_rsrc_t& r, unsigned lds_addr, unsigned voff, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(voff), "s"(r), "s"(soff) : "memory");
-}
-__device__ __forceinline__ float tt_row16_sum(float v) {   // sum over the 16 lanes of a DPP row, result in every lane
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));  // row_half_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));  // row_mirror
-    return v;
-}
 }   // namespace
 
 // -DTT_TIMING (probe build): wall-clock stamps (100 MHz) per workgroup: start, first barrier passed, K loop done, epilogue done
@@ -89,12 +60,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tt_kernel(GP p, int TR) {
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = w >> 2, wc = w & 3;
     TT_STAMP(0);
-    int wi = blockIdx.x;
-    {   // workgroup b runs on XCD b % 8: every XCD gets a contiguous run of (batch element, row tile) -- the row tiles of a
-        // batch element read the same B from one L2
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wi & 7;
-        wi = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (wi >> 3);
-    }
+    // workgroup b runs on XCD b % 8: every XCD gets a contiguous run of (batch element, row tile) -- the row tiles of a
+    // batch element read the same B from one L2
+    const int wi = xcd_contiguous(blockIdx.x, gridDim.x);
     const int tm = wi % p.ntiles, bz = wi / p.ntiles;
     const int z0 = bz / p.batch_inner, z1 = bz % p.batch_inner;
     const u16* A = (const u16*)p.A + z0 * p.a_bs0 + z1 * p.a_bs1;
@@ -154,13 +122,13 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tt_kernel(GP p, int TR) {
             const unsigned so = (unsigned)k2 * kstep2;
             const int krem = p.K - k2 * TT_BK;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) tt_dma16(rX2, dst + q * 1024, kq[q] < krem ? voff2[q] : OOB, so);
+            for (int q = 0; q < 4; ++q) dma16(rX2, dst + q * 1024, kq[q] < krem ? voff2[q] : OOB, so);
             return;
         }
         const unsigned so = (unsigned)kt * kstep;
         const int krem = p.K - kt * TT_BK;      // <= 0: a K-tile past the end (zeros)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) tt_dma16(rX, dst + q * 1024, kq[q] < krem ? voff[q] : OOB, so);
+        for (int q = 0; q < 4; ++q) dma16(rX, dst + q * 1024, kq[q] < krem ? voff[q] : OOB, so);
     };
 
     // ---- fragment geometry: lane (g, pp)
@@ -278,9 +246,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tt_kernel(GP p, int TR) {
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float t = tt_row16_sum(cs[j][r]);
+                const float t = row16_sum(cs[j][r]);
                 if (DUAL) {     // first product's sums from the hand-over, second = the rest
-                    const float t1 = tt_row16_sum(cs1[j][r] * alpha);
+                    const float t1 = row16_sum(cs1[j][r] * alpha);
                     if (pp == 0 && ccol + j * 16 < p.N) {
                         atomicAdd(o + j * 16 + r, p.colsum_scale * t1);
                         atomicAdd(o + (p.colsum2 - p.colsum) + j * 16 + r, p.colsum_scale * (t - t1));

@@ -34,7 +34,7 @@ struct GP {
     int colsum_slots, colsum_ss;   // >1: atomics spread over `slots` accumulator copies, `ss` floats apart
     unsigned int drop_key, drop_thr;
     float drop_inv;   // 1/(1-p), 0 when dropout is off
-    // 8-phase kernel (gemm_bf16_8p.hip)
+    // 8-phase kernels (gemm_bf16_8p.hip, gemm_bf16_tn.hip)
     unsigned char* keep_out;        // optional: one keep bit per output (value > 0), tile-major image
     const unsigned char* keep_in;   // optional: keep bits applied as a mask (written by the GEMM with the same M x N tiling)
     unsigned int a_bytes, b_bytes;  // operand extents for the buffer descriptors
@@ -251,7 +251,9 @@ void glds_plan(const GP& p, int batch, int ly, GemmPlan* pl);   // gemm_bf16.hip
 int glds_launch(const GP& p, const GemmPlan& pl, hipStream_t stream);
 bool pn_plan(const GP& p, int batch, int ly, GemmPlan* pl);     // gemm_bf16_pn.hip
 int pn_launch(const GP& p, const GemmPlan& pl, hipStream_t stream);
-bool g8_plan(const GP& p, int batch, int ly, GemmPlan* pl);     // gemm_bf16_8p.hip: G8, G8_TN, G8_TN3
+bool g8_plan(const GP& p, int batch, int ly, GemmPlan* pl);     // gemm_bf16_8p.hip: G8, and G8_TN / G8_TN3 through g8_tn_plan
 int g8_launch(const GP& p, const GemmPlan& pl, hipStream_t stream);
+bool g8_tn_plan(const GP& p, int batch, GemmPlan* pl);          // gemm_bf16_tn.hip: G8_TN, G8_TN3
+int g8_tn_launch(const GP& p, const GemmPlan& pl, hipStream_t stream);
 bool tt_plan(const GP& p, int batch, int ly, GemmPlan* pl);     // gemm_bf16_tt.hip
 int tt_launch(const GP& p, const GemmPlan& pl, hipStream_t stream);

@@ -503,7 +503,7 @@ int a3t_gemm_pn_mode(int mode);
  * (A3T_GEMM_TT). */
 int a3t_gemm_tt_mode(int mode);
 /* Weight gradients (token reductions, multi_layer_conv.py:52-63 / torch.nn.Linear backward): 0 = never use the 128 x 384-tile
- * 8-phase kernel with the deterministic split-K fold, 1 = whenever the descriptor is legal for it, 2 (default) = when its tiles
+ * 8-phase kernel (csrc/gemm_bf16_tn.hip) with the deterministic split-K fold, 1 = whenever the descriptor is legal for it, 2 (default) = when its tiles
  * cover the output to >= 85 % and the launch has >= 96 workgroups, -1 = re-read A3T_GEMM_8P_TN3.  Returns the previous mode.
  * (a3t_gemm_8p_mode(0) switches it off together with every other 8-phase kernel.) */
 int a3t_gemm_tn3_mode(int mode);

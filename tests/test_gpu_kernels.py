@@ -895,6 +895,62 @@ def test_grouped_linear_weight_gradients_equal_the_single_launches():
         lib.a3t_gemm_tn3_mode(old3)
 
 
+def test_token_reduction_tiles_share_one_loader_and_one_fold():
+    """Both token-reduction kernels (gemm_bf16_tn.hip: 256 x 256 and 128 x 384 tiles on one loader) and their one fold kernel on
+    small shapes with every kind of edge: 3 x 701 tokens (no multiple of the 64-token K-tile or of T, 33 K-tiles = 2 K splits ->
+    slab + fold), cout = 264 (a row tile whose second 128-row half holds 8 rows), cin = 136 (a column half of 8 columns); a conv
+    weight gradient whose 384-column tile spans three taps with utterance boundaries inside K-tiles; and 3 x 200 tokens (one
+    split: the 256 x 256 kernel writes C from its accumulators, no fold).  Each route forced by the mode switches and checked by
+    name; store onto zeros, sole-writer and atomic accumulation onto a random base; run twice: bit-identical; against fp32 torch
+    math at the 1e-4 of the neighbouring tests (fp32 sums of <= 2103 exact bf16 products: restated on the CPU, the fp32
+    reference sits at 1.5e-7 .. 2.5e-7 of the largest element against float64 at these three shapes)."""
+    from a3t_amd import _lib
+    from a3t_amd._lib import ACC_ATOMIC, ACC_SOLE, ACC_STORE, BF16
+    ops = _ops()
+    lib = _lib.load()
+    g = torch.Generator(device=DEV).manual_seed(11)
+    rn = lambda *s: torch.randn(*s, device=DEV, generator=g)
+    old8, old3 = lib.a3t_gemm_8p_mode(1), lib.a3t_gemm_tn3_mode(0)
+    try:
+        for (B, T, cin, cout, taps) in [(3, 701, 136, 264, 1), (3, 701, 128, 136, 3), (3, 200, 136, 264, 1)]:
+            M = B * T
+            dy, x = rn(M, cout).bfloat16(), rn(M, cin).bfloat16()
+            xs, dyf = x.float().view(B, T, cin), dy.float().view(B, T, cout)
+            ref = torch.zeros(cout, taps, cin, device=DEV)
+            for t in range(taps):
+                sh = t - (taps // 2)
+                xsft = torch.zeros_like(xs)
+                if sh < 0:
+                    xsft[:, -sh:] = xs[:, :sh]
+                elif sh > 0:
+                    xsft[:, :-sh] = xs[:, sh:]
+                else:
+                    xsft = xs
+                ref[:, t, :] = 0.5 * torch.einsum("btn,btc->nc", dyf, xsft)
+            sc = float(ref.abs().max())
+            base = rn(cout, taps, cin)
+
+            def run(acc, start):
+                dW = start.clone()
+                ops.gemm(dy, x, dW, cout, taps * cin, M, 1, cout, 1, cin, taps * cin, taps=taps, pad=taps // 2, Tseq=T if taps > 1 else 0,
+                         alpha=0.5, acc=acc, compute=BF16)
+                return dW, lib.a3t_gemm_last_kernel().decode()
+            for tn3, want in ((0, "gemm_bf16_8p_tn_kernel"), (1, "gemm_bf16_8p_tn3_kernel")):
+                lib.a3t_gemm_tn3_mode(tn3)
+                for acc, start, target in ((ACC_STORE, torch.zeros_like(ref), ref), (ACC_SOLE, base, base + ref), (ACC_ATOMIC, base, base + ref)):
+                    d1, k1 = run(acc, start)
+                    d2, _ = run(acc, start)
+                    torch.cuda.synchronize()
+                    assert k1 == "%s<%s>" % (want, "true" if taps > 1 else "false"), (k1, want)
+                    err = float((d1 - target).abs().max()) / sc
+                    print(f"B*T={M} cin={cin} cout={cout} taps={taps} {k1} acc={acc}: max error / max |ref| = {err:.3g}")
+                    assert torch.equal(d1, d2), (k1, acc)
+                    assert err < 1e-4, (k1, acc, err)
+    finally:
+        lib.a3t_gemm_8p_mode(old8)
+        lib.a3t_gemm_tn3_mode(old3)
+
+
 def test_bf16_output_accumulates_in_fp32_with_one_rounding_and_keeps_its_own_column_sum():
     """Round 6: A3T_ACC_ADD on a bf16 C (the second attention product adds d(q+v) onto d(q+u) in the q third of dqkv): the sum is
     formed in fp32 from the stored bf16 value and rounded once; the fused column sum takes the INCREMENT alone (the bias gradient

@@ -174,7 +174,10 @@ def test_gemm_register_budget():
     path = path.replace("gemm_bf16.resources.json", "gemm_bf16_8p.resources.json")
     rows = json.load(open(path))
     assert len(rows) >= 2
-    for name, r in rows.items():
+    # ... and so do the token reductions of the same family (gemm_bf16_tn.hip: four kernel instantiations and their two folds)
+    tn_rows = json.load(open(path.replace("gemm_bf16_8p.resources.json", "gemm_bf16_tn.resources.json")))
+    assert sum("8p_tn" in name and "fold" not in name for name in tn_rows) == 4 and sum("fold" in name for name in tn_rows) == 2
+    for name, r in list(rows.items()) + list(tn_rows.items()):
         assert r["ScratchSize [bytes/lane]"] == 0 and r["VGPRs"] <= 256, (name, r["VGPRs"])
         assert r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, (name, r)
     # the 384-column panel kernel: same discipline (one 512-thread workgroup per CU, counted vmcnt waits in the K loop): no
@@ -304,7 +307,7 @@ def test_token_reduction_kernels_keep_their_register_footprint_and_their_dma_pip
     import subprocess
     import tempfile
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = os.path.join(root, "a3t_amd", "lib", "gemm_bf16_8p.resources.json")
+    res = os.path.join(root, "a3t_amd", "lib", "gemm_bf16_tn.resources.json")
     if not os.path.exists(res):
         pytest.skip("library not built by a3t_amd.build in this tree")
     rows = json.load(open(res))
@@ -318,7 +321,7 @@ def test_token_reduction_kernels_keep_their_register_footprint_and_their_dma_pip
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
         subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
-                               "-o", out, os.path.join(root, "a3t_amd", "csrc", "gemm_bf16_8p.hip")], stderr=subprocess.DEVNULL)
+                               "-o", out, os.path.join(root, "a3t_amd", "csrc", "gemm_bf16_tn.hip")], stderr=subprocess.DEVNULL)
         lines = open(out).read().splitlines()
     starts = [(i, l.split(":")[0]) for i, l in enumerate(lines) if re.match(r"^_Z\d+gemm_bf16_8p_tn3?_kernelILb[01]E", l)]
     assert len(starts) == 4, [s for _, s in starts]

@@ -1,4 +1,4 @@
-"""8-phase TN kernel (weight gradients) vs the 128x128 kernel and torch; timing at the benchmark shapes."""
+"""8-phase TN kernel (weight gradients, csrc/gemm_bf16_tn.hip) vs the 128x128 kernel and torch; timing at the benchmark shapes."""
 import sys
 import torch
 from a3t_amd import _lib, ops

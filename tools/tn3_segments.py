@@ -1,5 +1,5 @@
 """Where a K-tile of the 128 x 384 token-reduction kernel spends its cycles: reads the segment timers of an instrumented build
-(hipcc -DG8_TIMING [-DG8_TIMING_D] on gemm_bf16_8p.hip, linked to tools/ab/liba3t_hip_tn3_timing[_d].so; A3T_LIB_PATH selects it).
+(hipcc -DG8_TIMING [-DG8_TIMING_D] on gemm_bf16_tn.hip, linked to tools/ab/liba3t_hip_tn3_timing[_d].so; A3T_LIB_PATH selects it).
 Slots per phase p = 0..2: 4p+0 load segment up to the first barrier (only with G8_TIMING_D: the stamp forces the fragment reads
 home), 4p+1 first barrier + lgkmcnt(0) (without _D: the whole load segment too), 4p+2 the 16 MFMAs' issue, 4p+3 second barrier."""
 import ctypes, os, sys

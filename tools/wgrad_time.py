@@ -1,4 +1,4 @@
-"""The fused conv weight gradients of configs[1] alone (A3T_LIB_PATH selects an instrumented library)."""
+"""The fused conv weight gradients of configs[1] alone (the token reductions of csrc/gemm_bf16_tn.hip; A3T_LIB_PATH selects an instrumented library)."""
 import os
 import sys
 
