@@ -667,6 +667,67 @@ def pwg_block_f16(x_in, x_out, cu16, w0h, b0, w1h, b1, skips, tiles, B, Tw, dil)
                                        _ptr(skips), _ptr(tiles), nt, B, Tw, dil, _stream()), "pwg_block_f16")
 
 
+def leaky_relu(x, y, slope):
+    """y = x > 0 ? x : x * slope (a3t_leaky_relu), contiguous fp32 of the same size; y may be x."""
+    _ragged_f32("leaky_relu", x, y)
+    if x.numel() != y.numel():
+        raise ValueError("leaky_relu: x and y must have the same size")
+    L.check(L.load().a3t_leaky_relu(_ptr(x), _ptr(y), x.numel(), slope, _stream()), "leaky_relu")
+
+
+def _hfg_tiles(what, tiles, B, Tw):
+    """(pointer, ntiles) of an optional tile list (vocoder.pwg_tile_list) for B rows of Tw samples; ntiles < 0: nothing to do."""
+    if tiles is None:
+        return None, 0
+    if tiles.dim() != 2 or tiles.shape[1] != 4:
+        raise ValueError(f"{what}: tiles must be (ntiles, 4), got {tuple(tiles.shape)}")
+    if tiles.shape[0] > B * ((Tw + 255) // 256):
+        raise ValueError(f"{what}: {tiles.shape[0]} tiles do not fit {B} rows of {Tw} samples")
+    _i32(tiles, "tiles")
+    if tiles.shape[0] == 0:      # (an empty tensor has no address: NULL would mean "dense")
+        return None, -1
+    return _ptr(tiles), tiles.shape[0]
+
+
+def hfg_conv(x, wt, bias, y, B, Tw, dil, slope, R=None, acc=None, alpha=1.0, acc_add=False, tiles=None):
+    """One HiFi-GAN residual-unit convolution (a3t_hfg_conv): v = bias + conv(leaky(x, slope)) (+ R); y = v (y may be None) and
+    acc = alpha * v or, with acc_add, acc += alpha * v (acc may be None).  x / R / y / acc fp32 [B*Tw][C], C in {32, 64};
+    wt [taps*C][C] k-major (vocoder.pack_hifigan_conv), taps odd <= 11.  R may be y; x must overlap neither y nor acc (checked here).
+    tiles: as pwg_block, the kernel trusts the list's entries."""
+    C = x.shape[-1]
+    if wt.dim() != 2 or wt.shape[1] != C or wt.shape[0] % C:
+        raise ValueError(f"hfg_conv: wt must be [taps*{C}][{C}], got {tuple(wt.shape)}")
+    for name, t in (("x", x), ("R", R), ("y", y), ("acc", acc)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != C or t.numel() != B * Tw * C):
+            raise ValueError(f"hfg_conv: {name} must be a contiguous fp32 [{B * Tw}][{C}] tensor")
+    nbytes = 4 * B * Tw * C
+    for name, t in (("y", y), ("acc", acc)):      # other tiles read x[t +- halo]: no output may overlap the input, or the other
+        for oname, o in (("x", x), ("acc", acc if name == "y" else None)):
+            if t is not None and o is not None and abs(t.data_ptr() - o.data_ptr()) < nbytes:
+                raise ValueError(f"hfg_conv: {name} overlaps {oname}")
+    _ragged_f32("hfg_conv", wt, bias)
+    if bias is not None and bias.numel() != C:
+        raise ValueError(f"hfg_conv: bias must have {C} entries")
+    tp, nt = _hfg_tiles("hfg_conv", tiles, B, Tw)
+    if nt < 0:
+        return
+    L.check(L.load().a3t_hfg_conv(_ptr(x), _ptr(wt), _ptr(bias), _ptr(R), _ptr(y), _ptr(acc), alpha, int(bool(acc_add)), slope,
+                                  tp, nt, B, Tw, C, wt.shape[0] // C, dil, _stream()), "hfg_conv")
+
+
+def hfg_out(x, w, bias, y, B, Tw, slope, tiles=None):
+    """y [B*Tw] = tanh(bias + conv_K(leaky(x, slope))) (a3t_hfg_out): x fp32 [B*Tw][C], w [K][C] (tap, in channel), bias [1] or
+    None.  tiles: as hfg_conv."""
+    C = x.shape[-1]
+    _ragged_f32("hfg_out", x, w, bias, y)
+    if w.dim() != 2 or w.shape[1] != C or x.numel() != B * Tw * C or y.numel() != B * Tw:
+        raise ValueError("hfg_out: shapes do not fit")
+    tp, nt = _hfg_tiles("hfg_out", tiles, B, Tw)
+    if nt < 0:
+        return
+    L.check(L.load().a3t_hfg_out(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), slope, tp, nt, B, Tw, C, w.shape[0], _stream()), "hfg_out")
+
+
 def splice_spans(after, speech, speech_mask, spans, out, lens):
     """out[b][t] = after[b][t] inside spans[b], speech[b][t] for the other valid frames, 0 behind the row's length (the sum of
     its speech_mask, written to lens).  after / speech [B][Tin][C] fp32, speech_mask [B][Tin] bool / uint8, out [B][Tout][C]."""

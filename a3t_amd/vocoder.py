@@ -7,6 +7,8 @@ the network restated is the vendored twin ``ParallelWaveGANGenerator``
 parallel_wavegan/upsample.py:22-189), weight-norm removed.  Layout is channels-last [T][C] so every
 Conv1d (dilated k=3, 1x1) is the shared implicit-im2col MFMA GEMM; the gated activation, residual /
 skip update and nearest-neighbour upsampling+smoothing are element-wise HIP kernels.
+
+HiFiGANGeneratorHIP (below) is the second generator family of the same model zoo, with the same inference interface.
 """
 import math
 import os
@@ -16,7 +18,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import ACT_RELU, F32
+from ._lib import ACT_RELU, ACT_TANH, F32
 
 
 def pwg_margin_frames(layers=30, stacks=3, kernel_size=3, upsample_scales: Sequence[int] = (4, 5, 3, 5),
@@ -267,5 +269,309 @@ class ParallelWaveGANGeneratorHIP:
     def margin_frames(self) -> int:
         """pwg_margin_frames of this generator's configuration (kernel size 3: the only one the class builds)."""
         return pwg_margin_frames(self.layers, self.stacks, 3, self.scales, self.ctx)
+
+    __call__ = inference
+
+
+# ---------------------------------------------------------------------------------------------------- HiFi-GAN generator
+def hifigan_margin_frames(upsample_scales: Sequence[int] = (5, 5, 4, 3), resblock_kernel_sizes: Sequence[int] = (3, 7, 11),
+                          resblock_dilations=((1, 3, 5),) * 3, kernel_size: int = 7, use_additional_convs: bool = True) -> int:
+    """pwg_margin_frames for the HiFi-GAN generator.  Walked from the output back to the mel: the output convolution reaches
+    (K-1)/2 samples; the residual blocks of stage i max_j sum_d (k_j-1)/2 * (d + 1) samples of stage i (+ 1: the additional
+    convolution of dilation 1; without it sum_d (k_j-1)/2 * d); a transposed convolution of scale s turns a reach of n output
+    samples into ceil(n / s) + 1 input samples (output q*s + r reads inputs q-1 .. q+1); the input convolution adds (K-1)/2
+    frames.  20 for the 24 kHz v1 plan (5, 5, 4, 3) x (3, 7, 11) x (1, 3, 5), K = 7 (a probe of a model of that plan: 19
+    reproduces the span, 18 does not: the ceil of each stage is what the formula gives away)."""
+    extra = 1 if use_additional_convs else 0
+    reach = max(sum((int(k) - 1) // 2 * (int(d) + extra) for d in dils)
+                for k, dils in zip(resblock_kernel_sizes, resblock_dilations))
+    n = (int(kernel_size) - 1) // 2
+    for s in reversed([int(s) for s in upsample_scales]):
+        n = -(-(n + reach) // s) + 1
+    return n + (int(kernel_size) - 1) // 2
+
+
+def fold_weight_norm(state_dict, prefix: str) -> torch.Tensor:
+    """`prefix`.weight of a state dict as fp32, from the plain tensor or from weight_g / weight_v (torch.nn.utils.weight_norm
+    with its default dim = 0: w = g * v / ||v||, the norm over all dims but the first -- for a ConvTranspose1d [Cin][Cout][k]
+    that is dims 1, 2), folded in fp64."""
+    if prefix + ".weight" in state_dict:
+        return torch.as_tensor(np.asarray(state_dict[prefix + ".weight"]), dtype=torch.float32)
+    g = torch.as_tensor(np.asarray(state_dict[prefix + ".weight_g"]), dtype=torch.float64)
+    v = torch.as_tensor(np.asarray(state_dict[prefix + ".weight_v"]), dtype=torch.float64)
+    norm = v.flatten(1).norm(dim=1).reshape(-1, *([1] * (v.dim() - 1)))
+    return (g * v / norm).to(torch.float32)
+
+
+def pack_hifigan_upsample(w: torch.Tensor, scale: int) -> torch.Tensor:
+    """ConvTranspose1d(k = 2s, stride s, padding = ceil(s/2), output_padding = s % 2) as a 3-tap stride-1 convolution with
+    N = s * Cout output columns (pure; any dtype).  w [Cin][Cout][2s] -> Wk [s*Cout][3][Cin] for ops.conv_fwd(pad=1): output
+    sample q*s + r, channel co (column r*Cout + co) reads input q + t - 1 through w[:, co, (1 - t)*s + r + ceil(s/2)], zero where
+    that index leaves [0, 2s).  The [B*T][s*Cout] result is the [B*T*s][Cout] tensor."""
+    s = int(scale)
+    Cin, Cout, k = w.shape
+    if k != 2 * s:
+        raise ValueError(f"pack_hifigan_upsample: kernel size {k} is not 2 * scale {s}")
+    p = (s + 1) // 2
+    Wk = torch.zeros(s, Cout, 3, Cin, dtype=w.dtype, device=w.device)
+    for t in range(3):
+        for r in range(s):
+            i = (1 - t) * s + r + p
+            if 0 <= i < k:
+                Wk[r, :, t, :] = w[:, :, i].t()
+    return Wk.reshape(s * Cout, 3, Cin).contiguous()
+
+
+def pack_hifigan_conv(w: torch.Tensor) -> torch.Tensor:
+    """Conv1d weight [Cout][Cin][k] -> the k-major operand of a3t_hfg_conv [k*Cin][Cout] (row = tap*Cin + in channel)."""
+    Cout, Cin, k = w.shape
+    return w.permute(2, 1, 0).reshape(k * Cin, Cout).contiguous()
+
+
+class HiFiGANGeneratorHIP:
+    """HiFi-GAN generator inference (espnet2/gan_tts/hifigan/hifigan.py:25-221, state-dict compatible with the
+    parallel_wavegan zoo's HiFiGANGenerator), channels-last fp32 [B*T][C] on the device.
+
+    fused=False: layer by layer -- a3t_leaky_relu in front of every convolution, every convolution (the transposed ones as
+    3-tap convolutions, pack_hifigan_upsample) on the exact-fp32 GEMM.  fused=True: the residual blocks of the stages with 32 or
+    64 channels run on a3t_hfg_conv (LeakyReLU, bias, residual and the MRF mean inside the launch) and the output convolution
+    on a3t_hfg_out; stages of another width run layer by layer.  fused=True is the default because it is the faster path on the v1
+    plan (profiles/hifigan_latency.txt: 46 ms against 83 ms for 8 x 1000 frames)."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", in_channels=80, channels=512, kernel_size=7,
+                 upsample_scales: Sequence[int] = (5, 5, 4, 3), upsample_kernel_sizes: Sequence[int] = (10, 10, 8, 6),
+                 resblock_kernel_sizes: Sequence[int] = (3, 7, 11), resblock_dilations=((1, 3, 5),) * 3,
+                 use_additional_convs=True, bias=True, negative_slope=0.1, stats: Optional[Dict[str, np.ndarray]] = None,
+                 fused=True):
+        self.scales = tuple(int(s) for s in upsample_scales)
+        self.rk = tuple(int(k) for k in resblock_kernel_sizes)
+        self.rd = tuple(tuple(int(d) for d in ds) for ds in resblock_dilations)
+        if kernel_size % 2 == 0:
+            raise ValueError(f"kernel_size {kernel_size} must be odd")
+        if any(k % 2 == 0 for k in self.rk):
+            raise ValueError(f"resblock_kernel_sizes {list(self.rk)} must be odd")
+        if len(upsample_kernel_sizes) != len(self.scales) or any(int(k) != 2 * s for k, s in zip(upsample_kernel_sizes, self.scales)):
+            raise ValueError(f"upsample_kernel_sizes {list(upsample_kernel_sizes)} must be twice upsample_scales {list(self.scales)}")
+        if len(self.rk) != len(self.rd):
+            raise ValueError("resblock_dilations must have one list per entry of resblock_kernel_sizes")
+        if channels % (2 ** len(self.scales)):
+            raise ValueError(f"channels {channels} must be divisible by 2^{len(self.scales)}")
+        self.dev = torch.device(device)
+        self.A, self.C0, self.K = int(in_channels), int(channels), int(kernel_size)
+        self.add, self.slope = bool(use_additional_convs), float(negative_slope)
+        self.upsample_factor = int(np.prod(self.scales))
+        self.stats = None
+        if stats is not None:     # normalize_before of the pretrained wrapper (c - mean) / scale
+            self.stats = (torch.as_tensor(stats["mean"], dtype=torch.float32, device=self.dev),
+                          torch.as_tensor(stats["scale"], dtype=torch.float32, device=self.dev))
+
+        def w(p):
+            return fold_weight_norm(state_dict, p)
+
+        def b(p, n, rep=1):
+            if not bias and p + ".bias" not in state_dict:
+                return None
+            v = torch.as_tensor(np.asarray(state_dict[p + ".bias"]), dtype=torch.float32)
+            if v.numel() != n:
+                raise ValueError(f"{p}.bias has {v.numel()} entries, expected {n}")
+            return v.repeat(rep).contiguous().to(self.dev)
+
+        def conv(t):              # (out, in, taps) -> [out][tap][in]
+            return t.permute(0, 2, 1).contiguous().to(self.dev)
+
+        self.w_in, self.b_in = conv(w("input_conv")), torch.as_tensor(np.asarray(state_dict["input_conv.bias"]),
+                                                                      dtype=torch.float32).to(self.dev)
+        if tuple(self.w_in.shape) != (self.C0, self.K, self.A):
+            raise ValueError(f"input_conv.weight {tuple(self.w_in.shape)} does not fit channels / kernel_size / in_channels")
+        self.stages = []
+        for i, s in enumerate(self.scales):
+            C = self.C0 >> (i + 1)
+            st = dict(C=C, s=s, w_up=pack_hifigan_upsample(w(f"upsamples.{i}.1"), s).to(self.dev),
+                      b_up=torch.as_tensor(np.asarray(state_dict[f"upsamples.{i}.1.bias"]), dtype=torch.float32).repeat(s).to(self.dev),
+                      fused=bool(fused) and C in (32, 64) and max(self.rk) <= 11, blocks=[])
+            for j, (k, dils) in enumerate(zip(self.rk, self.rd)):
+                units = []
+                for d in range(len(dils)):
+                    p = f"blocks.{i * len(self.rk) + j}."
+                    names = [p + f"convs1.{d}.1"] + ([p + f"convs2.{d}.1"] if self.add else [])
+                    ws = [w(n) for n in names]
+                    units.append(dict(dil=dils[d], b=[b(n, C) for n in names],
+                                      w=[(pack_hifigan_conv(t).to(self.dev) if st["fused"] else conv(t)) for t in ws]))
+                st["blocks"].append(dict(k=k, units=units))
+            self.stages.append(st)
+        Cl = self.C0 >> len(self.scales)
+        w_out = w("output_conv.1")
+        if tuple(w_out.shape) != (1, Cl, self.K):
+            raise NotImplementedError(f"out_channels: output_conv.1.weight {tuple(w_out.shape)} is not (1, {Cl}, {self.K})")
+        self.w_out = conv(w_out)                                      # [1][K][Cl]
+        self.b_out = torch.as_tensor(np.asarray(state_dict["output_conv.1.bias"]), dtype=torch.float32).to(self.dev)
+        self.fused_out = bool(fused) and Cl <= 64 and Cl % 4 == 0 and self.K <= 11
+        self.fused = any(st["fused"] for st in self.stages)
+
+    @classmethod
+    def from_config(cls, state_dict, generator_params: Dict, generator_type: str = "HiFiGANGenerator", **kw):
+        """From the `generator_params` (and `generator_type`) of a parallel_wavegan config.yml and the checkpoint's
+        model["generator"] state dict.  kw: device, stats, fused."""
+        if generator_type != "HiFiGANGenerator":
+            raise NotImplementedError(f"generator_type {generator_type!r}: only HiFiGANGenerator is built here")
+        p = dict(generator_params)
+        if int(p.pop("out_channels", 1)) != 1:
+            raise NotImplementedError("out_channels != 1 is not supported (no multi-band / PQMF synthesis)")
+        if int(p.pop("global_channels", -1)) > 0:
+            raise NotImplementedError("global_channels > 0 (global conditioning) is not supported")
+        act = p.pop("nonlinear_activation", "LeakyReLU")
+        if act != "LeakyReLU":
+            raise NotImplementedError(f"nonlinear_activation {act!r}: only LeakyReLU is built into the kernels")
+        if p.pop("use_causal_conv", False):
+            raise NotImplementedError("use_causal_conv is not supported")
+        ap = dict(p.pop("nonlinear_activation_params", None) or {"negative_slope": 0.1})
+        p.pop("use_weight_norm", None)      # the state dict says which form it holds
+        if "upsample_kernal_sizes" in p:    # (the zoo's older configs spell it so)
+            p["upsample_kernel_sizes"] = p.pop("upsample_kernal_sizes")
+        known = ("in_channels", "channels", "kernel_size", "upsample_scales", "upsample_kernel_sizes", "resblock_kernel_sizes",
+                 "resblock_dilations", "use_additional_convs", "bias")
+        unknown = sorted(set(p) - set(known))
+        if unknown:
+            raise NotImplementedError(f"generator_params {unknown} are not understood")
+        return cls(state_dict, negative_slope=float(ap.get("negative_slope", 0.01)), **p, **kw)
+
+    @property
+    def margin_frames(self) -> int:
+        return hifigan_margin_frames(self.scales, self.rk, self.rd, self.K, self.add)
+
+    def _lrelu(self, x, slope=None):
+        y = torch.empty_like(x)
+        ops.leaky_relu(x, y, self.slope if slope is None else slope)
+        return y
+
+    @torch.no_grad()
+    def inference(self, c: torch.Tensor, z: Optional[torch.Tensor] = None, normalize_before: bool = False,
+                  lengths: Optional[Sequence[int]] = None):
+        """c (T_feats, aux) [or (B, T_feats, aux)] -> (T_wav, 1) [or (B, T_wav, 1)]; z must be None (HiFi-GAN has no noise input).
+
+        lengths (host integers, one per row of a (B, Tmax, aux) batch): row b is computed exactly as if c[b, :L_b] had been
+        passed alone -- every convolution reads zeros behind the row's end at its own rate and stores zeros there -- and the
+        result (B, Tmax * hop, 1) is zero behind L_b * hop.  What the padding of c holds reaches no valid sample."""
+        if z is not None:
+            raise ValueError("HiFiGANGeneratorHIP.inference: z must be None, the HiFi-GAN generator has no noise input")
+        single = (c.dim() == 2)
+        c = c.to(self.dev, torch.float32)
+        if single:
+            c = c[None]
+        B, Tf, A = c.shape
+        if A != self.A:
+            raise ValueError(f"c has {A} channels, the generator {self.A}")
+        if normalize_before and self.stats is not None:
+            c = (c - self.stats[0]) / self.stats[1]
+        if lengths is not None and single:
+            raise ValueError("lengths= goes with a (B, Tmax, aux) batch")
+        dev = self.dev
+        lens, tiles = None, {}
+        if lengths is not None:
+            lengths = [int(x) for x in lengths]
+            if len(lengths) != B or any(n < 0 or n > Tf for n in lengths):
+                raise ValueError(f"lengths {lengths} do not fit a batch of {B} rows of {Tf} frames")
+            # one H2D copy: lens [B] | one tile list per fused rate (offsets kept 16-byte aligned)
+            rates, r = [], 1
+            for st in self.stages:
+                r *= st["s"]
+                if st["fused"]:
+                    rates.append(r)
+            if self.fused_out and r not in rates:
+                rates.append(r)
+            lists = [pwg_tile_list(lengths, r) for r in rates]
+            off = (B + 3) // 4 * 4
+            host = np.zeros(off + sum(tl.size for tl in lists), dtype=np.int32)
+            host[:B] = lengths
+            o = off
+            for tl in lists:
+                host[o:o + tl.size] = tl.reshape(-1)
+                o += tl.size
+            meta, o = torch.from_numpy(host).to(dev), off
+            lens = meta[:B]
+            for r, tl in zip(rates, lists):
+                tiles[r] = meta[o:o + tl.size].view(len(tl), 4)
+                o += tl.size
+
+        def tail(x, rate, T):
+            if lens is not None:
+                ops.zero_tail(x, lens, rate, B, T)
+
+        c = c.contiguous()
+        if lens is not None:      # (a copy: c may be the caller's tensor)
+            c = c.clone()
+            tail(c, 1, Tf)
+        x = torch.empty(B * Tf, self.C0, device=dev)
+        ops.conv_fwd(c.view(B * Tf, A), self.w_in, x, Tf, (self.K - 1) // 2, bias=self.b_in, compute=F32)
+        tail(x, 1, Tf)
+        T, rate = Tf, 1
+        for st in self.stages:
+            C, s = st["C"], st["s"]
+            up = torch.empty(B * T, s * C, device=dev)
+            ops.conv_fwd(self._lrelu(x), st["w_up"], up, T, 1, bias=st["b_up"], compute=F32)
+            T, rate = T * s, rate * s
+            up = up.view(B * T, C)
+            tail(up, rate, T)
+            run = self._stage_fused if st["fused"] else self._stage_layers
+            x = run(st, up, B, T, rate, lens, tiles.get(rate))
+        wav = torch.empty(B * T, 1, device=dev)
+        if self.fused_out:
+            if lens is not None:      # the kernel writes no sample behind a row's end
+                wav.zero_()
+            ops.hfg_out(x, self.w_out.view(self.K, -1), self.b_out, wav, B, T, 0.01, tiles.get(rate))
+        else:
+            ops.conv_fwd(self._lrelu(x, 0.01), self.w_out, wav, T, (self.K - 1) // 2, bias=self.b_out, act=ACT_TANH, compute=F32)
+            tail(wav, rate, T)
+        wav = wav.view(B, T, 1)
+        return wav[0] if single else wav
+
+    def _stage_layers(self, st, up, B, T, rate, lens, tiles):
+        """The residual blocks of one stage and their mean, layer by layer: (sum_j block_j(up)) / num_blocks, the division
+        deliberately as one multiplication by fp32(1 / num_blocks) (a3t_scale): at most one ulp from the reference's quotient."""
+        bufs = [torch.empty_like(up) for _ in range(3)]
+        cs = torch.empty_like(up)
+        for j, blk in enumerate(st["blocks"]):
+            pad, x = (blk["k"] - 1) // 2, up
+            for u, unit in enumerate(blk["units"]):
+                xn, xt = bufs[u % 2], bufs[2]
+                if self.add:
+                    ops.conv_fwd(self._lrelu(x), unit["w"][0], xt, T, pad, unit["dil"], bias=unit["b"][0], compute=F32)
+                    if lens is not None:
+                        ops.zero_tail(xt, lens, rate, B, T)
+                    ops.conv_fwd(self._lrelu(xt), unit["w"][1], xn, T, pad, 1, bias=unit["b"][1], R=x, compute=F32)
+                else:
+                    ops.conv_fwd(self._lrelu(x), unit["w"][0], xn, T, pad, unit["dil"], bias=unit["b"][0], R=x, compute=F32)
+                if lens is not None:
+                    ops.zero_tail(xn, lens, rate, B, T)
+                x = xn
+            if j == 0:
+                cs.copy_(x)
+            else:
+                ops.axpy(x, cs, 1.0)
+        ops.scale(cs, cs, 1.0 / len(st["blocks"]))
+        return cs
+
+    def _stage_fused(self, st, up, B, T, rate, lens, tiles):
+        """The same on a3t_hfg_conv: the last convolution of block j leaves alpha * block_j in the mean's buffer (alpha =
+        1 / num_blocks), so block outputs are never stored.  Rows behind a row's end are not written by the kernel: the mean's
+        buffer starts as zeros there for the (unragged) convolution that reads it next."""
+        bufs = [torch.empty_like(up) for _ in range(3)]
+        cs = torch.zeros_like(up) if lens is not None else torch.empty_like(up)
+        alpha = 1.0 / len(st["blocks"])
+        for j, blk in enumerate(st["blocks"]):
+            x = up
+            for u, unit in enumerate(blk["units"]):
+                xn, xt = bufs[u % 2], bufs[2]
+                if u == len(blk["units"]) - 1:
+                    out = dict(y=None, acc=cs, alpha=alpha, acc_add=j > 0)
+                else:
+                    out = dict(y=xn)
+                src, dil = x, unit["dil"]
+                if self.add:
+                    ops.hfg_conv(x, unit["w"][0], unit["b"][0], xt, B, T, dil, self.slope, tiles=tiles)
+                    src, dil = xt, 1
+                ops.hfg_conv(src, unit["w"][-1], unit["b"][-1], out.pop("y"), B, T, dil, self.slope, R=x, tiles=tiles, **out)
+                x = xn
+        return cs
 
     __call__ = inference

@@ -476,6 +476,27 @@ int a3t_pwg_block_f16(const float* x_in, float* x_out, const void* cu16, const v
 /* dst[i] = fp16(src[i]), round to nearest even, saturated to +-65504; both 16-byte aligned. */
 int a3t_cast_f16_sat(const float* src, void* dst, int64_t n, void* stream);
 
+/* HiFi-GAN generator kernels (espnet2/gan_tts/hifigan/hifigan.py:25-221, residual_block.py:17-99; csrc/hifigan.hip), fp32
+ * channels-last [B*Tw][C].  leaky(v) = v > 0 ? v : v * slope.
+ * a3t_hfg_conv: one residual-unit convolution of a narrow stage, C in = C out = C in {32, 64}, taps odd <= 11, dil >= 1:
+ *   v[t] = bias + sum_{tap,c} wt[tap*C + c][:] * leaky(x[t + (tap - (taps-1)/2) * dil][c]) (+ R[t]),  zero padding per row;
+ *   y[t] = v[t] when y is given, and when acc is given acc[t] = alpha * v[t] (acc_add == 0) or acc[t] += alpha * v[t].
+ *   wt [taps*C][C] k-major (row = tap*C + in channel, column = out channel); bias [C], R, y, acc may be NULL (y or acc must be
+ *   given).  R may alias y; x must be neither y nor acc (a tile reads x[t +- halo] of other tiles).  Exact fp32 products
+ *   (v_mfma_f32_32x32x2f32).  tiles == NULL (and ntiles == 0): every row is Tw samples long; else the tile list of
+ *   a3t_pwg_block_ragged with its rules (a tap at ts is zero unless 0 <= ts < W_b; rows behind W_b are neither read nor
+ *   written).  x, wt and tiles 16-byte aligned.  A sample's result does not depend on its tile or on the other rows.
+ * a3t_hfg_out: y[t] = tanh(bias[0] + sum_{tap,c} w[tap*C + c] * leaky(x[t + tap - (K-1)/2][c])), x [B*Tw][C] -> y [B*Tw];
+ *   C % 4 == 0, C <= 64, K odd <= 11; tiles as above.
+ * a3t_leaky_relu: y[i] = leaky(x[i]) over n floats, in place allowed.
+ * A3T_EINVAL for anything outside these contracts. */
+int a3t_hfg_conv(const float* x, const float* wt, const float* bias, const float* R, float* y, float* acc, float alpha,
+                 int acc_add, float slope, const int32_t* tiles, int ntiles, int B, int Tw, int C, int taps, int dil,
+                 void* stream);
+int a3t_hfg_out(const float* x, const float* w, const float* bias, float* y, float slope, const int32_t* tiles, int ntiles,
+                int B, int Tw, int C, int K, void* stream);
+int a3t_leaky_relu(const float* x, float* y, int64_t n, float slope, void* stream);
+
 /* On-device half of MLMCollateFn (espnet2/train/collate_fn.py:330-385): masked_position, speech / text segment ids and the
  * two padding masks painted from integer span lists.  fs / fe [B][P] int32: frame span of phone j (floor(fs * t / hop) taken
  * on the host in the alignment's dtype, collate_fn.py:236-237); alen [B] phones per utterance; sel [B][P] uint8: phone j is
