@@ -22,8 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/a3t_hip.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "wave_tiles.h"
 
 __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
 
@@ -37,12 +36,10 @@ struct HfgArgs {
     float slope, alpha;
     int acc_add;          // acc += alpha * v, else acc = alpha * v
     int B, Tw, taps, dil, tiles_t;
-    const int4* tiles;    // RAGGED: [ntiles] {row b, first sample t0, valid samples W_b of row b, 0}
+    const int4* tiles;    // RAGGED: [ntiles] tile list (wave_tiles.h)
 };
 
-// RAGGED: the rules of pwg_stage_kernel<STAGE, RAGGED>: row b is valid for W_b <= Tw samples and is computed as if it were
-// alone -- a tap beyond W_b is zero like one beyond the utterance, rows behind W_b are neither loaded nor stored -- and the
-// grid is the host-built list of the tiles that hold valid samples.
+// RAGGED: the tile contract of wave_tiles.h, the grid is the host-built list of the tiles that hold valid samples.
 template <int C, bool RAGGED>
 __global__ __launch_bounds__(256) void hfg_conv_kernel(HfgArgs a) {
     // 4 waves, each 64 samples x C channels: 2 x C/32 accumulator blocks, every A value feeds C/32 MFMAs, every B value two
@@ -51,13 +48,8 @@ __global__ __launch_bounds__(256) void hfg_conv_kernel(HfgArgs a) {
     __shared__ __attribute__((aligned(16))) float Ws[2][BK * C];
 
     const int tid = threadIdx.x, lane = tid & 63, wm = (tid >> 6) * 64, lr = lane & 31, lk = lane >> 5;
-    int b, t0, Wb;
-    if (RAGGED) {
-        const int4 e = a.tiles[blockIdx.x];
-        b = e.x, t0 = e.y, Wb = e.z;
-    } else {
-        b = blockIdx.x / a.tiles_t, t0 = (blockIdx.x - b * a.tiles_t) * TILE, Wb = a.Tw;
-    }
+    const WaveTile at = wave_tile<RAGGED>(a.tiles, blockIdx.x, a.tiles_t, a.Tw);
+    const int b = at.b, t0 = at.t0, Wb = at.Wb;      // (named: the lambdas below capture them)
     const int nch = a.taps * CPT, half = (a.taps - 1) / 2;
     const int t = t0 + tid;                                  // the row this thread stages
     const float* xb = a.x + (int64_t)b * a.Tw * C;
@@ -128,7 +120,7 @@ __global__ __launch_bounds__(256) void hfg_conv_kernel(HfgArgs a) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int tt = t0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int tt = acc32_row(r, lk, t0 + wm + i * 32);
                 if (tt >= Wb) continue;
                 const int64_t idx = ((int64_t)b * a.Tw + tt) * C + col;
                 float v = acc[i][j][r] + bj;
@@ -148,21 +140,16 @@ static int hfg_conv_launch(const HfgArgs& a, int ntiles, void* stream) {
 extern "C" int a3t_hfg_conv(const float* x, const float* wt, const float* bias, const float* R, float* y, float* acc,
                             float alpha, int acc_add, float slope, const int32_t* tiles, int ntiles, int B, int Tw, int C,
                             int taps, int dil, void* stream) {
-    if (!x || !wt || (!y && !acc) || B <= 0 || Tw <= 0 || (C != 32 && C != 64) || taps < 1 || taps > 11 || !(taps & 1) ||
-        dil < 1 || ntiles < 0 || (!tiles && ntiles))
-        return A3T_EINVAL;
+    if (!x || !wt || (!y && !acc) || (C != 32 && C != 64) || taps < 1 || taps > 11 || !(taps & 1) || dil < 1) return A3T_EINVAL;
     if (x == y || x == acc || (y && y == acc)) return A3T_EINVAL;      // other tiles read x[t +- halo]
-    if (((uintptr_t)x | (uintptr_t)wt | (uintptr_t)tiles) & 15) return A3T_EINVAL;
+    if (((uintptr_t)x | (uintptr_t)wt) & 15) return A3T_EINVAL;
+    const int n = wave_grid(tiles, ntiles, B, Tw);
+    if (n <= 0) return n;
     HfgArgs a;
     a.x = x, a.wt = wt, a.bias = bias, a.R = R, a.y = y, a.acc = acc, a.slope = slope, a.alpha = alpha, a.acc_add = acc_add;
-    a.B = B, a.Tw = Tw, a.taps = taps, a.dil = dil, a.tiles_t = (Tw + 255) / 256, a.tiles = (const int4*)tiles;
-    if (tiles) {
-        if (!ntiles) return 0;
-        return C == 32 ? hfg_conv_launch<32, true>(a, ntiles, stream) : hfg_conv_launch<64, true>(a, ntiles, stream);
-    }
-    const int64_t n = (int64_t)B * a.tiles_t;
-    if (n > 0x7fffffff) return A3T_EINVAL;
-    return C == 32 ? hfg_conv_launch<32, false>(a, (int)n, stream) : hfg_conv_launch<64, false>(a, (int)n, stream);
+    a.B = B, a.Tw = Tw, a.taps = taps, a.dil = dil, a.tiles_t = wave_tiles_t(Tw), a.tiles = (const int4*)tiles;
+    if (tiles) return C == 32 ? hfg_conv_launch<32, true>(a, n, stream) : hfg_conv_launch<64, true>(a, n, stream);
+    return C == 32 ? hfg_conv_launch<32, false>(a, n, stream) : hfg_conv_launch<64, false>(a, n, stream);
 }
 
 // ---------------------------------------------------------------- output convolution: C -> 1, LeakyReLU in front, tanh behind
@@ -179,13 +166,7 @@ __global__ __launch_bounds__(256) void hfg_out_kernel(const float* __restrict__ 
     float* Xs = lds;                   // [rows][C + 1]
     float* Wk = lds + rows * ld;       // [K][C]
     const int tid = threadIdx.x;
-    int b, t0, Wb;
-    if (RAGGED) {
-        const int4 e = tiles[blockIdx.x];
-        b = e.x, t0 = e.y, Wb = e.z;
-    } else {
-        b = blockIdx.x / tiles_t, t0 = (blockIdx.x - b * tiles_t) * TILE, Wb = Tw;
-    }
+    const auto [b, t0, Wb] = wave_tile<RAGGED>(tiles, blockIdx.x, tiles_t, Tw);
     const float* xb = x + (int64_t)b * Tw * C;
     for (int i = tid; i < rows * C; i += 256) {
         const int r = i / C, c = i - r * C, ts = t0 - half + r;
@@ -211,24 +192,18 @@ __global__ __launch_bounds__(256) void hfg_out_kernel(const float* __restrict__ 
 
 extern "C" int a3t_hfg_out(const float* x, const float* w, const float* bias, float* y, float slope, const int32_t* tiles,
                            int ntiles, int B, int Tw, int C, int K, void* stream) {
-    if (!x || !w || !y || B <= 0 || Tw <= 0 || C < 4 || C > 64 || (C & 3) || K < 1 || K > 11 || !(K & 1) || ntiles < 0 ||
-        (!tiles && ntiles) || ((uintptr_t)tiles & 15))
-        return A3T_EINVAL;
-    const int lds = ((256 + K - 1) * (C + 1) + K * C) * 4, tiles_t = (Tw + 255) / 256;
-    // more than 64 KiB at C = 64: the limit is raised on every launch (per device and cheap), and a refusal is reported
-    const void* fn = tiles ? (const void*)hfg_out_kernel<true> : (const void*)hfg_out_kernel<false>;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (!x || !w || !y || C < 4 || C > 64 || (C & 3) || K < 1 || K > 11 || !(K & 1)) return A3T_EINVAL;
+    const int n = wave_grid(tiles, ntiles, B, Tw);
+    if (n <= 0) return n;
+    const int lds = ((256 + K - 1) * (C + 1) + K * C) * 4, tiles_t = wave_tiles_t(Tw);      // more than 64 KiB at C = 64
+    const hipError_t e = tiles ? wave_lds_opt_in<hfg_out_kernel<true>>(lds) : wave_lds_opt_in<hfg_out_kernel<false>>(lds);
     if (e != hipSuccess) return (int)e;
-    if (tiles) {
-        if (!ntiles) return 0;
-        hipLaunchKernelGGL(hfg_out_kernel<true>, dim3(ntiles), dim3(256), lds, (hipStream_t)stream, x, w, bias, y, slope, C, K, Tw,
+    if (tiles)
+        hipLaunchKernelGGL(hfg_out_kernel<true>, dim3(n), dim3(256), lds, (hipStream_t)stream, x, w, bias, y, slope, C, K, Tw,
                            tiles_t, (const int4*)tiles);
-    } else {
-        const int64_t n = (int64_t)B * tiles_t;
-        if (n > 0x7fffffff) return A3T_EINVAL;
-        hipLaunchKernelGGL(hfg_out_kernel<false>, dim3((int)n), dim3(256), lds, (hipStream_t)stream, x, w, bias, y, slope, C, K, Tw,
+    else
+        hipLaunchKernelGGL(hfg_out_kernel<false>, dim3(n), dim3(256), lds, (hipStream_t)stream, x, w, bias, y, slope, C, K, Tw,
                            tiles_t, (const int4*)nullptr);
-    }
     return (int)hipGetLastError();
 }
 

@@ -16,8 +16,7 @@
 #include <stdint.h>
 #include "../../include/a3t_hip.h"
 #include "device_cus.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "wave_tiles.h"
 
 struct PwgArgs {
     const float* x_in;    // [B*Tw][64]   stage 0: conv input;  stage 1: residual input (may alias x_out)
@@ -29,13 +28,12 @@ struct PwgArgs {
     float* x_out;         // stage 1 out
     float* skips;         // stage 1 accumulate
     int B, Tw, dil, tiles_t;
-    const int4* tiles;    // RAGGED: [ntiles] {row b, first sample t0, valid samples W_b of row b, 0}: the tiles that hold valid samples
+    const int4* tiles;    // RAGGED: [ntiles] tile list (wave_tiles.h)
     int ntiles;           // RAGGED: entries of `tiles`
 };
 
-// RAGGED: row b is valid for W_b <= Tw samples and is computed as if it were alone: a tap beyond W_b is zero like one beyond
-// the utterance, rows behind W_b are neither loaded, computed nor stored, and the persistent loop walks the host-built list of
-// the tiles that hold valid samples instead of all B * tiles_t (one uniform 16-byte load per tile and walker).
+// RAGGED: the tile contract of wave_tiles.h; the persistent loop walks the host-built list of the tiles that hold valid
+// samples instead of all B * tiles_t (one uniform 16-byte load per tile and walker).
 template <int STAGE, bool RAGGED>
 __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
     // 8 waves = 4 (rows) x 2 (columns), each a 64 x 64 sub-tile of the 256-sample tile: two waves per SIMD, so one wave's
@@ -56,15 +54,13 @@ __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
     // tile index -> row, first sample and the row's valid length.  RAGGED: the list entry is fetched when the tile index
     // changes, not per chunk (the chunk requests and the MFMA loop each walk the tiles in order, so each keeps its last entry
     // instead of putting a uniform load and its wait in front of every chunk request; measured cost of the list on equal
-    // lengths: profiles/sedit_batch_latency.txt)
+    // lengths: profiles/sedit_batch_latency.txt).  Results by reference: returning the WaveTile reorders instructions of the
+    // RAGGED kernels (profiles/vocoder_tiles.txt).
     struct TileAt { int tile; int4 e; } req = {-1, {}}, cur = {-1, {}};
     auto locate = [&](TileAt& at, int tile, int& b, int& t0, int& Wb) {
-        if (RAGGED) {
-            if (tile != at.tile) at.e = a.tiles[tile < ntiles ? tile : 0], at.tile = tile;
-            b = at.e.x, t0 = at.e.y, Wb = at.e.z;
-        } else {
-            b = tile / a.tiles_t, t0 = (tile - b * a.tiles_t) * TILE, Wb = a.Tw;
-        }
+        if (RAGGED && tile != at.tile) at.e = a.tiles[tile < ntiles ? tile : 0], at.tile = tile;
+        const WaveTile w = RAGGED ? wave_tile_of(at.e) : wave_tile<false>(nullptr, tile, a.tiles_t, a.Tw);
+        b = w.b, t0 = w.t0, Wb = w.Wb;
     };
     const int r0 = tid >> 1, kq = (tid & 1) * (BK / 2);
     // The activation chunks are requested TWO chunks ahead of the MFMAs that consume them (register ring P0 / P1): with
@@ -140,7 +136,7 @@ __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int t = t0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                    const int t = acc32_row(r, lk, t0 + wm + i * 32);
                     const int64_t i0 = ((int64_t)b * a.Tw + (t < Wb ? t : 0)) * 64 + lr;
                     old[i][0][r] = oldsrc[i0];
                     old[i][1][r] = oldsrc[i0 + 32];
@@ -164,14 +160,12 @@ __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int t = t0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                    const int t = acc32_row(r, lk, t0 + wm + i * 32);
                     if (t >= Wb) continue;
                     const int64_t row = (int64_t)b * a.Tw + t;
                     if (STAGE == 0) {
                         const float ya = acc[i][0][r] + bj0, yb = acc[i][1][r] + bj1;
-                        // tanh(y) = 1 - 2 / (1 + e^{2y}): two v_exp_f32 + two v_rcp_f32 per output (abs error ~1e-7)
-                        const float th = 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * ya));
-                        a.g[row * 64 + (wn >> 1) + lr] = th * __frcp_rn(1.f + __expf(-yb));
+                        a.g[row * 64 + (wn >> 1) + lr] = pwg_gate(ya, yb);
                     } else {
                         const float o0 = acc[i][0][r] + bj0, o1 = acc[i][1][r] + bj1;
                         const int64_t i0 = row * 64 + lr;
@@ -199,12 +193,9 @@ __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
 template <bool RAGGED>
 static int pwg_launch(PwgArgs a, const float* wt0, const float* b0, const float* wt1, const float* b1, int ntiles, void* stream) {
     constexpr int lds0 = (272 * 128 + 2 * 8 * 260) * 4, lds1 = (64 * 128 + 2 * 16 * 260) * 4;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)pwg_stage_kernel<0, RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds0);
-        (void)hipFuncSetAttribute((const void*)pwg_stage_kernel<1, RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1);
-        attr = true;
-    }
+    hipError_t e = wave_lds_opt_in<pwg_stage_kernel<0, RAGGED>>(lds0);
+    if (e == hipSuccess) e = wave_lds_opt_in<pwg_stage_kernel<1, RAGGED>>(lds1);
+    if (e != hipSuccess) return (int)e;
     const int cus = device_cus();
     a.wt = wt0, a.bias = b0;
     int g0 = ntiles < cus ? ntiles : cus;                 // stage 0: 153 KiB of LDS -> one persistent workgroup per CU
@@ -218,13 +209,14 @@ static int pwg_launch(PwgArgs a, const float* wt0, const float* b0, const float*
 // Both entry points: tiles == nullptr is the dense form, all B rows Tw samples long.
 static int pwg_block(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1, float* g,
                      float* skips, const int32_t* tiles, int ntiles, int B, int Tw, int dil, void* stream) {
-    if (B <= 0 || Tw <= 0 || dil <= 0 || ntiles < 0 || ((uintptr_t)tiles & 15)) return A3T_EINVAL;
+    if (dil <= 0 || !x || !cu || !wt0 || !b0 || !wt1 || !b1 || !g || !skips) return A3T_EINVAL;
+    const int n = wave_grid(tiles, ntiles, B, Tw);
+    if (n <= 0) return n;
     PwgArgs a;
     a.x_in = x, a.cu = cu, a.gin = g, a.g = g, a.x_out = x, a.skips = skips;
-    a.B = B, a.Tw = Tw, a.dil = dil, a.tiles_t = (Tw + 255) / 256;
+    a.B = B, a.Tw = Tw, a.dil = dil, a.tiles_t = wave_tiles_t(Tw);
     a.tiles = (const int4*)tiles, a.ntiles = ntiles;
-    if (tiles) return ntiles ? pwg_launch<true>(a, wt0, b0, wt1, b1, ntiles, stream) : 0;
-    return pwg_launch<false>(a, wt0, b0, wt1, b1, B * a.tiles_t, stream);
+    return tiles ? pwg_launch<true>(a, wt0, b0, wt1, b1, n, stream) : pwg_launch<false>(a, wt0, b0, wt1, b1, n, stream);
 }
 
 // One residual block, in place on x and skips.  wt0: [272][128] (k = tap*64 + ch | 192 + aux ch; column n' = permuted
@@ -235,9 +227,8 @@ extern "C" int a3t_pwg_block(float* x, const float* cu, const float* wt0, const 
     return pwg_block(x, cu, wt0, b0, wt1, b1, g, skips, nullptr, 0, B, Tw, dil, stream);
 }
 
-// The same block over rows of different length in the padded [B][Tw] layout.  tiles: device int32 [ntiles][4] =
-// {row b, first sample t0 (a multiple of 256), valid samples W_b of row b, 0}, one entry per 256-sample tile with t0 < W_b
-// (0 <= b < B, W_b <= Tw: the caller's to guarantee, the kernel trusts the list).  Rows behind W_b keep what they held.
+// The same block over rows of different length in the padded [B][Tw] layout.  tiles: the device tile list of wave_tiles.h.
+// Rows behind W_b keep what they held.
 extern "C" int a3t_pwg_block_ragged(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1,
                                     const float* b1, float* g, float* skips, const int32_t* tiles, int ntiles, int B, int Tw,
                                     int dil, void* stream) {

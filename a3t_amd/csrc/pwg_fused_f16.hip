@@ -33,8 +33,8 @@
 #include <stdint.h>
 #include "../../include/a3t_hip.h"
 #include "device_cus.h"
+#include "wave_tiles.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct PwgF16Args {
@@ -46,11 +46,19 @@ struct PwgF16Args {
     const _Float16* w1;      // [64][128] = conv1x1_out.weight^T
     const float* b1;         // [128]
     float* skips;            // [B*Tw][64]
-    const int4* tiles;       // RAGGED: [ntiles] {row b, first sample t0, valid samples W_b, 0}
+    const int4* tiles;       // RAGGED: [ntiles] tile list (wave_tiles.h)
     int ntiles, B, Tw, dil, tiles_t;
 };
 
 __device__ __forceinline__ float sat16(float v) { return fminf(fmaxf(v, -65504.f), 65504.f); }
+
+// h() of eight consecutive values
+__device__ __forceinline__ f16x8 pack_f16_sat(float4 v0, float4 v1) {
+    f16x8 q;
+    q[0] = (_Float16)sat16(v0.x), q[1] = (_Float16)sat16(v0.y), q[2] = (_Float16)sat16(v0.z), q[3] = (_Float16)sat16(v0.w);
+    q[4] = (_Float16)sat16(v1.x), q[5] = (_Float16)sat16(v1.y), q[6] = (_Float16)sat16(v1.z), q[7] = (_Float16)sat16(v1.w);
+    return q;
+}
 
 // channel of output row i (0..31) of M-tile mt (0..1) of the second product
 __device__ __forceinline__ int out_channel(int mt, int i) {
@@ -59,7 +67,7 @@ __device__ __forceinline__ int out_channel(int mt, int i) {
 
 template <bool RAGGED>
 __global__ __launch_bounds__(512) void pwg_f16_kernel(PwgF16Args a) {
-    constexpr int KS0 = 17, KS1 = 4, TILE = 256;
+    constexpr int KS0 = 17, KS1 = 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     f16x8* W0f = (f16x8*)smem;                 // [4][KS0][64]
     f16x8* W1f = W0f + 4 * KS0 * 64;           // [4][KS1][64]
@@ -91,13 +99,7 @@ __global__ __launch_bounds__(512) void pwg_f16_kernel(PwgF16Args a) {
 
     const int ntiles = RAGGED ? a.ntiles : a.B * a.tiles_t;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        int b, t0, Wb;
-        if (RAGGED) {
-            const int4 e = a.tiles[tile];
-            b = e.x, t0 = e.y, Wb = e.z;
-        } else {
-            b = tile / a.tiles_t, t0 = (tile - b * a.tiles_t) * TILE, Wb = a.Tw;
-        }
+        const auto [b, t0, Wb] = wave_tile<RAGGED>(a.tiles, tile, a.tiles_t, a.Tw);
         if (t0 + w * 32 >= Wb) continue;        // (wave-uniform; no barrier below)
         const int t = t0 + w * 32 + r;
         const bool valid = t < Wb;
@@ -117,10 +119,7 @@ __global__ __launch_bounds__(512) void pwg_f16_kernel(PwgF16Args a) {
                 float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
                 if (ok) v0 = *(const float4*)(src + 16 * s), v1 = *(const float4*)(src + 16 * s + 4);
                 if (tap == 1) xc[s][0] = v0, xc[s][1] = v1;
-                f16x8 q;
-                q[0] = (_Float16)sat16(v0.x), q[1] = (_Float16)sat16(v0.y), q[2] = (_Float16)sat16(v0.z), q[3] = (_Float16)sat16(v0.w);
-                q[4] = (_Float16)sat16(v1.x), q[5] = (_Float16)sat16(v1.y), q[6] = (_Float16)sat16(v1.z), q[7] = (_Float16)sat16(v1.w);
-                bf[tap * 4 + s] = q;
+                bf[tap * 4 + s] = pack_f16_sat(v0, v1);
             }
         }
 #pragma unroll
@@ -164,9 +163,7 @@ __global__ __launch_bounds__(512) void pwg_f16_kernel(PwgF16Args a) {
                 for (int e = 0; e < 4; ++e) {
                     const int i = 4 * q + e;
                     const float ya = acc[2 * gt][i] + bav[e], yb = acc[2 * gt + 1][i] + bbv[e];
-                    // tanh(y) = 1 - 2 / (1 + e^{2y}), as in pwg_fused.hip
-                    const float th = 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * ya));
-                    gf[2 * gt + (q >> 1)][4 * (q & 1) + e] = (_Float16)(th * __frcp_rn(1.f + __expf(-yb)));
+                    gf[2 * gt + (q >> 1)][4 * (q & 1) + e] = (_Float16)pwg_gate(ya, yb);
                 }
             }
 
@@ -209,11 +206,8 @@ __global__ __launch_bounds__(512) void pwg_f16_kernel(PwgF16Args a) {
 template <bool RAGGED>
 static int pwg_f16_launch(const PwgF16Args& a, int ntiles, void* stream) {
     constexpr int lds = (4 * 17 + 4 * 4) * 64 * 16 + 256 * 4;      // 87 040 B
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)pwg_f16_kernel<RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr = true;
-    }
+    const hipError_t e = wave_lds_opt_in<pwg_f16_kernel<RAGGED>>(lds);
+    if (e != hipSuccess) return (int)e;
     const int cus = device_cus();
     hipLaunchKernelGGL((pwg_f16_kernel<RAGGED>), dim3(ntiles < cus ? ntiles : cus), dim3(512), lds, (hipStream_t)stream, a);
     return (int)hipGetLastError();
@@ -221,35 +215,30 @@ static int pwg_f16_launch(const PwgF16Args& a, int ntiles, void* stream) {
 
 // One residual block on the 16-bit MFMA.  x_in -> x_out (two different buffers: the caller swaps them per layer), skips updated
 // in place.  cu16 [B*Tw][80] fp16 (a3t_cast_f16_sat of the upsampled mel); w0h [272][128] fp16, rows and columns as wt0 of
-// a3t_pwg_block; w1h [64][128] fp16 = conv1x1_out.weight^T; b0 / b1 fp32 as there.  tiles: NULL = every row is Tw samples long,
-// else the list of a3t_pwg_block_ragged with its rules.
+// a3t_pwg_block; w1h [64][128] fp16 = conv1x1_out.weight^T; b0 / b1 fp32 as there.  tiles: the contract of wave_tiles.h.
 extern "C" int a3t_pwg_block_f16(const float* x_in, float* x_out, const void* cu16, const void* w0h, const float* b0,
                                  const void* w1h, const float* b1, float* skips, const int32_t* tiles, int ntiles, int B, int Tw,
                                  int dil, void* stream) {
-    if (B <= 0 || Tw <= 0 || dil <= 0 || !x_in || !x_out || !cu16 || !w0h || !b0 || !w1h || !b1 || !skips) return A3T_EINVAL;
-    if ((((uintptr_t)x_in | (uintptr_t)x_out | (uintptr_t)cu16 | (uintptr_t)skips | (uintptr_t)tiles) & 15) ||
+    const int n = wave_grid(tiles, ntiles, B, Tw);
+    if (n < 0 || dil <= 0 || !x_in || !x_out || !cu16 || !w0h || !b0 || !w1h || !b1 || !skips) return A3T_EINVAL;
+    if ((((uintptr_t)x_in | (uintptr_t)x_out | (uintptr_t)cu16 | (uintptr_t)skips) & 15) ||
         (((uintptr_t)w0h | (uintptr_t)w1h) & 1) || (((uintptr_t)b0 | (uintptr_t)b1) & 3))
         return A3T_EINVAL;
     const uintptr_t bytes = (uintptr_t)B * (uintptr_t)Tw * 64 * sizeof(float), xi = (uintptr_t)x_in, xo = (uintptr_t)x_out;
     if (xi < xo + bytes && xo < xi + bytes) return A3T_EINVAL;      // x_out overlaps x_in
-    if (tiles ? ntiles < 0 : ntiles != 0) return A3T_EINVAL;
+    if (!n) return 0;
     PwgF16Args a;
     a.x_in = x_in, a.x_out = x_out, a.cu = (const _Float16*)cu16, a.w0 = (const _Float16*)w0h, a.b0 = b0;
     a.w1 = (const _Float16*)w1h, a.b1 = b1, a.skips = skips;
-    a.B = B, a.Tw = Tw, a.dil = dil, a.tiles_t = (Tw + 255) / 256;
+    a.B = B, a.Tw = Tw, a.dil = dil, a.tiles_t = wave_tiles_t(Tw);
     a.tiles = (const int4*)tiles, a.ntiles = ntiles;
-    if (tiles) return ntiles ? pwg_f16_launch<true>(a, ntiles, stream) : 0;
-    return pwg_f16_launch<false>(a, B * a.tiles_t, stream);
+    return tiles ? pwg_f16_launch<true>(a, n, stream) : pwg_f16_launch<false>(a, n, stream);
 }
 
 __global__ void cast_f16_sat_kernel(const float* __restrict__ src, _Float16* __restrict__ dst, int64_t n) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
     if (i + 8 <= n) {
-        const float4 v0 = *(const float4*)(src + i), v1 = *(const float4*)(src + i + 4);
-        f16x8 q;
-        q[0] = (_Float16)sat16(v0.x), q[1] = (_Float16)sat16(v0.y), q[2] = (_Float16)sat16(v0.z), q[3] = (_Float16)sat16(v0.w);
-        q[4] = (_Float16)sat16(v1.x), q[5] = (_Float16)sat16(v1.y), q[6] = (_Float16)sat16(v1.z), q[7] = (_Float16)sat16(v1.w);
-        *(f16x8*)(dst + i) = q;
+        *(f16x8*)(dst + i) = pack_f16_sat(*(const float4*)(src + i), *(const float4*)(src + i + 4));
     } else {
         for (int64_t j = i; j < n; ++j) dst[j] = (_Float16)sat16(src[j]);
     }

@@ -612,25 +612,35 @@ def relpos_softmax_fwd_ragged(ac, bd, lens, probs, B, H, T, scale):
             "softmax_fwd_ragged")
 
 
+def _tile_list(what, tiles, B, Tw):
+    """(pointer, ntiles) of an optional tile list (vocoder.pwg_tile_list) for B rows of Tw samples (the contract of
+    csrc/wave_tiles.h: what can be checked on the host is, the kernels trust the entries); ntiles < 0: nothing to do."""
+    if tiles is None:
+        return None, 0
+    if tiles.dim() != 2 or tiles.shape[1] != 4:
+        raise ValueError(f"{what}: tiles must be (ntiles, 4), got {tuple(tiles.shape)}")
+    if tiles.shape[0] > B * ((Tw + 255) // 256):
+        raise ValueError(f"{what}: {tiles.shape[0]} tiles do not fit {B} rows of {Tw} samples")
+    _i32(tiles, "tiles")
+    if tiles.shape[0] == 0:      # (an empty tensor has no address: NULL would mean "dense")
+        return None, -1
+    return _ptr(tiles), tiles.shape[0]
+
+
 def pwg_block(x, cu, wt0, b0, wt1, b1, g, skips, B, Tw, dil, tiles=None):
     """Fused residual block, x and skips updated in place.  tiles None: all rows Tw samples long (a3t_pwg_block); else rows of
     different length (a3t_pwg_block_ragged), tiles: device int32 [ntiles][4] = {row b, first sample t0, valid samples W_b, 0}
     (vocoder.pwg_tile_list).  The kernel indexes x / cu / g / skips with the list's entries unchecked: 0 <= b < B, t0 < W_b <= Tw
-    are the caller's to guarantee; what can be checked on the host is."""
+    are the caller's to guarantee."""
     for name, t, C in (("x", x, 64), ("cu", cu, 80), ("g", g, 64), ("skips", skips, 64)):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != B * Tw * C:
             raise ValueError(f"pwg_block: {name} must be a contiguous fp32 [{B * Tw}][{C}] tensor")
     args = (_ptr(x), _ptr(cu), _ptr(wt0), _ptr(b0), _ptr(wt1), _ptr(b1), _ptr(g), _ptr(skips))
+    tp, nt = _tile_list("pwg_block", tiles, B, Tw)
     if tiles is None:
         L.check(L.load().a3t_pwg_block(*args, B, Tw, dil, _stream()), "pwg_block")
-        return
-    if tiles.dim() != 2 or tiles.shape[1] != 4:
-        raise ValueError(f"pwg_block: tiles must be (ntiles, 4), got {tuple(tiles.shape)}")
-    if tiles.shape[0] > B * ((Tw + 255) // 256):
-        raise ValueError(f"pwg_block: {tiles.shape[0]} tiles do not fit {B} rows of {Tw} samples")
-    _i32(tiles, "tiles")
-    if tiles.shape[0]:      # (an empty tensor has no address)
-        L.check(L.load().a3t_pwg_block_ragged(*args, _ptr(tiles), tiles.shape[0], B, Tw, dil, _stream()), "pwg_block")
+    elif nt > 0:
+        L.check(L.load().a3t_pwg_block_ragged(*args, tp, nt, B, Tw, dil, _stream()), "pwg_block")
 
 
 def cast_f16_sat(src, dst):
@@ -653,18 +663,11 @@ def pwg_block_f16(x_in, x_out, cu16, w0h, b0, w1h, b1, skips, tiles, B, Tw, dil)
                                ("b0", b0, (128,), torch.float32), ("b1", b1, (128,), torch.float32)):
         if t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape:
             raise ValueError(f"pwg_block_f16: {name} must be a contiguous {dt} tensor of shape {shape}")
-    nt = 0
-    if tiles is not None:
-        if tiles.dim() != 2 or tiles.shape[1] != 4:
-            raise ValueError(f"pwg_block_f16: tiles must be (ntiles, 4), got {tuple(tiles.shape)}")
-        if tiles.shape[0] > B * ((Tw + 255) // 256):
-            raise ValueError(f"pwg_block_f16: {tiles.shape[0]} tiles do not fit {B} rows of {Tw} samples")
-        nt = tiles.shape[0]
-        _i32(tiles, "tiles")
-        if nt == 0:      # (an empty tensor has no address: NULL would mean "dense")
-            return
+    tp, nt = _tile_list("pwg_block_f16", tiles, B, Tw)
+    if nt < 0:
+        return
     L.check(L.load().a3t_pwg_block_f16(_ptr(x_in), _ptr(x_out), _ptr(cu16), _ptr(w0h), _ptr(b0), _ptr(w1h), _ptr(b1),
-                                       _ptr(skips), _ptr(tiles), nt, B, Tw, dil, _stream()), "pwg_block_f16")
+                                       _ptr(skips), tp, nt, B, Tw, dil, _stream()), "pwg_block_f16")
 
 
 def leaky_relu(x, y, slope):
@@ -673,20 +676,6 @@ def leaky_relu(x, y, slope):
     if x.numel() != y.numel():
         raise ValueError("leaky_relu: x and y must have the same size")
     L.check(L.load().a3t_leaky_relu(_ptr(x), _ptr(y), x.numel(), slope, _stream()), "leaky_relu")
-
-
-def _hfg_tiles(what, tiles, B, Tw):
-    """(pointer, ntiles) of an optional tile list (vocoder.pwg_tile_list) for B rows of Tw samples; ntiles < 0: nothing to do."""
-    if tiles is None:
-        return None, 0
-    if tiles.dim() != 2 or tiles.shape[1] != 4:
-        raise ValueError(f"{what}: tiles must be (ntiles, 4), got {tuple(tiles.shape)}")
-    if tiles.shape[0] > B * ((Tw + 255) // 256):
-        raise ValueError(f"{what}: {tiles.shape[0]} tiles do not fit {B} rows of {Tw} samples")
-    _i32(tiles, "tiles")
-    if tiles.shape[0] == 0:      # (an empty tensor has no address: NULL would mean "dense")
-        return None, -1
-    return _ptr(tiles), tiles.shape[0]
 
 
 def hfg_conv(x, wt, bias, y, B, Tw, dil, slope, R=None, acc=None, alpha=1.0, acc_add=False, tiles=None):
@@ -708,7 +697,7 @@ def hfg_conv(x, wt, bias, y, B, Tw, dil, slope, R=None, acc=None, alpha=1.0, acc
     _ragged_f32("hfg_conv", wt, bias)
     if bias is not None and bias.numel() != C:
         raise ValueError(f"hfg_conv: bias must have {C} entries")
-    tp, nt = _hfg_tiles("hfg_conv", tiles, B, Tw)
+    tp, nt = _tile_list("hfg_conv", tiles, B, Tw)
     if nt < 0:
         return
     L.check(L.load().a3t_hfg_conv(_ptr(x), _ptr(wt), _ptr(bias), _ptr(R), _ptr(y), _ptr(acc), alpha, int(bool(acc_add)), slope,
@@ -722,7 +711,7 @@ def hfg_out(x, w, bias, y, B, Tw, slope, tiles=None):
     _ragged_f32("hfg_out", x, w, bias, y)
     if w.dim() != 2 or w.shape[1] != C or x.numel() != B * Tw * C or y.numel() != B * Tw:
         raise ValueError("hfg_out: shapes do not fit")
-    tp, nt = _hfg_tiles("hfg_out", tiles, B, Tw)
+    tp, nt = _tile_list("hfg_out", tiles, B, Tw)
     if nt < 0:
         return
     L.check(L.load().a3t_hfg_out(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), slope, tp, nt, B, Tw, C, w.shape[0], _stream()), "hfg_out")

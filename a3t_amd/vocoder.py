@@ -63,31 +63,74 @@ def pwg_gate_perm(gate_channels: int = 128) -> np.ndarray:
     return (n // 64) * 32 + n % 32 + (gate_channels // 2) * ((n // 32) % 2)
 
 
-def pack_pwg_block_f16(conv_w, conv_b, aux_w, out_w):
-    """Operands of a3t_pwg_block_f16 from one residual block's parameters (CPU or device tensors; pure).
+def _pack_pwg_block(conv_w, conv_b, aux_w, out_w, cast=torch.Tensor.contiguous):
+    """Operands of the fused residual blocks from one block's parameters (CPU or device tensors; pure).
 
     conv_w (128, 64, 3) dilated conv, conv_b (128,), aux_w (128, 80[, 1]) conv1x1_aux, out_w (128, 64[, 1]) conv1x1_out ->
-    w0h fp16 [272][128]: row k = tap*64 + in_channel for the taps at t-dil, t, t+dil, then 192 + aux channel (tap-major K
-    order); column n' = pwg_gate_perm;  b0 fp32 [128] permuted the same way;  w1h fp16 [64][128] = conv1x1_out.weight^T.
-    The cast is round-to-nearest-even and saturates to +-65504."""
+    w0 [272][128]: row k = tap*64 + in_channel for the taps at t-dil, t, t+dil, then 192 + aux channel (tap-major K
+    order); column n' = pwg_gate_perm;  b0 fp32 [128] permuted the same way;  w1 [64][128] = conv1x1_out.weight^T.
+    cast: what the two weight matrices pass through (the fp32 kernels: nothing)."""
     conv_w = torch.as_tensor(conv_w, dtype=torch.float32)
     G, R, taps = conv_w.shape
     aux_w = torch.as_tensor(aux_w, dtype=torch.float32).reshape(G, -1)
     out_w = torch.as_tensor(out_w, dtype=torch.float32).reshape(-1, G // 2)
     if (G, R, taps, aux_w.shape[1], out_w.shape[0]) != (128, 64, 3, 80, 128):
-        raise ValueError("pack_pwg_block_f16: the kernel is built for the v1 channel plan (64 / 128 / 64 / 80, kernel size 3)")
+        raise ValueError("pwg block operands: the kernels are built for the v1 channel plan (64 / 128 / 64 / 80, kernel size 3)")
     perm = torch.as_tensor(pwg_gate_perm(G), device=conv_w.device)
     wk = conv_w.permute(0, 2, 1).reshape(G, taps * R)                       # [out][tap*64 + in]
     w0 = torch.cat([wk, aux_w.to(conv_w.device)], dim=1)[perm]               # [n'][272]
-
-    def h(t):
-        return t.clamp(-F16_MAX, F16_MAX).to(torch.float16).contiguous()
-
     b0 = torch.as_tensor(conv_b, dtype=torch.float32).to(conv_w.device)[perm].contiguous()
-    return h(w0.t()), b0, h(out_w.to(conv_w.device).t())
+    return cast(w0.t()), b0, cast(out_w.to(conv_w.device).t())
 
 
-class ParallelWaveGANGeneratorHIP:
+def pack_pwg_block_f16(conv_w, conv_b, aux_w, out_w):
+    """Operands of a3t_pwg_block_f16: _pack_pwg_block with w0h / w1h cast to fp16, round-to-nearest-even and saturated to
+    +-65504."""
+    return _pack_pwg_block(conv_w, conv_b, aux_w, out_w, lambda t: t.clamp(-F16_MAX, F16_MAX).to(torch.float16).contiguous())
+
+
+class _WaveGeneratorHIP:
+    """What the generators share: the device, the statistics of normalize_before and the preamble of inference."""
+
+    def _setup(self, device, aux_channels, stats):
+        self.dev, self.A = torch.device(device), int(aux_channels)
+        self.stats = None
+        if stats is not None:     # normalize_before of the pretrained wrapper (c - mean) / scale
+            self.stats = (torch.as_tensor(stats["mean"], dtype=torch.float32, device=self.dev),
+                          torch.as_tensor(stats["scale"], dtype=torch.float32, device=self.dev))
+
+    def prepare(self, c, normalize_before, lengths, rates):
+        """c (T_feats, aux) or (B, T_feats, aux) -> (c [B][Tf][A] fp32 on the device, single, lens, tiles).  lengths (host
+        integers, one per row): lens = the device int32 [B] of them and tiles = {rate: pwg_tile_list(lengths, rate) on the device}
+        for the samples-per-frame rates that fused kernels run at, else None and {}."""
+        single = (c.dim() == 2)
+        c = c.to(self.dev, torch.float32)
+        if single:
+            c = c[None]
+        B, Tf, A = c.shape
+        if A != self.A:
+            raise ValueError(f"c has {A} channels, the generator {self.A}")
+        if normalize_before and self.stats is not None:
+            c = (c - self.stats[0]) / self.stats[1]
+        if lengths is None:
+            return c, single, None, {}
+        if single:
+            raise ValueError("lengths= goes with a (B, Tmax, aux) batch")
+        lengths = [int(x) for x in lengths]
+        if len(lengths) != B or any(n < 0 or n > Tf for n in lengths):
+            raise ValueError(f"lengths {lengths} do not fit a batch of {B} rows of {Tf} frames")
+        # one H2D copy: lens [B] | one tile list [ntiles][4] = {b, t0, W_b, 0} per rate (offsets kept 16-byte aligned)
+        lists = [pwg_tile_list(lengths, r) for r in rates]
+        offs = np.cumsum([(B + 3) // 4 * 4] + [tl.size for tl in lists]).tolist()
+        host = np.zeros(offs[-1], dtype=np.int32)
+        host[:B] = lengths
+        for o, tl in zip(offs, lists):
+            host[o:o + tl.size] = tl.reshape(-1)
+        meta = torch.from_numpy(host).to(self.dev)
+        return c, single, meta[:B], {r: meta[o:o + tl.size].view(len(tl), 4) for r, o, tl in zip(rates, offs, lists)}
+
+
+class ParallelWaveGANGeneratorHIP(_WaveGeneratorHIP):
     """compute="f32" (default): exact fp32 products.  compute="f16": the residual blocks run on the 16-bit MFMA, one launch per
     block (pwg_fused_f16.hip): the conv input, the upsampled mel, the gate output and the block weights are rounded to fp16
     (nearest even, saturated), everything else stays fp32.  It needs the fused v1 channel plan."""
@@ -105,16 +148,12 @@ class ParallelWaveGANGeneratorHIP:
                 raise ValueError("compute='f16' is a mode of the fused residual blocks: fused=False cannot be combined with it")
             fused = True
         self.compute = compute
-        self.dev = torch.device(device)
+        self._setup(device, aux_channels, stats)
         self.layers, self.stacks = layers, stacks
-        self.R, self.G, self.S, self.A = residual_channels, gate_channels, skip_channels, aux_channels
+        self.R, self.G, self.S = residual_channels, gate_channels, skip_channels
         self.ctx = aux_context_window
         self.scales = tuple(upsample_scales)
         self.upsample_factor = int(np.prod(self.scales))
-        self.stats = None
-        if stats is not None:     # normalize_before of the pretrained wrapper (c - mean) / scale
-            self.stats = (torch.as_tensor(stats["mean"], dtype=torch.float32, device=self.dev),
-                          torch.as_tensor(stats["scale"], dtype=torch.float32, device=self.dev))
 
         def t(k):
             return torch.as_tensor(np.asarray(state_dict[k]), dtype=torch.float32).to(self.dev)
@@ -131,9 +170,6 @@ class ParallelWaveGANGeneratorHIP:
         if fused is None:
             fused = os.environ.get("A3T_PWG_FUSED", "1") != "0"
         self.fused = bool(fused) and (self.R, self.G, self.S, self.A) == (64, 128, 64, 80)
-        # stage-0 output column n' holds gate channel c = 32*(n'//64) + n'%32, tanh half for (n'//32)%2 == 0 else sigmoid
-        npr = np.arange(128)
-        perm = torch.as_tensor((npr // 64) * 32 + npr % 32 + 64 * ((npr // 32) % 2), device=self.dev)
         self.blocks = []
         for l in range(layers):
             p = f"conv_layers.{l}."
@@ -141,14 +177,11 @@ class ParallelWaveGANGeneratorHIP:
                        aux=t(p + "conv1x1_aux.weight").reshape(self.G, self.A).contiguous(),
                        out=t(p + "conv1x1_out.weight").reshape(self.R + self.S, self.G // 2).contiguous(),
                        bout=t(p + "conv1x1_out.bias"))
-            if self.fused:
-                wk = blk["w"].reshape(self.G, 3 * self.R)                       # [out][tap*64 + in]
-                w0 = torch.cat([wk, blk["aux"]], dim=1)[perm]                   # [n'][272]
-                blk["wt0"] = w0.t().contiguous()                                # [272][128] k-major
-                blk["b0"] = blk["b"][perm].contiguous()
-                blk["wt1"] = blk["out"].t().contiguous()                        # [64][128]
-            if compute == "f16":
-                blk["w0h"], blk["b0h"], blk["w1h"] = pack_pwg_block_f16(t(p + "conv.weight"), blk["b"], blk["aux"], blk["out"])
+            if self.fused:      # wt0 [272][128] k-major in the gate permutation, wt1 [64][128]
+                raw = (t(p + "conv.weight"), blk["b"], blk["aux"], blk["out"])
+                blk["wt0"], blk["b0"], blk["wt1"] = _pack_pwg_block(*raw)
+                if compute == "f16":
+                    blk["w0h"], blk["b0h"], blk["w1h"] = pack_pwg_block_f16(*raw)
             self.blocks.append(blk)
         self.w_l1 = t("last_conv_layers.1.weight").reshape(self.S, self.S).contiguous()
         self.b_l1 = t("last_conv_layers.1.bias")
@@ -164,31 +197,12 @@ class ParallelWaveGANGeneratorHIP:
         z[b, :L_b * hop]) had been passed alone -- replicate padding, the smoothing and the dilated convolutions see the row's
         own end -- and the result (B, Tmax * hop, 1) is zero behind L_b * hop.  What the padding of c and z holds reaches no
         valid sample, and with the fused blocks the padding costs no time."""
-        single = (c.dim() == 2)
-        c = c.to(self.dev, torch.float32)
-        if single:
-            c = c[None]
-        B, Tf, A = c.shape
-        if normalize_before and self.stats is not None:
-            c = (c - self.stats[0]) / self.stats[1]
-        if lengths is not None and single:
-            raise ValueError("lengths= goes with a (B, Tmax, aux) batch")
         hop = self.upsample_factor
+        c, single, lens, tiles = self.prepare(c, normalize_before, lengths, (hop,))
+        tiles = tiles.get(hop)
+        B, Tf, A = c.shape
         Tw = Tf * hop
         dev = self.dev
-        lens = tiles = None
-        if lengths is not None:
-            lengths = [int(x) for x in lengths]
-            if len(lengths) != B or any(n < 0 or n > Tf for n in lengths):
-                raise ValueError(f"lengths {lengths} do not fit a batch of {B} rows of {Tf} frames")
-            # one H2D copy: lens [B] | tile list [ntiles][4] = {b, t0, W_b, 0} for the fused blocks (offset kept 16-byte aligned)
-            tl = pwg_tile_list(lengths, hop)
-            off = (B + 3) // 4 * 4
-            host = np.zeros(off + tl.size, dtype=np.int32)
-            host[:B] = lengths
-            host[off:] = tl.reshape(-1)
-            meta = torch.from_numpy(host).to(dev)
-            lens, tiles = meta[:B], meta[off:].view(len(tl), 4)
         if z is None:
             z = torch.randn(B, Tw, 1, device=dev)
         z = z.to(dev, torch.float32).reshape(B * Tw, 1).contiguous()
@@ -328,7 +342,7 @@ def pack_hifigan_conv(w: torch.Tensor) -> torch.Tensor:
     return w.permute(2, 1, 0).reshape(k * Cin, Cout).contiguous()
 
 
-class HiFiGANGeneratorHIP:
+class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
     """HiFi-GAN generator inference (espnet2/gan_tts/hifigan/hifigan.py:25-221, state-dict compatible with the
     parallel_wavegan zoo's HiFiGANGenerator), channels-last fp32 [B*T][C] on the device.
 
@@ -356,14 +370,10 @@ class HiFiGANGeneratorHIP:
             raise ValueError("resblock_dilations must have one list per entry of resblock_kernel_sizes")
         if channels % (2 ** len(self.scales)):
             raise ValueError(f"channels {channels} must be divisible by 2^{len(self.scales)}")
-        self.dev = torch.device(device)
-        self.A, self.C0, self.K = int(in_channels), int(channels), int(kernel_size)
+        self._setup(device, in_channels, stats)
+        self.C0, self.K = int(channels), int(kernel_size)
         self.add, self.slope = bool(use_additional_convs), float(negative_slope)
         self.upsample_factor = int(np.prod(self.scales))
-        self.stats = None
-        if stats is not None:     # normalize_before of the pretrained wrapper (c - mean) / scale
-            self.stats = (torch.as_tensor(stats["mean"], dtype=torch.float32, device=self.dev),
-                          torch.as_tensor(stats["scale"], dtype=torch.float32, device=self.dev))
 
         def w(p):
             return fold_weight_norm(state_dict, p)
@@ -454,44 +464,16 @@ class HiFiGANGeneratorHIP:
         result (B, Tmax * hop, 1) is zero behind L_b * hop.  What the padding of c holds reaches no valid sample."""
         if z is not None:
             raise ValueError("HiFiGANGeneratorHIP.inference: z must be None, the HiFi-GAN generator has no noise input")
-        single = (c.dim() == 2)
-        c = c.to(self.dev, torch.float32)
-        if single:
-            c = c[None]
-        B, Tf, A = c.shape
-        if A != self.A:
-            raise ValueError(f"c has {A} channels, the generator {self.A}")
-        if normalize_before and self.stats is not None:
-            c = (c - self.stats[0]) / self.stats[1]
-        if lengths is not None and single:
-            raise ValueError("lengths= goes with a (B, Tmax, aux) batch")
-        dev = self.dev
-        lens, tiles = None, {}
-        if lengths is not None:
-            lengths = [int(x) for x in lengths]
-            if len(lengths) != B or any(n < 0 or n > Tf for n in lengths):
-                raise ValueError(f"lengths {lengths} do not fit a batch of {B} rows of {Tf} frames")
-            # one H2D copy: lens [B] | one tile list per fused rate (offsets kept 16-byte aligned)
-            rates, r = [], 1
-            for st in self.stages:
-                r *= st["s"]
-                if st["fused"]:
-                    rates.append(r)
-            if self.fused_out and r not in rates:
+        rates, r = [], 1      # the rates of the fused kernels
+        for st in self.stages:
+            r *= st["s"]
+            if st["fused"]:
                 rates.append(r)
-            lists = [pwg_tile_list(lengths, r) for r in rates]
-            off = (B + 3) // 4 * 4
-            host = np.zeros(off + sum(tl.size for tl in lists), dtype=np.int32)
-            host[:B] = lengths
-            o = off
-            for tl in lists:
-                host[o:o + tl.size] = tl.reshape(-1)
-                o += tl.size
-            meta, o = torch.from_numpy(host).to(dev), off
-            lens = meta[:B]
-            for r, tl in zip(rates, lists):
-                tiles[r] = meta[o:o + tl.size].view(len(tl), 4)
-                o += tl.size
+        if self.fused_out and r not in rates:
+            rates.append(r)
+        c, single, lens, tiles = self.prepare(c, normalize_before, lengths, rates)
+        B, Tf, A = c.shape
+        dev = self.dev
 
         def tail(x, rate, T):
             if lens is not None:

@@ -459,18 +459,22 @@ int a3t_dropout_bwd_cast(const float* g, void* gm, int gm_dtype, float* colsum, 
  * b0 [128] permuted the same way.  wt1 [64][128] = conv1x1_out.weight^T (columns 0..63 residual, 64..127 skip), b1 [128]. */
 int a3t_pwg_block(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1,
                   float* g, float* skips, int B, int Tw, int dil, void* stream);
-/* a3t_pwg_block over rows of different length: tiles [ntiles][4] int32 on the device (16-byte aligned) = {row b, first
- * sample t0 (multiple of 256), valid samples W_b <= Tw of row b, 0}, one entry per 256-sample tile with t0 < W_b.  A tap at
- * ts is zero unless 0 <= ts < W_b; rows behind W_b are neither read nor written; tiles that are not listed cost nothing. */
+/* The tile contract of the waveform kernels (a3t_pwg_block_ragged, a3t_pwg_block_f16, a3t_hfg_conv, a3t_hfg_out;
+ * csrc/wave_tiles.h).  tiles == NULL (and ntiles == 0): every row is Tw samples long.  Else rows of different length: tiles
+ * [ntiles][4] int32 on the device (16-byte aligned) = {row b, first sample t0 (multiple of 256), valid samples W_b <= Tw of row
+ * b, 0}, one entry per 256-sample tile with t0 < W_b (the kernels trust the entries).  Row b is computed as if it were alone:
+ * a tap at ts is zero unless 0 <= ts < W_b; rows behind W_b are neither read nor written; tiles that are not listed cost
+ * nothing, and ntiles == 0 is a successful no-op.  A3T_EINVAL for B, Tw or ntiles out of range, ntiles without a list, a
+ * misaligned list, or a dense grid B * ceil(Tw / 256) beyond INT_MAX.
+ * a3t_pwg_block_ragged: a3t_pwg_block over such a list (tiles must be given).  Both refuse a NULL operand. */
 int a3t_pwg_block_ragged(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1,
                          float* g, float* skips, const int32_t* tiles, int ntiles, int B, int Tw, int dil, void* stream);
 /* The same block in ONE launch on the 16-bit MFMA (fp16 operands, fp32 accumulation): the conv input x, cu, the gate output
  * and the weights are rounded to nearest even to fp16 and saturated to +-65504; biases, tanh / sigmoid, the residual stream and
  * skips stay fp32.  x_in -> x_out, two buffers that must not overlap (a tile reads x[t +- dil] of tiles that may be finished
  * already; the caller swaps them per layer); skips in place.  cu16 [B*Tw][80] fp16 (a3t_cast_f16_sat of cu); w0h [272][128] and
- * w1h [64][128] fp16 with the rows and columns of wt0 / wt1 above; b0 / b1 fp32 as above.  tiles == NULL (and ntiles == 0):
- * every row is Tw samples long; else the tile list of a3t_pwg_block_ragged, with its rules.  x_in, x_out, cu16, skips and tiles
- * 16-byte aligned.  A sample's result does not depend on its tile or on the other rows of the batch. */
+ * w1h [64][128] fp16 with the rows and columns of wt0 / wt1 above; b0 / b1 fp32 as above.  tiles / ntiles: the tile
+ * contract above.  x_in, x_out, cu16 and skips 16-byte aligned.  A sample's result does not depend on its tile or on the other rows of the batch. */
 int a3t_pwg_block_f16(const float* x_in, float* x_out, const void* cu16, const void* w0h, const float* b0, const void* w1h,
                       const float* b1, float* skips, const int32_t* tiles, int ntiles, int B, int Tw, int dil, void* stream);
 /* dst[i] = fp16(src[i]), round to nearest even, saturated to +-65504; both 16-byte aligned. */
@@ -483,9 +487,7 @@ int a3t_cast_f16_sat(const float* src, void* dst, int64_t n, void* stream);
  *   y[t] = v[t] when y is given, and when acc is given acc[t] = alpha * v[t] (acc_add == 0) or acc[t] += alpha * v[t].
  *   wt [taps*C][C] k-major (row = tap*C + in channel, column = out channel); bias [C], R, y, acc may be NULL (y or acc must be
  *   given).  R may alias y; x must be neither y nor acc (a tile reads x[t +- halo] of other tiles).  Exact fp32 products
- *   (v_mfma_f32_32x32x2f32).  tiles == NULL (and ntiles == 0): every row is Tw samples long; else the tile list of
- *   a3t_pwg_block_ragged with its rules (a tap at ts is zero unless 0 <= ts < W_b; rows behind W_b are neither read nor
- *   written).  x, wt and tiles 16-byte aligned.  A sample's result does not depend on its tile or on the other rows.
+ *   (v_mfma_f32_32x32x2f32).  tiles / ntiles: the tile contract above.  x and wt 16-byte aligned.  A sample's result does not depend on its tile or on the other rows.
  * a3t_hfg_out: y[t] = tanh(bias[0] + sum_{tap,c} w[tap*C + c] * leaky(x[t + tap - (K-1)/2][c])), x [B*Tw][C] -> y [B*Tw];
  *   C % 4 == 0, C <= 64, K odd <= 11; tiles as above.
  * a3t_leaky_relu: y[i] = leaky(x[i]) over n floats, in place allowed.

@@ -198,3 +198,45 @@ def test_z_raises():
         g.inference(torch.zeros(3, 80), z=torch.zeros(900, 1))
     with pytest.raises(ValueError, match="z"):
         g(torch.zeros(3, 80), torch.zeros(900, 1))
+
+
+def test_pwg_refuses_another_channel_count():
+    """The shared preamble refuses a c of the wrong width for ParallelWaveGAN too, before anything touches a device."""
+    import pwg_f16_ref
+    from a3t_amd.vocoder import ParallelWaveGANGeneratorHIP
+    g = ParallelWaveGANGeneratorHIP(pwg_f16_ref.vocoder_state(seed=4)[1], device="cpu")
+    with pytest.raises(ValueError, match="79 channels"):
+        g.inference(torch.zeros(5, 79))
+    with pytest.raises(ValueError, match="goes with a"):
+        g.inference(torch.zeros(5, 80), lengths=[5])
+    with pytest.raises(ValueError, match="do not fit"):
+        g.inference(torch.zeros(2, 5, 80), lengths=[5, 6])
+
+
+@pytest.mark.parametrize("rates", [(300,), (25, 100, 300)])
+def test_shared_preamble(rates):
+    """prepare(): lens and one tile list per rate, all views of ONE int32 buffer, every list at a multiple of 4 words."""
+    from a3t_amd.vocoder import HiFiGANGeneratorHIP, pwg_tile_list
+    g = HiFiGANGeneratorHIP(R.procedural_hifigan_state(NARROW, 7), device="cpu", **NARROW)
+    lengths, mel = (3, 0, 2), torch.randn(3, 3, 80, dtype=torch.float64)
+    c, single, lens, tiles = g.prepare(mel, False, lengths, rates)
+    assert c.dtype == torch.float32 and c.shape == (3, 3, 80) and torch.equal(c, mel.float()) and not single
+    assert lens.dtype == torch.int32 and lens.tolist() == list(lengths) and lens.storage_offset() == 0
+    assert list(tiles) == list(rates)
+    end = 4      # lens [3], padded to 4 words
+    for r in rates:
+        want = pwg_tile_list(lengths, r)
+        assert tiles[r].dtype == torch.int32 and tiles[r].is_contiguous() and np.array_equal(tiles[r].numpy(), want)
+        assert tiles[r].untyped_storage().data_ptr() == lens.untyped_storage().data_ptr()
+        assert tiles[r].storage_offset() % 4 == 0 and tiles[r].storage_offset() == end
+        end += want.size
+    assert lens.untyped_storage().nbytes() == 4 * end
+    # without lengths: no buffer at all; a single utterance gains its batch dimension
+    c1, single, lens, tiles = g.prepare(mel[0], False, None, rates)
+    assert c1.shape == (1, 3, 80) and single and lens is None and tiles == {}
+    with pytest.raises(ValueError, match="goes with a"):
+        g.prepare(mel[0], False, [3], rates)
+    with pytest.raises(ValueError, match="do not fit"):
+        g.prepare(mel, False, (3, 4, 2), rates)
+    with pytest.raises(ValueError, match="do not fit"):
+        g.prepare(mel, False, (3, 2), rates)

@@ -57,10 +57,21 @@ def test_operands_stay_far_inside_the_fp16_range():
     assert stats["max_x"] < 100 and stats["max_cu"] < 100
 
 
+def _check_block_layout(w0, b0, w1, conv_w, conv_b, aux_w, out_w, perm, rnd):
+    """w0 [272][128] / b0 / w1 [64][128] against an index formula of the test's own; rnd: the rounding of the weights."""
+    for tap in range(3):
+        want = rnd(conv_w[:, :, tap])[perm].t()                        # [in][n']
+        assert torch.equal(w0[tap * 64:(tap + 1) * 64].float(), want), tap
+    assert torch.equal(w0[192:].float(), rnd(aux_w[:, :, 0])[perm].t())
+    assert torch.equal(w1.float(), rnd(out_w[:, :, 0]).t())
+    assert torch.equal(b0, conv_b[perm])
+
+
 def test_packer_layout_and_rounding():
     """w0h [272][128]: tap-major K order (k = tap * 64 + in channel | 192 + aux channel), columns in the gate permutation; w1h =
-    conv1x1_out.weight^T; dequantised they ARE the permuted fp32 weights rounded to fp16; saturation instead of infinity."""
-    from a3t_amd.vocoder import pack_pwg_block_f16, pwg_gate_perm
+    conv1x1_out.weight^T; dequantised they ARE the permuted fp32 weights rounded to fp16; saturation instead of infinity.
+    Second case: the fp32 operands of the fused path (wt0 / b0 / wt1 of a generator) against the same formula without rounding."""
+    from a3t_amd.vocoder import ParallelWaveGANGeneratorHIP, pack_pwg_block_f16, pwg_gate_perm
     rs = np.random.RandomState(11)
     conv_w = torch.from_numpy(rs.standard_normal((128, 64, 3)).astype(np.float32))
     conv_b = torch.from_numpy(rs.standard_normal(128).astype(np.float32))
@@ -78,18 +89,20 @@ def test_packer_layout_and_rounding():
     for c in (0, 31, 32, 63):
         for half in (0, 1):
             assert perm[64 * (c // 32) + 32 * half + c % 32] == c + 64 * half
-    rnd = R.rounder(torch.float16)
-    for tap in range(3):
-        want = rnd(conv_w[:, :, tap])[perm].t()                        # [in][n']
-        assert torch.equal(w0h[tap * 64:(tap + 1) * 64].float(), want), tap
-    assert torch.equal(w0h[192:].float(), rnd(aux_w[:, :, 0])[perm].t())
-    assert torch.equal(w1h.float(), rnd(out_w[:, :, 0]).t())
-    assert torch.equal(b0, conv_b[perm])
+    _check_block_layout(w0h, b0, w1h, conv_w, conv_b, aux_w, out_w, perm, R.rounder(torch.float16))
     assert torch.isfinite(w0h.float()).all() and torch.isfinite(w1h.float()).all()
     n5 = int(np.where(perm == 5)[0][0])
     assert float(w0h[2 * 64 + 7, n5]) == 65504.0 and float(w1h[9, 3]) == -65504.0
     with pytest.raises(ValueError):
         pack_pwg_block_f16(conv_w[:, :32], conv_b, aux_w, out_w)
+    cfg, state = R.vocoder_state(seed=4)
+    gen = ParallelWaveGANGeneratorHIP(state, device="cpu", fused=True)
+    for l in (0, 17):
+        blk, (cw, cb, aw, ow) = gen.blocks[l], (torch.as_tensor(np.asarray(state[f"conv_layers.{l}.{k}"]), dtype=torch.float32)
+                                                for k in ("conv.weight", "conv.bias", "conv1x1_aux.weight", "conv1x1_out.weight"))
+        for name, shape in (("wt0", (272, 128)), ("b0", (128,)), ("wt1", (64, 128))):
+            assert blk[name].shape == shape and blk[name].dtype == torch.float32 and blk[name].is_contiguous()
+        _check_block_layout(blk["wt0"], blk["b0"], blk["wt1"], cw, cb, aw, ow, perm, lambda t: t)
 
 
 def test_packer_agrees_with_the_fp32_operands_of_the_fused_path():
@@ -112,8 +125,40 @@ def test_new_entry_points_are_exported():
     assert len(_lib._SIGS["a3t_pwg_block_f16"]) == 14 and len(_lib._SIGS["a3t_cast_f16_sat"]) == 4
 
 
+PWG_OPERANDS = ("x", "cu", "wt0", "b0", "wt1", "b1", "g", "skips")
+# argument order of the five entry points of the tiled waveform kernels; pointers are named after what they hold
+ENTRY_ARGS = {
+    "a3t_pwg_block": PWG_OPERANDS + ("B", "Tw", "dil", "stream"),
+    "a3t_pwg_block_ragged": PWG_OPERANDS + ("tiles", "ntiles", "B", "Tw", "dil", "stream"),
+    "a3t_pwg_block_f16": ("x", "y", "cu", "wt0", "b0", "wt1", "b1", "skips", "tiles", "ntiles", "B", "Tw", "dil", "stream"),
+    "a3t_hfg_conv": ("x", "wt0", "b0", "R", "y", "acc", "alpha", "acc_add", "slope", "tiles", "ntiles", "B", "Tw", "C", "taps",
+                     "dil", "stream"),
+    "a3t_hfg_out": ("x", "wt0", "b0", "y", "slope", "tiles", "ntiles", "B", "Tw", "C", "K", "stream"),
+}
+DENSE = ("a3t_pwg_block", "a3t_pwg_block_f16", "a3t_hfg_conv", "a3t_hfg_out")
+WITH_LIST = ("a3t_pwg_block_ragged", "a3t_pwg_block_f16", "a3t_hfg_conv", "a3t_hfg_out")
+
+
+def _refusal_rows(tl):
+    """(entry, the arguments that differ from a call that would launch); tl: the address of an aligned tile list."""
+    rows = []
+    for name in WITH_LIST:
+        rows += [(name, dict(tiles=tl + 4, ntiles=1)), (name, dict(tiles=tl, ntiles=-1)), (name, dict(tiles=None, ntiles=1))]
+    for name, args in ENTRY_ARGS.items():
+        rows += [(name, {k: v}) for k in ("B", "Tw", "dil") if k in args for v in (0, -1)]
+    # a dense grid of 2^20 x 2^23 tiles, beyond INT_MAX (and Tw + 255 beyond it already)
+    rows += [(name, dict(B=1 << 20, Tw=0x7fffffff)) for name in DENSE]
+    for name in ("a3t_pwg_block", "a3t_pwg_block_ragged"):
+        rows += [(name, {k: None}) for k in PWG_OPERANDS]
+    rows.append(("a3t_pwg_block_ragged", dict(tiles=None, ntiles=0)))
+    return rows
+
+
 def test_entry_point_refuses_bad_arguments_on_the_host():
-    """Aliasing, misalignment and non-positive sizes are refused before anything is launched (no device needed)."""
+    """Aliasing, misalignment and non-positive sizes are refused before anything is launched (no device needed), and the five
+    entry points of the tiled waveform kernels share one argument contract (csrc/wave_tiles.h): a misaligned list, a negative
+    count, a count without a list, non-positive sizes, a dense grid beyond INT_MAX and (the fp32 PWG blocks) a NULL operand are
+    A3T_EINVAL.  Every row has to be refused before any HIP call: the pointers are host memory."""
     import ctypes
     from a3t_amd import _lib
     lib = _lib.load()
@@ -131,6 +176,19 @@ def test_entry_point_refuses_bad_arguments_on_the_host():
     assert f(x, y, cu, w0, b0, w1, b1, sk, tl, -1, 1, 1, 1, None) == einval
     assert lib.a3t_cast_f16_sat(ctypes.c_void_p(x.value + 4), y, 8, None) == einval
     assert lib.a3t_cast_f16_sat(x, y, -1, None) == einval
+
+    pointers = dict(x=x, y=y, cu=cu, wt0=w0, b0=b0, wt1=w1, b1=b1, skips=sk, g=ctypes.c_void_p(a + 256 * 9), R=None, acc=None,
+                    stream=None)
+    good = dict(pointers, alpha=1.0, acc_add=0, slope=0.1, B=1, Tw=1, dil=1, C=32, taps=3, K=7)
+    rows = _refusal_rows(tl.value)
+    assert len(rows) == 12 + 28 + 4 + 16 + 1
+    for name, change in rows:
+        ragged = name == "a3t_pwg_block_ragged"
+        v = dict(good, tiles=tl.value if ragged else None, ntiles=1 if ragged else 0)
+        assert change and set(change) <= set(ENTRY_ARGS[name]) and any(v[k] != change[k] for k in change)
+        v.update(change)
+        v["tiles"] = None if v["tiles"] is None else ctypes.c_void_p(v["tiles"])
+        assert getattr(lib, name)(*(v[k] for k in ENTRY_ARGS[name])) == einval, (name, change)
 
 
 def test_constructor_refuses_f16_without_the_fused_v1_plan():
