@@ -110,6 +110,7 @@ _SIGS = {
     "a3t_pwg_block_f16": [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_cast_f16_sat": [_P, _P, c_int64, _P],
     "a3t_hfg_conv": [_P, _P, _P, _P, _P, _P, c_float, c_int, c_float, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
+    "a3t_hfg_conv_f16": [_P, _P, _P, _P, _P, _P, c_float, c_int, c_float, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "a3t_hfg_out": [_P, _P, _P, _P, c_float, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "a3t_leaky_relu": [_P, _P, c_int64, c_float, _P],
     "a3t_duration_head": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P],

@@ -704,6 +704,33 @@ def hfg_conv(x, wt, bias, y, B, Tw, dil, slope, R=None, acc=None, alpha=1.0, acc
                                   tp, nt, B, Tw, C, wt.shape[0] // C, dil, _stream()), "hfg_conv")
 
 
+def hfg_conv_f16(x, wf, bias, y, B, Tw, dil, slope, R=None, acc=None, alpha=1.0, acc_add=False, tiles=None):
+    """hfg_conv with fp16 operands on the 16-bit MFMA (a3t_hfg_conv_f16): leaky(x) is rounded to fp16 (saturated) on its way into
+    the product, wf holds the fp16 weight fragments [taps*C/16][C/32][64][8] of vocoder.pack_hifigan_conv_f16; C in {32, 64, 128,
+    256}.  Everything else, fp32 accumulation included, as hfg_conv."""
+    C = x.shape[-1]
+    if wf.dtype != torch.float16 or not wf.is_contiguous() or wf.dim() != 4 or C % 32 or tuple(wf.shape[1:]) != (C // 32, 64, 8) \
+            or wf.shape[0] % (C // 16):
+        raise ValueError(f"hfg_conv_f16: wf must be a contiguous fp16 [taps*{C // 16}][{C // 32}][64][8] tensor, got "
+                         f"{wf.dtype} {tuple(wf.shape)}")
+    for name, t in (("x", x), ("R", R), ("y", y), ("acc", acc)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != C or t.numel() != B * Tw * C):
+            raise ValueError(f"hfg_conv_f16: {name} must be a contiguous fp32 [{B * Tw}][{C}] tensor")
+    nbytes = 4 * B * Tw * C
+    for name, t in (("y", y), ("acc", acc)):      # as hfg_conv: no output may overlap the input, or the other output
+        for oname, o in (("x", x), ("acc", acc if name == "y" else None)):
+            if t is not None and o is not None and abs(t.data_ptr() - o.data_ptr()) < nbytes:
+                raise ValueError(f"hfg_conv_f16: {name} overlaps {oname}")
+    _ragged_f32("hfg_conv_f16", bias)
+    if bias is not None and bias.numel() != C:
+        raise ValueError(f"hfg_conv_f16: bias must have {C} entries")
+    tp, nt = _tile_list("hfg_conv_f16", tiles, B, Tw)
+    if nt < 0:
+        return
+    L.check(L.load().a3t_hfg_conv_f16(_ptr(x), _ptr(wf), _ptr(bias), _ptr(R), _ptr(y), _ptr(acc), alpha, int(bool(acc_add)), slope,
+                                      tp, nt, B, Tw, C, wf.shape[0] // (C // 16), dil, _stream()), "hfg_conv_f16")
+
+
 def hfg_out(x, w, bias, y, B, Tw, slope, tiles=None):
     """y [B*Tw] = tanh(bias + conv_K(leaky(x, slope))) (a3t_hfg_out): x fp32 [B*Tw][C], w [K][C] (tap, in channel), bias [1] or
     None.  tiles: as hfg_conv."""

@@ -342,6 +342,26 @@ def pack_hifigan_conv(w: torch.Tensor) -> torch.Tensor:
     return w.permute(2, 1, 0).reshape(k * Cin, Cout).contiguous()
 
 
+def pack_hifigan_conv_f16(w: torch.Tensor) -> torch.Tensor:
+    """Conv1d weight [Cout][Cin][k] fp32 (Cout = Cin = C, a multiple of 32) -> the fp16 operand of a3t_hfg_conv_f16 (pure torch, any
+    device): the MFMA's A fragments in the order the kernel streams them, P [k*C/16][C/32][64][8] with
+
+        P[ks][mt][l][j] = fp16(w[32*mt + (l & 31)][16*(ks % (C/16)) + 8*(l >> 5) + j][ks // (C/16)])
+
+    (k-step ks = tap-major, 16 input channels each; M-tile mt = 32 output channels; lane l; element j), rounded to nearest even and
+    saturated to +-65504."""
+    Cout, Cin, k = w.shape
+    if Cout != Cin or Cout % 32:
+        raise ValueError(f"pack_hifigan_conv_f16: weight {tuple(w.shape)} is not [C][C][k] with C a multiple of 32")
+    C = Cout
+    t = w.to(torch.float32).clamp(-65504.0, 65504.0).to(torch.float16)
+    t = t.permute(2, 1, 0).reshape(k, C // 16, 2, 8, C // 32, 32)      # [tap][ci / 16][l >> 5][j][mt][l & 31]
+    return t.permute(0, 1, 4, 2, 5, 3).reshape(k * (C // 16), C // 32, 64, 8).contiguous()
+
+
+F16_WIDTHS = (32, 64, 128, 256)      # the stage widths whose residual blocks compute="f16" moves to a3t_hfg_conv_f16
+
+
 class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
     """HiFi-GAN generator inference (espnet2/gan_tts/hifigan/hifigan.py:25-221, state-dict compatible with the
     parallel_wavegan zoo's HiFiGANGenerator), channels-last fp32 [B*T][C] on the device.
@@ -350,13 +370,24 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
     3-tap convolutions, pack_hifigan_upsample) on the exact-fp32 GEMM.  fused=True: the residual blocks of the stages with 32 or
     64 channels run on a3t_hfg_conv (LeakyReLU, bias, residual and the MRF mean inside the launch) and the output convolution
     on a3t_hfg_out; stages of another width run layer by layer.  fused=True is the default because it is the faster path on the v1
-    plan (profiles/hifigan_latency.txt: 46 ms against 83 ms for 8 x 1000 frames)."""
+    plan (profiles/hifigan_latency.txt: 46 ms against 83 ms for 8 x 1000 frames).
+
+    compute="f16" (opt-in; needs fused=True): the residual blocks of every stage with C in F16_WIDTHS and kernels <= 11 run on
+    a3t_hfg_conv_f16 -- in each of their convolutions leaky(x) is computed in fp32 and rounded to fp16 (nearest even, saturated
+    to +-65504), the weight is rounded to fp16 once here, after the fp64 weight-norm fold, products accumulate in fp32.  Biases,
+    residuals, the MRF mean and every tensor in memory stay fp32, and so do the input, transposed and output convolutions and
+    the stages of another width.  compute="f32" (the default) is the exact-fp32 path, bit for bit what it was."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", in_channels=80, channels=512, kernel_size=7,
                  upsample_scales: Sequence[int] = (5, 5, 4, 3), upsample_kernel_sizes: Sequence[int] = (10, 10, 8, 6),
                  resblock_kernel_sizes: Sequence[int] = (3, 7, 11), resblock_dilations=((1, 3, 5),) * 3,
                  use_additional_convs=True, bias=True, negative_slope=0.1, stats: Optional[Dict[str, np.ndarray]] = None,
-                 fused=True):
+                 fused=True, compute="f32"):
+        if compute not in ("f32", "f16"):
+            raise ValueError(f"compute must be 'f32' or 'f16', got {compute!r}")
+        if compute == "f16" and not fused:
+            raise ValueError("compute='f16' is a mode of the fused kernels: it needs fused=True")
+        self.compute = compute
         self.scales = tuple(int(s) for s in upsample_scales)
         self.rk = tuple(int(k) for k in resblock_kernel_sizes)
         self.rd = tuple(tuple(int(d) for d in ds) for ds in resblock_dilations)
@@ -396,9 +427,10 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
         self.stages = []
         for i, s in enumerate(self.scales):
             C = self.C0 >> (i + 1)
-            st = dict(C=C, s=s, w_up=pack_hifigan_upsample(w(f"upsamples.{i}.1"), s).to(self.dev),
+            f16 = compute == "f16" and C in F16_WIDTHS and max(self.rk) <= 11
+            st = dict(C=C, s=s, f16=f16, w_up=pack_hifigan_upsample(w(f"upsamples.{i}.1"), s).to(self.dev),
                       b_up=torch.as_tensor(np.asarray(state_dict[f"upsamples.{i}.1.bias"]), dtype=torch.float32).repeat(s).to(self.dev),
-                      fused=bool(fused) and C in (32, 64) and max(self.rk) <= 11, blocks=[])
+                      fused=f16 or (bool(fused) and C in (32, 64) and max(self.rk) <= 11), blocks=[])
             for j, (k, dils) in enumerate(zip(self.rk, self.rd)):
                 units = []
                 for d in range(len(dils)):
@@ -406,7 +438,8 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
                     names = [p + f"convs1.{d}.1"] + ([p + f"convs2.{d}.1"] if self.add else [])
                     ws = [w(n) for n in names]
                     units.append(dict(dil=dils[d], b=[b(n, C) for n in names],
-                                      w=[(pack_hifigan_conv(t).to(self.dev) if st["fused"] else conv(t)) for t in ws]))
+                                      w=[(pack_hifigan_conv_f16(t).to(self.dev) if f16 else
+                                          pack_hifigan_conv(t).to(self.dev) if st["fused"] else conv(t)) for t in ws]))
                 st["blocks"].append(dict(k=k, units=units))
             self.stages.append(st)
         Cl = self.C0 >> len(self.scales)
@@ -421,7 +454,7 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
     @classmethod
     def from_config(cls, state_dict, generator_params: Dict, generator_type: str = "HiFiGANGenerator", **kw):
         """From the `generator_params` (and `generator_type`) of a parallel_wavegan config.yml and the checkpoint's
-        model["generator"] state dict.  kw: device, stats, fused."""
+        model["generator"] state dict.  kw: device, stats, fused, compute."""
         if generator_type != "HiFiGANGenerator":
             raise NotImplementedError(f"generator_type {generator_type!r}: only HiFiGANGenerator is built here")
         p = dict(generator_params)
@@ -534,12 +567,13 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
         return cs
 
     def _stage_fused(self, st, up, B, T, rate, lens, tiles):
-        """The same on a3t_hfg_conv: the last convolution of block j leaves alpha * block_j in the mean's buffer (alpha =
-        1 / num_blocks), so block outputs are never stored.  Rows behind a row's end are not written by the kernel: the mean's
-        buffer starts as zeros there for the (unragged) convolution that reads it next."""
+        """The same on a3t_hfg_conv (a3t_hfg_conv_f16 for a stage of compute="f16"): the last convolution of block j leaves
+        alpha * block_j in the mean's buffer (alpha = 1 / num_blocks), so block outputs are never stored.  Rows behind a row's end
+        are not written by the kernel: the mean's buffer starts as zeros there for the (unragged) convolution that reads it next."""
         bufs = [torch.empty_like(up) for _ in range(3)]
         cs = torch.zeros_like(up) if lens is not None else torch.empty_like(up)
         alpha = 1.0 / len(st["blocks"])
+        conv = ops.hfg_conv_f16 if st["f16"] else ops.hfg_conv
         for j, blk in enumerate(st["blocks"]):
             x = up
             for u, unit in enumerate(blk["units"]):
@@ -550,9 +584,9 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
                     out = dict(y=xn)
                 src, dil = x, unit["dil"]
                 if self.add:
-                    ops.hfg_conv(x, unit["w"][0], unit["b"][0], xt, B, T, dil, self.slope, tiles=tiles)
+                    conv(x, unit["w"][0], unit["b"][0], xt, B, T, dil, self.slope, tiles=tiles)
                     src, dil = xt, 1
-                ops.hfg_conv(src, unit["w"][-1], unit["b"][-1], out.pop("y"), B, T, dil, self.slope, R=x, tiles=tiles, **out)
+                conv(src, unit["w"][-1], unit["b"][-1], out.pop("y"), B, T, dil, self.slope, R=x, tiles=tiles, **out)
                 x = xn
         return cs
 

@@ -459,7 +459,7 @@ int a3t_dropout_bwd_cast(const float* g, void* gm, int gm_dtype, float* colsum, 
  * b0 [128] permuted the same way.  wt1 [64][128] = conv1x1_out.weight^T (columns 0..63 residual, 64..127 skip), b1 [128]. */
 int a3t_pwg_block(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1,
                   float* g, float* skips, int B, int Tw, int dil, void* stream);
-/* The tile contract of the waveform kernels (a3t_pwg_block_ragged, a3t_pwg_block_f16, a3t_hfg_conv, a3t_hfg_out;
+/* The tile contract of the waveform kernels (a3t_pwg_block_ragged, a3t_pwg_block_f16, a3t_hfg_conv, a3t_hfg_conv_f16, a3t_hfg_out;
  * csrc/wave_tiles.h).  tiles == NULL (and ntiles == 0): every row is Tw samples long.  Else rows of different length: tiles
  * [ntiles][4] int32 on the device (16-byte aligned) = {row b, first sample t0 (multiple of 256), valid samples W_b <= Tw of row
  * b, 0}, one entry per 256-sample tile with t0 < W_b (the kernels trust the entries).  Row b is computed as if it were alone:
@@ -495,6 +495,14 @@ int a3t_cast_f16_sat(const float* src, void* dst, int64_t n, void* stream);
 int a3t_hfg_conv(const float* x, const float* wt, const float* bias, const float* R, float* y, float* acc, float alpha,
                  int acc_add, float slope, const int32_t* tiles, int ntiles, int B, int Tw, int C, int taps, int dil,
                  void* stream);
+/* a3t_hfg_conv with fp16 operands on v_mfma_f32_32x32x16_f16 (csrc/hifigan_f16.hip), C in {32, 64, 128, 256}: leaky(x) is
+ * computed in fp32 and rounded to nearest even to fp16, saturated to +-65504; the weight is fp16; products accumulate in fp32;
+ * bias, R, y and acc stay fp32.  wf: fp16 fragments [taps*C/16][C/32][64][8] (a3t_amd/vocoder.py::pack_hifigan_conv_f16),
+ *   wf[ks][mt][l][j] = fp16(W[out 32 mt + (l & 31)][in 16 (ks % (C/16)) + 8 (l >> 5) + j][tap ks / (C/16)]).
+ * Everything else as a3t_hfg_conv; x, wf, bias, R, y and acc 16-byte aligned. */
+int a3t_hfg_conv_f16(const float* x, const void* wf, const float* bias, const float* R, float* y, float* acc, float alpha,
+                     int acc_add, float slope, const int32_t* tiles, int ntiles, int B, int Tw, int C, int taps, int dil,
+                     void* stream);
 int a3t_hfg_out(const float* x, const float* w, const float* bias, float* y, float slope, const int32_t* tiles, int ntiles,
                 int B, int Tw, int C, int K, void* stream);
 int a3t_leaky_relu(const float* x, float* y, int64_t n, float slope, void* stream);
