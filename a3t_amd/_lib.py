@@ -113,6 +113,11 @@ _SIGS = {
     "a3t_hfg_conv_f16": [_P, _P, _P, _P, _P, _P, c_float, c_int, c_float, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "a3t_hfg_out": [_P, _P, _P, _P, c_float, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "a3t_leaky_relu": [_P, _P, c_int64, c_float, _P],
+    "a3t_mgan_stack": [_P, _P, _P, _P, c_float, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
+    "a3t_mgan_out": [_P, _P, _P, _P, c_float, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P],
+    "a3t_pqmf_synthesis": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
+    "a3t_reflect_pad_rows": [_P, _P, c_int64, c_int64, c_int, c_int, _P],
+    "a3t_reflect_pad_rows_ragged": [_P, _P, _P, c_int, c_int64, c_int64, c_int, c_int, _P],
     "a3t_duration_head": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P],
     "a3t_l2_normalize": [_P, _P, c_int, c_int, c_float, _P],
     "a3t_gst_conv_bn_relu": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P],

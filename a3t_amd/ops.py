@@ -744,6 +744,79 @@ def hfg_out(x, w, bias, y, B, Tw, slope, tiles=None):
     L.check(L.load().a3t_hfg_out(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), slope, tp, nt, B, Tw, C, w.shape[0], _stream()), "hfg_out")
 
 
+def _tile_wmin(tiles, wmin, Tw):
+    """The smallest W_b of a tile list for the kernels that reflect at a row's end: the caller's statement (host integers it
+    built the list from), else read back from the list (a device synchronisation: tests and one-off calls)."""
+    if tiles is None:
+        return Tw
+    if wmin is not None:
+        return int(wmin)
+    return int(tiles[:, 2].min().item()) if tiles.shape[0] else Tw
+
+
+def mgan_stack(x, w, bias, y, B, Tw, dil, slope, tiles=None, wmin=None):
+    """One MelGAN ResidualStack in one launch (a3t_mgan_stack): y = (bs + b2) + Ws x + W2 leaky(b1 + conv3_dil(leaky(reflect(x)))).
+    x / y fp32 [B*Tw][C], C in {48, 96, 192}; w / bias from vocoder.pack_melgan_stack.  y must not overlap x.  tiles: as hfg_conv;
+    wmin: the smallest W_b of the list (None: read from the list, which synchronises)."""
+    C = x.shape[-1]
+    Cp = (C + 31) // 32 * 32
+    for name, t in (("x", x), ("y", y)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != C or t.numel() != B * Tw * C:
+            raise ValueError(f"mgan_stack: {name} must be a contiguous fp32 [{B * Tw}][{C}] tensor")
+    if abs(x.data_ptr() - y.data_ptr()) < 4 * B * Tw * C:
+        raise ValueError("mgan_stack: y overlaps x")
+    _ragged_f32("mgan_stack", w, bias)
+    if tuple(w.shape) != (4 * C + Cp, Cp) or tuple(bias.shape) != (2, Cp):
+        raise ValueError(f"mgan_stack: w must be [{4 * C + Cp}][{Cp}] and bias [2][{Cp}], got {tuple(w.shape)} and {tuple(bias.shape)}")
+    tp, nt = _tile_list("mgan_stack", tiles, B, Tw)
+    if nt < 0:
+        return
+    L.check(L.load().a3t_mgan_stack(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), slope, tp, nt, _tile_wmin(tiles, wmin, Tw), B, Tw, C,
+                                    dil, _stream()), "mgan_stack")
+
+
+def mgan_out(x, w, bias, y, B, Tw, slope, tanh=True, tiles=None, wmin=None):
+    """y [B*Tw][O] = act(bias + conv_K(leaky(x, slope))) with reflection at each row's ends (a3t_mgan_out): x fp32 [B*Tw][C],
+    w [O][K][C] (out channel, tap, in channel), bias [O] or None, act = tanh or identity.  tiles / wmin: as mgan_stack."""
+    C = x.shape[-1]
+    _ragged_f32("mgan_out", x, w, bias, y)
+    if w.dim() != 3 or w.shape[2] != C or x.numel() != B * Tw * C or y.numel() != B * Tw * w.shape[0] \
+            or (bias is not None and bias.numel() != w.shape[0]):
+        raise ValueError("mgan_out: shapes do not fit")
+    tp, nt = _tile_list("mgan_out", tiles, B, Tw)
+    if nt < 0:
+        return
+    L.check(L.load().a3t_mgan_out(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), slope, int(bool(tanh)), tp, nt,
+                                  _tile_wmin(tiles, wmin, Tw), B, Tw, C, w.shape[0], w.shape[1], _stream()), "mgan_out")
+
+
+def pqmf_synthesis(x, h, y, B, Ts, tiles=None):
+    """PQMF synthesis (a3t_pqmf_synthesis): x fp32 [B*Ts][S] sub-band samples, h [S][taps + 1] synthesis filters -> y [B*Ts*S].
+    tiles: a list at the OUTPUT rate (Tw = Ts * S), as hfg_conv."""
+    _ragged_f32("pqmf_synthesis", x, h, y)
+    if h.dim() != 2 or x.shape[-1] != h.shape[0] or x.numel() != B * Ts * h.shape[0] or y.numel() != x.numel():
+        raise ValueError("pqmf_synthesis: shapes do not fit")
+    tp, nt = _tile_list("pqmf_synthesis", tiles, B, Ts * h.shape[0])
+    if nt < 0:
+        return
+    L.check(L.load().a3t_pqmf_synthesis(_ptr(x), _ptr(h), _ptr(y), tp, nt, B, Ts, h.shape[0], h.shape[1] - 1, _stream()),
+            "pqmf_synthesis")
+
+
+def reflect_pad_rows(x, y, pad, lens=None, mul=1):
+    """x [T][C] or [B][T][C] (contiguous fp32) -> y [.., T + 2 pad, C], reflected like torch.nn.ReflectionPad1d (a3t_reflect_pad_rows).
+    lens (device int32 [B]): row b is reflected at its own ends, its length being lens[b] * mul."""
+    B, T, C = _rows_lens("reflect_pad_rows", x, lens)
+    _ragged_f32("reflect_pad_rows", x, y)
+    if y.numel() != B * (T + 2 * pad) * C:
+        raise ValueError("reflect_pad_rows: shapes do not fit")
+    if lens is None:
+        rc = L.load().a3t_reflect_pad_rows(_ptr(x), _ptr(y), B, T, C, pad, _stream())
+    else:
+        rc = L.load().a3t_reflect_pad_rows_ragged(_ptr(x), _ptr(y), _ptr(lens), mul, B, T, C, pad, _stream())
+    L.check(rc, "reflect_pad_rows")
+
+
 def splice_spans(after, speech, speech_mask, spans, out, lens):
     """out[b][t] = after[b][t] inside spans[b], speech[b][t] for the other valid frames, 0 behind the row's length (the sum of
     its speech_mask, written to lens).  after / speech [B][Tin][C] fp32, speech_mask [B][Tin] bool / uint8, out [B][Tout][C]."""

@@ -8,7 +8,8 @@ parallel_wavegan/upsample.py:22-189), weight-norm removed.  Layout is channels-l
 Conv1d (dilated k=3, 1x1) is the shared implicit-im2col MFMA GEMM; the gated activation, residual /
 skip update and nearest-neighbour upsampling+smoothing are element-wise HIP kernels.
 
-HiFiGANGeneratorHIP (below) is the second generator family of the same model zoo, with the same inference interface.
+HiFiGANGeneratorHIP and MelGANGeneratorHIP (below) are the second and third generator family of the same model zoo, with the
+same inference interface; generator_from_config picks the class from a checkpoint's config.
 """
 import math
 import os
@@ -591,3 +592,353 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
         return cs
 
     __call__ = inference
+
+
+# ------------------------------------------------------------------------------- MelGAN / multi-band MelGAN generator
+def melgan_margin_frames(upsample_scales: Sequence[int] = (5, 5, 3), stacks: int = 4, stack_kernel_size: int = 3,
+                         kernel_size: int = 7, out_channels: int = 4, pqmf_taps: int = 62) -> int:
+    """pwg_margin_frames for the MelGAN generator, walked from the output back to the mel like hifigan_margin_frames: the PQMF
+    synthesis filter reaches ceil((taps / 2) / subbands) sub-band samples (multi-band only), the output convolution (K-1)/2; the
+    residual stacks of a stage sum_j (ks-1)/2 * ks^j of its samples (their 1x1 convolutions none); a transposed convolution of
+    scale s turns a reach of n into ceil(n / s) + 1; the input convolution adds (K-1)/2 frames.  Reflection does not widen the
+    reach: it happens at an utterance's ends only, which a clipped window shares.  15 for the multi-band v2 plan."""
+    S, ks = int(out_channels), int(stack_kernel_size)
+    n = -(-(int(pqmf_taps) // 2) // S) if S > 1 else 0
+    n += (int(kernel_size) - 1) // 2
+    reach = sum((ks - 1) // 2 * ks ** j for j in range(int(stacks)))
+    for s in reversed([int(s) for s in upsample_scales]):
+        n = -(-(n + reach) // s) + 1
+    return n + (int(kernel_size) - 1) // 2
+
+
+def melgan_min_frames(upsample_scales: Sequence[int] = (5, 5, 3), stacks: int = 4, stack_kernel_size: int = 3,
+                      kernel_size: int = 7) -> int:
+    """The smallest number of frames for which every reflection of the plan is legal (ReflectionPad1d needs pad < length): the
+    input convolution pads (K-1)/2 frames, the widest stack of stage i (ks-1)/2 * ks^(stacks-1) samples at prod(scales[:i+1])
+    samples per frame, the output convolution (K-1)/2 samples at the last rate.  6 for the v2 plan."""
+    half, ks = (int(kernel_size) - 1) // 2, int(stack_kernel_size)
+    need, rate = half + 1, 1
+    dmax = (ks - 1) // 2 * ks ** (int(stacks) - 1) if stacks else 0
+    for s in upsample_scales:
+        rate *= int(s)
+        need = max(need, dmax // rate + 1)
+    return max(need, half // rate + 1)
+
+
+def pqmf_synthesis_filter(subbands: int = 4, taps: int = 62, cutoff_ratio: float = 0.142, beta: float = 9.0) -> np.ndarray:
+    """The synthesis filters [subbands][taps + 1] of the reference's PQMF (pqmf.py:17-53, 88-115: a Kaiser-windowed sinc prototype,
+    cosine modulated), computed in fp64 with numpy alone and rounded to fp32 -- the precision the reference holds them in, also in
+    its .double() model."""
+    if taps % 2 or not 0.0 < cutoff_ratio < 1.0:
+        raise ValueError("pqmf: taps must be even and 0 < cutoff_ratio < 1")
+    n = np.arange(taps + 1) - 0.5 * taps
+    with np.errstate(invalid="ignore", divide="ignore"):
+        h = np.sin(np.pi * cutoff_ratio * n) / (np.pi * n)
+    h[taps // 2] = np.cos(0) * cutoff_ratio
+    h = h * np.kaiser(taps + 1, beta)
+    out = np.zeros((subbands, taps + 1))
+    for k in range(subbands):
+        out[k] = 2 * h * np.cos((2 * k + 1) * (np.pi / (2 * subbands)) * (np.arange(taps + 1) - (taps / 2)) - (-1) ** k * np.pi / 4)
+    return out.astype(np.float32)
+
+
+MGAN_WIDTHS = (48, 96, 192)      # the stage widths a3t_mgan_stack is built for
+
+
+def melgan_hidden_order(Cp: int) -> np.ndarray:
+    """Hidden channel of row 16 q + 2 kk + lk of a3t_mgan_stack's W2 operand: the channel that register r = 8 (q & 1) + kk of
+    accumulator block q >> 1 holds in lane half lk."""
+    row = np.arange(Cp)
+    q, kk, lk = row // 16, (row % 16) // 2, row % 2
+    r = 8 * (q & 1) + kk
+    return 32 * (q >> 1) + (r & 3) + 8 * (r >> 2) + 4 * lk
+
+
+def pack_melgan_stack(w1, b1, w2, b2, ws, bs):
+    """Operands of a3t_mgan_stack from one ResidualStack's parameters (pure; CPU or device tensors): w1 [C][C][3] dilated conv,
+    w2 [C][C][1] and ws [C][C][1] (skip_layer), biases [C] or None -> w [4 C + Cp][Cp] (Cp = C rounded up to 32): rows tap*C + in
+    channel of w1, then the in channels of ws, then Cp rows of w2 in melgan_hidden_order, columns = out channels, zero where a
+    row or column is >= C;  bias [2][Cp] = b1 | bs + b2, zero-padded."""
+    w1 = torch.as_tensor(w1, dtype=torch.float32)
+    C = w1.shape[0]
+    if tuple(w1.shape) != (C, C, 3) or tuple(w2.shape) != (C, C, 1) or tuple(ws.shape) != (C, C, 1) or C % 16:
+        raise ValueError(f"pack_melgan_stack: weights {tuple(w1.shape)} / {tuple(w2.shape)} / {tuple(ws.shape)} are not a "
+                         "ResidualStack of kernel size 3 and a width that is a multiple of 16")
+    Cp = (C + 31) // 32 * 32
+    dev = w1.device
+    w = torch.zeros(4 * C + Cp, Cp, dtype=torch.float32, device=dev)
+    w[:3 * C, :C] = w1.permute(2, 1, 0).reshape(3 * C, C)
+    w[3 * C:4 * C, :C] = torch.as_tensor(ws, dtype=torch.float32).to(dev)[:, :, 0].t()
+    w2t = torch.zeros(Cp, Cp, dtype=torch.float32, device=dev)
+    w2t[:C, :C] = torch.as_tensor(w2, dtype=torch.float32).to(dev)[:, :, 0].t()      # [hidden][out]
+    w[4 * C:] = w2t[torch.as_tensor(melgan_hidden_order(Cp), device=dev)]
+    bias = torch.zeros(2, Cp, dtype=torch.float32, device=dev)
+    if b1 is not None:
+        bias[0, :C] = torch.as_tensor(b1, dtype=torch.float32).to(dev)
+    for v in (bs, b2):
+        if v is not None:
+            bias[1, :C] += torch.as_tensor(v, dtype=torch.float32).to(dev)
+    return w.contiguous(), bias
+
+
+class MelGANGeneratorHIP(_WaveGeneratorHIP):
+    """MelGAN / multi-band MelGAN generator inference (espnet2/gan_tts/melgan/melgan.py:22-199, residual_stack.py:16-71,
+    pqmf.py:56-160; state-dict compatible with the parallel_wavegan zoo's MelGANGenerator), channels-last fp32 [B*T][C] on the
+    device.  Every non-transposed convolution reflects at the ends of the row it belongs to (ReflectionPad1d), so an input needs
+    min_frames frames; out_channels > 1 is the multi-band form, whose sub-bands the PQMF synthesis filter bank (a3t_pqmf_synthesis)
+    turns into the waveform: upsample_factor = prod(upsample_scales) * out_channels.
+
+    fused=False: layer by layer -- a3t_leaky_relu, a3t_reflect_pad_rows, the convolution on the exact-fp32 GEMM over the padded
+    rows, the interior sliced out.  fused=True: the residual stacks of the stages whose width is in MGAN_WIDTHS run on
+    a3t_mgan_stack, one launch each, and the output convolution on a3t_mgan_out where it fits (C <= 64, out_channels <= 4,
+    K <= 11); the rest runs layer by layer.  fused=True is the default because it is the faster path on the v2 plan
+    (profiles/melgan_latency.txt: 4.3 ms against 11.3 ms for 8 x 1000 frames)."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", in_channels=80, out_channels=4, kernel_size=7,
+                 channels=384, upsample_scales: Sequence[int] = (5, 5, 3), stack_kernel_size=3, stacks=4, bias=True,
+                 negative_slope=0.2, use_final_nonlinear_activation=True, pqmf: Optional[Dict] = None,
+                 stats: Optional[Dict[str, np.ndarray]] = None, fused=True):
+        self.scales = tuple(int(s) for s in upsample_scales)
+        self.K, self.ks, self.nstacks, self.O = int(kernel_size), int(stack_kernel_size), int(stacks), int(out_channels)
+        if self.K % 2 == 0 or self.ks % 2 == 0:
+            raise ValueError(f"kernel_size {kernel_size} and stack_kernel_size {stack_kernel_size} must be odd")
+        if channels % (2 ** len(self.scales)):
+            raise ValueError(f"channels {channels} must be divisible by 2^{len(self.scales)}")
+        if self.O < 1:
+            raise ValueError(f"out_channels {out_channels} must be positive")
+        self._setup(device, in_channels, stats)
+        self.C0, self.slope, self.final_tanh = int(channels), float(negative_slope), bool(use_final_nonlinear_activation)
+        self.upsample_factor = int(np.prod(self.scales)) * self.O
+        self.pqmf = dict(dict(taps=62, cutoff_ratio=0.142, beta=9.0), **(pqmf or {})) if self.O > 1 else None
+        if self.pqmf is not None:
+            if self.O > 8 or self.pqmf["taps"] > 254:
+                raise NotImplementedError(f"pqmf: {self.O} sub-bands / {self.pqmf['taps']} taps: a3t_pqmf_synthesis is built for <= 8 / <= 254")
+            self.h_syn = torch.from_numpy(pqmf_synthesis_filter(self.O, **self.pqmf)).to(self.dev)
+        self.min_frames = melgan_min_frames(self.scales, self.nstacks, self.ks, self.K)
+
+        def w(p):
+            return fold_weight_norm(state_dict, p)
+
+        def b(p, n, rep=1):
+            if not bias and p + ".bias" not in state_dict:
+                return None
+            v = torch.as_tensor(np.asarray(state_dict[p + ".bias"]), dtype=torch.float32)
+            if v.numel() != n:
+                raise ValueError(f"{p}.bias has {v.numel()} entries, expected {n}")
+            return v.repeat(rep).contiguous().to(self.dev)
+
+        def conv(t):              # (out, in, taps) -> [out][tap][in]
+            return t.permute(0, 2, 1).contiguous().to(self.dev)
+
+        # the reference's Sequential: 0 pad, 1 conv | per stage: activation, transposed conv, `stacks` ResidualStacks | activation,
+        # pad, conv (, tanh)
+        self.w_in, self.b_in = conv(w("melgan.1")), b("melgan.1", self.C0)
+        if tuple(self.w_in.shape) != (self.C0, self.K, self.A):
+            raise ValueError(f"melgan.1.weight {tuple(self.w_in.shape)} does not fit channels / kernel_size / in_channels")
+        self.stages, idx = [], 2
+        for i, s in enumerate(self.scales):
+            C = self.C0 >> (i + 1)
+            st = dict(C=C, s=s, fused=bool(fused) and C in MGAN_WIDTHS and self.ks == 3, stacks=[],
+                      w_up=pack_hifigan_upsample(w(f"melgan.{idx + 1}"), s).to(self.dev), b_up=b(f"melgan.{idx + 1}", C, s))
+            for j in range(self.nstacks):
+                p = f"melgan.{idx + 2 + j}."
+                raw = (w(p + "stack.2"), b(p + "stack.2", C), w(p + "stack.4"), b(p + "stack.4", C), w(p + "skip_layer"),
+                       b(p + "skip_layer", C))
+                if tuple(raw[0].shape) != (C, C, self.ks):
+                    raise ValueError(f"{p}stack.2.weight {tuple(raw[0].shape)} is not ({C}, {C}, {self.ks})")
+                unit = dict(dil=self.ks ** j)
+                if st["fused"]:
+                    unit["w"], unit["b"] = (t.to(self.dev) for t in pack_melgan_stack(*raw))
+                else:
+                    unit.update(w1=conv(raw[0]), b1=raw[1], w2=raw[2].reshape(C, C).contiguous().to(self.dev), b2=raw[3],
+                                ws=raw[4].reshape(C, C).contiguous().to(self.dev), bs=raw[5])
+                st["stacks"].append(unit)
+            self.stages.append(st)
+            idx += 2 + self.nstacks
+        Cl = self.C0 >> len(self.scales)
+        self.w_out, self.b_out = conv(w(f"melgan.{idx + 2}")), b(f"melgan.{idx + 2}", self.O)      # [O][K][Cl]
+        if tuple(self.w_out.shape) != (self.O, self.K, Cl):
+            raise ValueError(f"melgan.{idx + 2}.weight {tuple(self.w_out.shape)} does not fit out_channels / kernel_size / channels")
+        self.fused_out = bool(fused) and Cl <= 64 and Cl % 2 == 0 and self.O <= 4 and self.K <= 11
+        self.fused = self.fused_out or any(st["fused"] for st in self.stages)
+
+    @classmethod
+    def from_config(cls, state_dict, generator_params: Dict, generator_type: str = "MelGANGenerator",
+                    pqmf_params: Optional[Dict] = None, **kw):
+        """From the `generator_params`, `generator_type` and `pqmf_params` of a parallel_wavegan config.yml and the checkpoint's
+        model["generator"] state dict.  kw: device, stats, fused."""
+        if generator_type != "MelGANGenerator":
+            raise NotImplementedError(f"generator_type {generator_type!r}: MelGANGeneratorHIP builds MelGANGenerator only")
+        p = dict(generator_params)
+        pad = p.pop("pad", "ReflectionPad1d")
+        if pad != "ReflectionPad1d":
+            raise NotImplementedError(f"pad {pad!r}: only ReflectionPad1d is built into the kernels")
+        if p.pop("pad_params", None):
+            raise NotImplementedError("pad_params must be empty (ReflectionPad1d takes none)")
+        act = p.pop("nonlinear_activation", "LeakyReLU")
+        if act != "LeakyReLU":
+            raise NotImplementedError(f"nonlinear_activation {act!r}: only LeakyReLU is built into the kernels")
+        if p.pop("use_causal_conv", False):
+            raise NotImplementedError("use_causal_conv is not supported")
+        ap = dict(p.pop("nonlinear_activation_params", None) or {"negative_slope": 0.2})
+        p.pop("use_weight_norm", None)      # the state dict says which form it holds
+        known = ("in_channels", "out_channels", "kernel_size", "channels", "upsample_scales", "stack_kernel_size", "stacks", "bias",
+                 "use_final_nonlinear_activation")
+        unknown = sorted(set(p) - set(known))
+        if unknown:
+            raise NotImplementedError(f"generator_params {unknown} are not understood")
+        p.setdefault("out_channels", 1)      # (the reference constructor's defaults, where they differ from this class's)
+        p.setdefault("channels", 512)
+        p.setdefault("upsample_scales", [8, 8, 2, 2])
+        p.setdefault("stacks", 3)
+        pq = dict(pqmf_params or {})
+        if int(pq.pop("subbands", p["out_channels"])) != int(p["out_channels"]) and int(p["out_channels"]) > 1:
+            raise NotImplementedError("pqmf_params.subbands must equal generator_params.out_channels")
+        bad = sorted(set(pq) - {"taps", "cutoff_ratio", "beta"})
+        if bad:
+            raise NotImplementedError(f"pqmf_params {bad} are not understood")
+        return cls(state_dict, negative_slope=float(ap.get("negative_slope", 0.01)), pqmf=pq, **p, **kw)
+
+    @property
+    def margin_frames(self) -> int:
+        return melgan_margin_frames(self.scales, self.nstacks, self.ks, self.K, self.O, self.pqmf["taps"] if self.pqmf else 0)
+
+    @torch.no_grad()
+    def inference(self, c: torch.Tensor, z: Optional[torch.Tensor] = None, normalize_before: bool = False,
+                  lengths: Optional[Sequence[int]] = None):
+        """c (T_feats, aux) [or (B, T_feats, aux)] -> (T_wav, 1) [or (B, T_wav, 1)]; z must be None (MelGAN has no noise input).
+
+        lengths (host integers, one per row of a (B, Tmax, aux) batch): row b is computed exactly as if c[b, :L_b] had been
+        passed alone -- every reflection happens at the row's own ends at that layer's rate, the transposed convolutions and the
+        PQMF filter read zeros behind them -- and the result (B, Tmax * hop, 1) is zero behind L_b * hop.  What the padding of c
+        holds reaches no valid sample.  An input, or a row that is not empty, needs min_frames frames (ValueError)."""
+        if z is not None:
+            raise ValueError("MelGANGeneratorHIP.inference: z must be None, the MelGAN generator has no noise input")
+        rows = [int(n) for n in lengths] if lengths is not None else [c.shape[-2]]
+        short = [n for n in rows if n < self.min_frames and (n > 0 or lengths is None)]      # (a length of 0 is an empty row)
+        if short:
+            raise ValueError(f"MelGANGeneratorHIP.inference: {short[0]} frames are fewer than min_frames = {self.min_frames} "
+                             "(a reflection must be shorter than the signal it pads)")
+        rates, r = [], 1      # the rates of the tiled kernels
+        for st in self.stages:
+            r *= st["s"]
+            if st["fused"]:
+                rates.append(r)
+        if self.fused_out and r not in rates:
+            rates.append(r)
+        if self.pqmf is not None and r * self.O not in rates:
+            rates.append(r * self.O)
+        c, single, lens, tiles = self.prepare(c, normalize_before, lengths, rates)
+        B, Tf, A = c.shape
+        dev, half = self.dev, (self.K - 1) // 2
+        Lmin = min([int(n) for n in lengths if int(n) > 0], default=Tf) if lengths is not None else Tf
+
+        def tail(x, rate, T):
+            if lens is not None:
+                ops.zero_tail(x, lens, rate, B, T)
+
+        def buf(T, C):      # the tiled kernels write nothing behind a row's end: what reads it next finds zeros there
+            return (torch.zeros if lens is not None else torch.empty)(B * T, C, device=dev)
+
+        c = c.contiguous()
+        if lens is not None:      # (a copy: c may be the caller's tensor)
+            c = c.clone()
+            tail(c, 1, Tf)
+        x = self._conv_reflect(c.view(B * Tf, A), self.w_in, self.b_in, B, Tf, half, 1, lens, 1)
+        tail(x, 1, Tf)
+        T, rate = Tf, 1
+        for st in self.stages:
+            C, s = st["C"], st["s"]
+            up = torch.empty(B * T, s * C, device=dev)
+            ops.conv_fwd(self._lrelu(x), st["w_up"], up, T, 1, bias=st["b_up"], compute=F32)
+            T, rate = T * s, rate * s
+            x = up.view(B * T, C)
+            tail(x, rate, T)
+            pp = [buf(T, C), buf(T, C)] if st["fused"] else None
+            for j, u in enumerate(st["stacks"]):
+                if st["fused"]:
+                    ops.mgan_stack(x, u["w"], u["b"], pp[j % 2], B, T, u["dil"], self.slope, tiles.get(rate), Lmin * rate)
+                    x = pp[j % 2]
+                else:
+                    x = self._stack_layers(u, x, B, T, rate, lens)
+            if not st["fused"]:
+                tail(x, rate, T)
+        if self.fused_out:
+            y = buf(T, self.O)
+            ops.mgan_out(x, self.w_out, self.b_out, y, B, T, self.slope, self.final_tanh, tiles.get(rate), Lmin * rate)
+        else:
+            y = self._conv_reflect(self._lrelu(x), self.w_out, self.b_out, B, T, half, 1, lens, rate,
+                                   ACT_TANH if self.final_tanh else 0)
+            tail(y, rate, T)
+        if self.pqmf is not None:
+            wav = buf(T * self.O, 1)
+            ops.pqmf_synthesis(y, self.h_syn, wav, B, T, tiles.get(rate * self.O))
+            T *= self.O
+        else:
+            wav = y
+        wav = wav.view(B, T, 1)
+        return wav[0] if single else wav
+
+    def _lrelu(self, x):
+        y = torch.empty_like(x)
+        ops.leaky_relu(x, y, self.slope)
+        return y
+
+    def _conv_reflect(self, x, w, bias, B, T, half, dil, lens, rate, act=0):
+        """conv(reflect_pad(x)) layer by layer, the convolution of 2 half + 1 taps at dilation dil: x [B*T][Cin] is padded by
+        half * dil rows at each row's own ends, convolved on the exact-fp32 GEMM over the padded rows and the interior sliced out
+        -> [B*T][Cout]."""
+        pad = half * dil
+        Tp, N = T + 2 * pad, w.shape[0]
+        xp = torch.empty(B * Tp, x.shape[1], device=self.dev)
+        ops.reflect_pad_rows(x.view(B, T, -1), xp, pad, lens, rate)
+        yp = torch.empty(B * Tp, N, device=self.dev)
+        ops.conv_fwd(xp, w, yp, Tp, half, dil, bias=bias, act=act, compute=F32)
+        return yp.view(B, Tp, N)[:, pad:pad + T].reshape(B * T, N)
+
+    def _stack_layers(self, u, x, B, T, rate, lens):
+        """One ResidualStack layer by layer: skip_1x1(x) + conv_1x1(leaky(conv_dilated(reflect_pad(leaky(x)))))."""
+        C = x.shape[1]
+        h = self._conv_reflect(self._lrelu(x), u["w1"], u["b1"], B, T, (self.ks - 1) // 2, u["dil"], lens, rate)
+        sk = torch.empty(B * T, C, device=self.dev)
+        ops.linear_fwd(x, u["ws"], sk, bias=u["bs"], compute=F32)
+        y = torch.empty(B * T, C, device=self.dev)
+        ops.linear_fwd(self._lrelu(h), u["w2"], y, bias=u["b2"], R=sk, compute=F32)
+        return y
+
+    __call__ = inference
+
+
+# ------------------------------------------------------------------------------------------ a generator from a config
+_PWG_KNOWN = ("layers", "stacks", "residual_channels", "gate_channels", "skip_channels", "aux_channels", "aux_context_window",
+              "upsample_params")
+_PWG_FIXED = dict(in_channels=1, out_channels=1, kernel_size=3, dropout=0.0, dropout_rate=0.0, bias=True,
+                  use_causal_conv=False, upsample_conditional_features=True, upsample_net="ConvInUpsampleNetwork")
+
+
+def generator_from_config(state_dict, config: Dict, **kw):
+    """The generator class of a parallel_wavegan checkpoint's config (the dict of its config.yml: generator_type,
+    generator_params and, for multi-band MelGAN, pqmf_params) over the checkpoint's model["generator"] state dict: what the
+    reference driver's load_vocoder(tag) does once the files are on disk.  kw: device, stats, fused (and compute, where the class
+    has it)."""
+    gtype = config.get("generator_type", "ParallelWaveGANGenerator")
+    params = dict(config.get("generator_params") or {})
+    if gtype == "MelGANGenerator":
+        return MelGANGeneratorHIP.from_config(state_dict, params, gtype, pqmf_params=config.get("pqmf_params"), **kw)
+    if gtype == "HiFiGANGenerator":
+        return HiFiGANGeneratorHIP.from_config(state_dict, params, gtype, **kw)
+    if gtype != "ParallelWaveGANGenerator":
+        raise NotImplementedError(f"generator_type {gtype!r}: ParallelWaveGANGenerator, HiFiGANGenerator and MelGANGenerator are built here")
+    params.pop("use_weight_norm", None)
+    for k, v in _PWG_FIXED.items():
+        if k in params and params.pop(k) != v:
+            raise NotImplementedError(f"generator_params.{k}: only {v!r} is built into ParallelWaveGANGeneratorHIP")
+    unknown = sorted(set(params) - set(_PWG_KNOWN))
+    if unknown:
+        raise NotImplementedError(f"generator_params {unknown} are not understood")
+    up = dict(params.pop("upsample_params", None) or {})
+    if "upsample_scales" in up:
+        params["upsample_scales"] = up.pop("upsample_scales")
+    if up:
+        raise NotImplementedError(f"generator_params.upsample_params {sorted(up)} are not understood")
+    return ParallelWaveGANGeneratorHIP(state_dict, **params, **kw)

@@ -459,7 +459,7 @@ int a3t_dropout_bwd_cast(const float* g, void* gm, int gm_dtype, float* colsum, 
  * b0 [128] permuted the same way.  wt1 [64][128] = conv1x1_out.weight^T (columns 0..63 residual, 64..127 skip), b1 [128]. */
 int a3t_pwg_block(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1,
                   float* g, float* skips, int B, int Tw, int dil, void* stream);
-/* The tile contract of the waveform kernels (a3t_pwg_block_ragged, a3t_pwg_block_f16, a3t_hfg_conv, a3t_hfg_conv_f16, a3t_hfg_out;
+/* The tile contract of the waveform kernels (a3t_pwg_block_ragged, a3t_pwg_block_f16, a3t_hfg_conv, a3t_hfg_conv_f16, a3t_hfg_out, a3t_mgan_*, a3t_pqmf_synthesis;
  * csrc/wave_tiles.h).  tiles == NULL (and ntiles == 0): every row is Tw samples long.  Else rows of different length: tiles
  * [ntiles][4] int32 on the device (16-byte aligned) = {row b, first sample t0 (multiple of 256), valid samples W_b <= Tw of row
  * b, 0}, one entry per 256-sample tile with t0 < W_b (the kernels trust the entries).  Row b is computed as if it were alone:
@@ -506,6 +506,38 @@ int a3t_hfg_conv_f16(const float* x, const void* wf, const float* bias, const fl
 int a3t_hfg_out(const float* x, const float* w, const float* bias, float* y, float slope, const int32_t* tiles, int ntiles,
                 int B, int Tw, int C, int K, void* stream);
 int a3t_leaky_relu(const float* x, float* y, int64_t n, float slope, void* stream);
+
+/* MelGAN / multi-band MelGAN generator kernels (espnet2/gan_tts/melgan/melgan.py:22-199, residual_stack.py:16-71, pqmf.py:56-160;
+ * csrc/melgan.hip), fp32 channels-last [B*Tw][C] on the tile contract above with ONE difference: a tap beyond a row's end is not
+ * zero but reflected at the row's own ends (torch.nn.ReflectionPad1d): refl(ts) = -ts for ts < 0, 2 (W_b - 1) - ts for ts >= W_b.
+ * The tile list lives on the device, so the caller states wmin, the smallest W_b of the listed rows (ignored for tiles == NULL,
+ * where it is Tw): a reflection that does not fit it is A3T_EINVAL (in the kernels such an index is clamped into the row).
+ * a3t_mgan_stack: one ResidualStack in one launch, C in {48, 96, 192}, kernel size 3, dil >= 1, dil < W_b:
+ *   h[t] = leaky(b1 + sum_{tap,c} W1[tap][c][:] * leaky(x[refl(t + (tap - 1) * dil)][c])),  y[t] = (bs + b2) + Ws x[t] + W2 h[t];
+ *   h stays in registers.  With Cp = C rounded up to 32: w [4 C + Cp][Cp], rows tap*C + c of W1 (in -> out), then C rows of the
+ *   skip 1x1 Ws, then Cp rows of W2 in the order of the MFMA accumulator (row 16 q + 2 kk + lk = hidden channel
+ *   32 (q >> 1) + (r & 3) + 8 (r >> 2) + 4 lk with r = 8 (q & 1) + kk), columns and rows >= C zero; bias [2][Cp] = b1 | bs + b2,
+ *   zero-padded (a3t_amd/vocoder.py::pack_melgan_stack).  y must not be x (tiles read each other's halo).  Exact fp32 products
+ *   (v_mfma_f32_32x32x2f32); x, w, bias, y 16-byte aligned.  A sample's result does not depend on its tile or on the other rows.
+ * a3t_mgan_out: y[t][o] = act(bias[o] + sum_{tap,c} w[o][tap][c] * leaky(x[refl(t + tap - (K-1)/2)][c])), x [B*Tw][C] ->
+ *   y [B*Tw][O]; C even <= 64, O <= 4, K odd <= 11, (K-1)/2 < W_b, act = tanh (act_tanh != 0) or identity; bias may be NULL.
+ * a3t_pqmf_synthesis: x [B*Ts][S] sub-band samples -> y [B*Ts*S],
+ *   y[n] = S * sum_{q,k} h[k][S q - n + taps/2] * x[q][k] over 0 <= q < W_b / S and 0 <= S q - n + taps/2 <= taps (zeros beyond the
+ *   row's end); h [S][taps + 1] the synthesis filters; S <= 8, taps even <= 254; tiles are counted in OUTPUT samples (Tw = Ts * S,
+ *   W_b a multiple of S); x 16-byte aligned for S = 4.
+ * a3t_reflect_pad_rows: x [B][T][C] -> y [B][T + 2 pad][C], y[b][u] = x[b][refl(u - pad)], pad < T.  _ragged: over the row's own
+ *   length lens[b] * mul (lens [B] int32 on the device; an empty row gives zeros, an index one reflection does not reach is
+ *   clamped into the row).
+ * Rows behind W_b are neither read nor written by the first three.  A3T_EINVAL for anything outside these contracts. */
+int a3t_mgan_stack(const float* x, const float* w, const float* bias, float* y, float slope, const int32_t* tiles, int ntiles,
+                   int wmin, int B, int Tw, int C, int dil, void* stream);
+int a3t_mgan_out(const float* x, const float* w, const float* bias, float* y, float slope, int act_tanh, const int32_t* tiles,
+                 int ntiles, int wmin, int B, int Tw, int C, int O, int K, void* stream);
+int a3t_pqmf_synthesis(const float* x, const float* h, float* y, const int32_t* tiles, int ntiles, int B, int Ts, int S,
+                       int taps, void* stream);
+int a3t_reflect_pad_rows(const float* x, float* y, int64_t B, int64_t T, int C, int pad, void* stream);
+int a3t_reflect_pad_rows_ragged(const float* x, float* y, const int32_t* lens, int mul, int64_t B, int64_t T, int C, int pad,
+                                void* stream);
 
 /* On-device half of MLMCollateFn (espnet2/train/collate_fn.py:330-385): masked_position, speech / text segment ids and the
  * two padding masks painted from integer span lists.  fs / fe [B][P] int32: frame span of phone j (floor(fs * t / hop) taken
