@@ -118,6 +118,9 @@ _SIGS = {
     "a3t_pqmf_synthesis": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "a3t_reflect_pad_rows": [_P, _P, c_int64, c_int64, c_int, c_int, _P],
     "a3t_reflect_pad_rows_ragged": [_P, _P, _P, c_int, c_int64, c_int64, c_int, c_int, _P],
+    "a3t_smg_conv": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                     c_int, _P],
+    "a3t_smg_stats": [_P, _P, _P, c_float, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_duration_head": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P],
     "a3t_l2_normalize": [_P, _P, c_int, c_int, c_float, _P],
     "a3t_gst_conv_bn_relu": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P],

@@ -803,6 +803,56 @@ def pqmf_synthesis(x, h, y, B, Ts, tiles=None):
             "pqmf_synthesis")
 
 
+SMG_PLAIN, SMG_TADE, SMG_GATE = 0, 1, 2
+
+
+def smg_conv(x, wt, bias, y, B, Tw, dil=1, up=1, mode=SMG_PLAIN, m=None, stats=None, ux=1, R=None, ur=1, sigmoid=False,
+             tiles=None):
+    """One convolution of a StyleMelGAN TADEResBlock (a3t_smg_conv): v = bias + conv(x nearest-upsampled by `up`), then
+    mode SMG_PLAIN: y = v (wt [taps*Cin][64]);  SMG_TADE: y = v[:, :64] * instance_norm(m upsampled by ux) + v[:, 64:] with
+    stats [B][2][64] = mean | rstd of m (smg_stats);  SMG_GATE: y = softmax(v[:, :64], channels) (or sigmoid) * tanh(v[:, 64:])
+    (+ R upsampled by ur) (both wt [taps*Cin][128]).  x fp32 [B*ceil(Tw/up)][Cin], Cin a multiple of 16; m / R [B*ceil(Tw/u)][64];
+    y [B*Tw][64], overlapping neither x nor m; wt k-major (vocoder.pack_hifigan_conv), taps odd <= 9.  tiles: as hfg_conv."""
+    Cin = x.shape[-1]
+    N = 64 if mode == SMG_PLAIN else 128
+    _ragged_f32("smg_conv", x, wt, bias, m, stats, R, y)
+    if wt.dim() != 2 or wt.shape[1] != N or wt.shape[0] % Cin:
+        raise ValueError(f"smg_conv: wt must be [taps*{Cin}][{N}], got {tuple(wt.shape)}")
+    for name, t, u, C in (("x", x, up, Cin), ("m", m, ux, 64), ("R", R, ur, 64), ("y", y, 1, 64)):
+        if t is not None and (u < 1 or t.shape[-1] != C or t.numel() != B * -(-Tw // u) * C):
+            raise ValueError(f"smg_conv: {name} must be a contiguous fp32 [{B * -(-Tw // max(u, 1))}][{C}] tensor")
+    if mode == SMG_TADE and (m is None or stats is None or stats.numel() != B * 128):
+        raise ValueError(f"smg_conv: the TADE epilogue needs m and stats [{B}][2][64]")
+    for name, o in (("x", x), ("m", m if mode == SMG_TADE else None)):      # other tiles read x[t +- halo] and m[t / ux]
+        if o is not None and y.data_ptr() < o.data_ptr() + 4 * o.numel() and o.data_ptr() < y.data_ptr() + 4 * y.numel():
+            raise ValueError(f"smg_conv: y overlaps {name}")
+    if bias is not None and bias.numel() != N:
+        raise ValueError(f"smg_conv: bias must have {N} entries")
+    tp, nt = _tile_list("smg_conv", tiles, B, Tw)
+    if nt < 0:
+        return
+    L.check(L.load().a3t_smg_conv(_ptr(x), _ptr(wt), _ptr(bias), _ptr(m), _ptr(stats), _ptr(R), _ptr(y), mode, int(bool(sigmoid)),
+                                  tp, nt, B, Tw, Cin, N, wt.shape[0] // Cin, dil, up, ux, ur, _stream()), "smg_conv")
+
+
+def smg_stats(x, stats, B, Tw, tiles=None, eps=1e-5, part=None):
+    """stats [B][2][64] = mean | 1 / sqrt(biased variance + eps) per (row, channel) of x fp32 [B*Tw][64] over each row's own
+    length (a3t_smg_stats; torch.nn.InstanceNorm1d).  Deterministic, and a row's result depends on nothing but the row.
+    part: scratch of 128 floats per tile (allocated here when None).  tiles: as hfg_conv."""
+    _ragged_f32("smg_stats", x, stats, part)
+    if x.shape[-1] != 64 or x.numel() != B * Tw * 64 or stats.numel() != B * 128:
+        raise ValueError(f"smg_stats: x must be [{B * Tw}][64] and stats [{B}][2][64]")
+    tp, nt = _tile_list("smg_stats", tiles, B, Tw)
+    if nt < 0:
+        return
+    need = 128 * (nt if tiles is not None else B * ((Tw + 255) // 256))
+    if part is None:
+        part = torch.empty(need, dtype=torch.float32, device=x.device)
+    elif part.numel() < need:
+        raise ValueError(f"smg_stats: part must hold {need} floats")
+    L.check(L.load().a3t_smg_stats(_ptr(x), _ptr(part), _ptr(stats), eps, tp, nt, B, Tw, 64, _stream()), "smg_stats")
+
+
 def reflect_pad_rows(x, y, pad, lens=None, mul=1):
     """x [T][C] or [B][T][C] (contiguous fp32) -> y [.., T + 2 pad, C], reflected like torch.nn.ReflectionPad1d (a3t_reflect_pad_rows).
     lens (device int32 [B]): row b is reflected at its own ends, its length being lens[b] * mul."""

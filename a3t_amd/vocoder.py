@@ -9,7 +9,8 @@ Conv1d (dilated k=3, 1x1) is the shared implicit-im2col MFMA GEMM; the gated act
 skip update and nearest-neighbour upsampling+smoothing are element-wise HIP kernels.
 
 HiFiGANGeneratorHIP and MelGANGeneratorHIP (below) are the second and third generator family of the same model zoo, with the
-same inference interface; generator_from_config picks the class from a checkpoint's config.
+same inference interface; generator_from_config picks the class from a checkpoint's config.  StyleMelGANGeneratorHIP is the
+fourth (built through its own from_config; generator_from_config does not dispatch to it yet).
 """
 import math
 import os
@@ -909,6 +910,223 @@ class MelGANGeneratorHIP(_WaveGeneratorHIP):
     __call__ = inference
 
 
+# ------------------------------------------------------------------------------------------------ StyleMelGAN generator
+class StyleMelGANGeneratorHIP(_WaveGeneratorHIP):
+    """StyleMelGAN generator inference (espnet2/gan_tts/style_melgan/style_melgan.py:28-232, tade_res_block.py:15-185; state-dict
+    compatible with the parallel_wavegan zoo's StyleMelGANGenerator, weight norm folded at load), channels-last fp32 [B*T][C] on
+    the device.  The defaults are the zoo's 24 kHz plan (hop 300).
+
+    The noise z has ceil(T / F) steps of in_channels (F = noise_upsample_factor), which the transposed convolutions
+    (pack_hifigan_upsample on the exact-fp32 GEMM, a3t_leaky_relu) bring to n_eff = ceil(T / F) * F frames of `channels`; c is
+    padded to n_eff frames with its last frame, the network runs over n_eff * hop samples and the output is cut to T * hop
+    (style_melgan.py:208-230).  A TADEResBlock is six a3t_smg_conv launches (nearest-neighbour upsampling is an index map inside
+    them) and two a3t_smg_stats; the output convolution is a3t_hfg_out with slope 1.
+
+    InstanceNorm1d takes its statistics over the whole time axis, so every sample depends on the whole utterance:
+    margin_frames is None (there is no finite margin, SpeechEditor vocodes whole utterances) and min_frames is 1."""
+
+    min_frames = 1
+    margin_frames = None
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", in_channels=128, aux_channels=80, channels=64,
+                 out_channels=1, kernel_size=9, dilation=2, bias=True, noise_upsample_scales: Sequence[int] = (10, 2, 2, 2),
+                 noise_upsample_negative_slope=0.2, upsample_scales: Sequence[int] = (5, 1, 5, 1, 3, 1, 2, 2, 1),
+                 gated_function="softmax", stats: Optional[Dict[str, np.ndarray]] = None):
+        if int(channels) != 64:
+            raise NotImplementedError(f"channels {channels}: a3t_smg_conv is built for 64 channels")
+        if int(out_channels) != 1:
+            raise NotImplementedError(f"out_channels {out_channels}: only 1 is built here")
+        if gated_function not in ("softmax", "sigmoid"):
+            raise NotImplementedError(f"gated_function {gated_function!r}: softmax and sigmoid are built into a3t_smg_conv")
+        if int(kernel_size) % 2 == 0 or int(kernel_size) > 9 or int(kernel_size) < 1:
+            raise NotImplementedError(f"kernel_size {kernel_size}: a3t_smg_conv takes an odd kernel size up to 9")
+        if int(in_channels) % 16 or int(in_channels) < 16:
+            raise NotImplementedError(f"in_channels {in_channels} must be a multiple of 16")
+        if int(aux_channels) % 16 or int(aux_channels) < 16:
+            raise NotImplementedError(f"aux_channels {aux_channels} must be a multiple of 16")
+        self.noise_scales = tuple(int(s) for s in noise_upsample_scales)
+        self.scales = tuple(int(s) for s in upsample_scales)
+        if any(s == 1 for s in self.noise_scales):      # (output_padding = s % 2 must be smaller than the stride)
+            raise NotImplementedError(f"noise_upsample_scales {list(self.noise_scales)}: a scale of 1 is a transposed convolution "
+                                      "the reference cannot run either")
+        if any(s < 1 for s in self.noise_scales + self.scales) or int(dilation) < 1:
+            raise ValueError("scales and dilation must be positive")
+        self._setup(device, aux_channels, stats)
+        self.Z, self.C, self.K, self.dil = int(in_channels), 64, int(kernel_size), int(dilation)
+        self.noise_slope, self.sigmoid = float(noise_upsample_negative_slope), gated_function == "sigmoid"
+        self.noise_upsample_factor = int(np.prod(self.noise_scales))
+        self.hop = self.upsample_factor = int(np.prod(self.scales))
+
+        def w(p):
+            return fold_weight_norm(state_dict, p)
+
+        def b(p, n, rep=1):
+            if not bias and p + ".bias" not in state_dict:
+                return None
+            v = torch.as_tensor(np.asarray(state_dict[p + ".bias"]), dtype=torch.float32)
+            if v.numel() != n:
+                raise ValueError(f"{p}.bias has {v.numel()} entries, expected {n}")
+            return v.repeat(rep).contiguous().to(self.dev)
+
+        def conv(p, cout, cin):      # Conv1d [cout][cin][K] -> the k-major operand [K*cin][cout]
+            t = w(p)
+            if tuple(t.shape) != (cout, cin, self.K):
+                raise ValueError(f"{p}.weight {tuple(t.shape)} is not ({cout}, {cin}, {self.K})")
+            return pack_hifigan_conv(t).to(self.dev), b(p, cout)
+
+        self.noise = []
+        for i, s in enumerate(self.noise_scales):
+            p, cin = f"noise_upsample.{2 * i}", self.Z if i == 0 else self.C
+            t = w(p)
+            if tuple(t.shape) != (cin, self.C, 2 * s):
+                raise ValueError(f"{p}.weight {tuple(t.shape)} is not ({cin}, {self.C}, {2 * s})")
+            self.noise.append(dict(s=s, w=pack_hifigan_upsample(t, s).to(self.dev), b=b(p, self.C, s)))
+        self.blocks = []
+        for k, u in enumerate(self.scales):
+            p, aux = f"blocks.{k}.", self.A if k == 0 else self.C
+            self.blocks.append(dict(u=u, aux1=conv(p + "tade1.aux_conv.0", 64, aux), tade1=conv(p + "tade1.gated_conv.0", 128, 64),
+                                    gate1=conv(p + "gated_conv1", 128, 64), aux2=conv(p + "tade2.aux_conv.0", 64, 64),
+                                    tade2=conv(p + "tade2.gated_conv.0", 128, 64), gate2=conv(p + "gated_conv2", 128, 64)))
+        w_out = w("output_conv.0")
+        if tuple(w_out.shape) != (1, self.C, self.K):
+            raise ValueError(f"output_conv.0.weight {tuple(w_out.shape)} is not (1, {self.C}, {self.K})")
+        self.w_out = w_out[0].t().contiguous().to(self.dev)      # [K][C]
+        self.b_out = b("output_conv.0", 1)
+
+    @classmethod
+    def from_config(cls, state_dict, generator_params: Dict, generator_type: str = "StyleMelGANGenerator", **kw):
+        """From the `generator_params` (and `generator_type`) of a parallel_wavegan config.yml and the checkpoint's
+        model["generator"] state dict.  kw: device, stats."""
+        if generator_type != "StyleMelGANGenerator":
+            raise NotImplementedError(f"generator_type {generator_type!r}: StyleMelGANGeneratorHIP builds StyleMelGANGenerator only")
+        p = dict(generator_params)
+        mode = p.pop("upsample_mode", "nearest")
+        if mode != "nearest":
+            raise NotImplementedError(f"upsample_mode {mode!r}: only nearest is built into a3t_smg_conv")
+        act = p.pop("noise_upsample_activation", "LeakyReLU")
+        if act != "LeakyReLU":
+            raise NotImplementedError(f"noise_upsample_activation {act!r}: only LeakyReLU is built here")
+        ap = p.pop("noise_upsample_activation_params", None)
+        ap = {"negative_slope": 0.2} if ap is None else dict(ap)      # (given but empty: torch's own default, 0.01)
+        p.pop("use_weight_norm", None)      # the state dict says which form it holds
+        known = ("in_channels", "aux_channels", "channels", "out_channels", "kernel_size", "dilation", "bias", "noise_upsample_scales",
+                 "upsample_scales", "gated_function")
+        unknown = sorted(set(p) - set(known))
+        if unknown:
+            raise NotImplementedError(f"generator_params {unknown} are not understood")
+        p.setdefault("noise_upsample_scales", [11, 2, 2, 2])      # (the reference constructor's defaults, where they differ)
+        p.setdefault("upsample_scales", [2, 2, 2, 2, 2, 2, 2, 2, 1])
+        return cls(state_dict, noise_upsample_negative_slope=float(ap.get("negative_slope", 0.01)), **p, **kw)
+
+    def noise_shape(self, frames: int):
+        """The shape of the noise z that `frames` frames take: (ceil(frames / F), in_channels)."""
+        return (-(-int(frames) // self.noise_upsample_factor), self.Z)
+
+    @torch.no_grad()
+    def inference(self, c: torch.Tensor, z: Optional[torch.Tensor] = None, normalize_before: bool = False,
+                  lengths: Optional[Sequence[int]] = None):
+        """c (T_feats, aux) [or (B, T_feats, aux)], z (m, in_channels) [or (B, m, in_channels)] with m = ceil(T_feats / F), or
+        None for torch.randn on the device -> (T_wav, 1) [or (B, T_wav, 1)].
+
+        lengths (host integers, one per row of a (B, Tmax, aux) batch): row b is computed exactly as if c[b, :L_b] and
+        z[b, :ceil(L_b / F)] had been passed alone: its network length is n_eff_b = ceil(L_b / F) * F frames, its c is padded to
+        that with its own last frame, every convolution reads zeros outside [0, n_eff_b * rate), every InstanceNorm statistic runs
+        over the row's own n_eff_b * rate samples, and the result (B, Tmax * hop, 1) is zero behind L_b * hop.  What the padding of
+        c and z holds reaches no valid sample."""
+        F, hop, dev = self.noise_upsample_factor, self.hop, self.dev
+        single = c.dim() == 2
+        c = c.to(dev, torch.float32)
+        if single:
+            if lengths is not None:
+                raise ValueError("lengths= goes with a (B, Tmax, aux) batch")
+            c = c[None]
+        B, Tf, A = c.shape
+        if A != self.A:
+            raise ValueError(f"c has {A} channels, the generator {self.A}")
+        if Tf < 1:
+            raise ValueError("StyleMelGANGeneratorHIP.inference: c has no frames")
+        if normalize_before and self.stats is not None:
+            c = (c - self.stats[0]) / self.stats[1]
+        rows = [Tf] * B if lengths is None else [int(n) for n in lengths]
+        if len(rows) != B or any(n < 0 or n > Tf for n in rows):
+            raise ValueError(f"lengths {rows} do not fit a batch of {B} rows of {Tf} frames")
+        msteps = [-(-n // F) for n in rows]
+        M = -(-Tf // F)
+        Te = M * F
+        want = (M, self.Z) if single else (B, M, self.Z)
+        if z is None:
+            z = torch.randn(B, M, self.Z, device=dev)
+        elif tuple(z.shape) != want:
+            raise ValueError(f"z has shape {tuple(z.shape)}, expected {want}: ceil({Tf} / {F}) steps of {self.Z} channels")
+        x = z.to(dev, torch.float32).reshape(B * M, self.Z).contiguous()
+        rates = sorted(set(np.cumprod((1,) + self.scales).tolist()))
+        lens = mlen = None
+        tiles = {}
+        if lengths is not None:      # one H2D copy: lengths | noise steps | one tile list of the n_eff per rate
+            lists = [pwg_tile_list([m * F for m in msteps], r) for r in rates]
+            Bp = (B + 3) // 4 * 4
+            offs = np.cumsum([2 * Bp] + [tl.size for tl in lists]).tolist()
+            host = np.zeros(offs[-1], dtype=np.int32)
+            host[:B], host[Bp:Bp + B] = rows, msteps
+            for o, tl in zip(offs, lists):
+                host[o:o + tl.size] = tl.reshape(-1)
+            meta = torch.from_numpy(host).to(dev)
+            lens, mlen = meta[:B], meta[Bp:Bp + B]
+            tiles = {r: meta[o:o + tl.size].view(len(tl), 4) for r, o, tl in zip(rates, offs, lists)}
+            x = x.clone()
+            ops.zero_tail(x, mlen, 1, B, M)
+        # ---- c padded to n_eff frames with each row's own last frame (a gather of frame indices)
+        last = torch.as_tensor([max(n - 1, 0) for n in rows], device=dev)
+        idx = torch.minimum(torch.arange(Te, device=dev)[None], last[:, None])
+        cc = c.gather(1, idx[:, :, None].expand(B, Te, A)).contiguous().view(B * Te, A)
+        # ---- noise path: transposed convolutions as 3-tap convolutions, LeakyReLU behind each
+        T = M
+        for st in self.noise:
+            up = torch.empty(B * T, st["s"] * self.C, device=dev)
+            ops.conv_fwd(x, st["w"], up, T, 1, bias=st["b"], compute=F32)
+            T *= st["s"]
+            x = up.view(B * T, self.C)
+            ops.leaky_relu(x, x, self.noise_slope)
+            if lens is not None:
+                ops.zero_tail(x, mlen, T // M, B, T)
+        # ---- TADEResBlocks
+        rate = 1
+        for blk in self.blocks:
+            x, cc, rate = self._block(blk, x, cc, B, Te, rate, tiles)
+        Tw = Te * hop
+        wav = (torch.zeros if lens is not None else torch.empty)(B * Tw, 1, device=dev)
+        ops.hfg_out(x, self.w_out, self.b_out, wav, B, Tw, 1.0, tiles.get(hop))      # slope 1: no activation in front
+        if lens is not None:
+            ops.zero_tail(wav, lens, hop, B, Tw)
+        wav = wav.view(B, Tw, 1)[:, :Tf * hop]
+        return wav[0] if single else wav.contiguous()
+
+    def _block(self, blk, x, c, B, Te, rate, tiles):
+        """One TADEResBlock: x, c [B * Te * rate][.] -> (x, c) [B * Te * rate * u][64], the new rate."""
+        dev, u, sg = self.dev, blk["u"], self.sigmoid
+        T1, T2 = Te * rate, Te * rate * u
+        t1, t2 = tiles.get(rate), tiles.get(rate * u)
+
+        def e(T):
+            return torch.empty(B * T, 64, device=dev)
+
+        st = torch.empty(2, B, 2, 64, device=dev)
+        part = torch.empty(128 * B * ((T1 + 255) // 256), device=dev)
+        ops.smg_stats(x, st[0], B, T1, t1, part=part)
+        c1, y1, g1 = e(T1), e(T1), e(T1)
+        ops.smg_conv(c, *blk["aux1"], c1, B, T1, tiles=t1)
+        ops.smg_conv(c1, *blk["tade1"], y1, B, T1, mode=ops.SMG_TADE, m=x, stats=st[0], tiles=t1)
+        ops.smg_conv(y1, *blk["gate1"], g1, B, T1, mode=ops.SMG_GATE, sigmoid=sg, tiles=t1)
+        ops.smg_stats(g1, st[1], B, T1, t1, part=part)
+        c2, y2, out = e(T2), e(T2), e(T2)
+        ops.smg_conv(c1, *blk["aux2"], c2, B, T2, up=u, tiles=t2)
+        ops.smg_conv(c2, *blk["tade2"], y2, B, T2, mode=ops.SMG_TADE, m=g1, stats=st[1], ux=u, tiles=t2)
+        ops.smg_conv(y2, *blk["gate2"], out, B, T2, dil=self.dil, mode=ops.SMG_GATE, R=x, ur=u, sigmoid=sg, tiles=t2)
+        return out, c2, rate * u
+
+    __call__ = inference
+
+
 # ------------------------------------------------------------------------------------------ a generator from a config
 _PWG_KNOWN = ("layers", "stacks", "residual_channels", "gate_channels", "skip_channels", "aux_channels", "aux_context_window",
               "upsample_params")
@@ -928,7 +1146,8 @@ def generator_from_config(state_dict, config: Dict, **kw):
     if gtype == "HiFiGANGenerator":
         return HiFiGANGeneratorHIP.from_config(state_dict, params, gtype, **kw)
     if gtype != "ParallelWaveGANGenerator":
-        raise NotImplementedError(f"generator_type {gtype!r}: ParallelWaveGANGenerator, HiFiGANGenerator and MelGANGenerator are built here")
+        raise NotImplementedError(f"generator_type {gtype!r}: ParallelWaveGANGenerator, HiFiGANGenerator and MelGANGenerator are built here"
+                                  + (" (a StyleMelGANGenerator: StyleMelGANGeneratorHIP.from_config)" if gtype == "StyleMelGANGenerator" else ""))
     params.pop("use_weight_norm", None)
     for k, v in _PWG_FIXED.items():
         if k in params and params.pop(k) != v:

@@ -459,7 +459,7 @@ int a3t_dropout_bwd_cast(const float* g, void* gm, int gm_dtype, float* colsum, 
  * b0 [128] permuted the same way.  wt1 [64][128] = conv1x1_out.weight^T (columns 0..63 residual, 64..127 skip), b1 [128]. */
 int a3t_pwg_block(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1,
                   float* g, float* skips, int B, int Tw, int dil, void* stream);
-/* The tile contract of the waveform kernels (a3t_pwg_block_ragged, a3t_pwg_block_f16, a3t_hfg_conv, a3t_hfg_conv_f16, a3t_hfg_out, a3t_mgan_*, a3t_pqmf_synthesis;
+/* The tile contract of the waveform kernels (a3t_pwg_block_ragged, a3t_pwg_block_f16, a3t_hfg_conv, a3t_hfg_conv_f16, a3t_hfg_out, a3t_mgan_*, a3t_pqmf_synthesis, a3t_smg_*;
  * csrc/wave_tiles.h).  tiles == NULL (and ntiles == 0): every row is Tw samples long.  Else rows of different length: tiles
  * [ntiles][4] int32 on the device (16-byte aligned) = {row b, first sample t0 (multiple of 256), valid samples W_b <= Tw of row
  * b, 0}, one entry per 256-sample tile with t0 < W_b (the kernels trust the entries).  Row b is computed as if it were alone:
@@ -538,6 +538,26 @@ int a3t_pqmf_synthesis(const float* x, const float* h, float* y, const int32_t* 
 int a3t_reflect_pad_rows(const float* x, float* y, int64_t B, int64_t T, int C, int pad, void* stream);
 int a3t_reflect_pad_rows_ragged(const float* x, float* y, const int32_t* lens, int mul, int64_t B, int64_t T, int C, int pad,
                                 void* stream);
+
+/* StyleMelGAN generator kernels (espnet2/gan_tts/style_melgan/style_melgan.py:28-232, tade_res_block.py:15-185;
+ * csrc/stylemelgan.hip), fp32 channels-last on the tile contract above (a tap beyond a row's end is zero).
+ * a3t_smg_conv: v[t] = bias + sum_{tap,c} wt[tap*Cin + c][:] * x[(t + (tap - (taps-1)/2) * dil) / up][c] for t in [0, W_b), on the
+ *   fp32 MFMA.  Nearest-neighbour upsampling is the index map: x holds ceil(Tw / up) rows per batch row (m and R likewise with
+ *   ux and ur).  mode 0 PLAIN (Cout = 64): y = v.  mode 1 TADE (Cout = 128): y[t][c] = v[t][c] * ((m[t / ux][c] - mean[b][c]) *
+ *   rstd[b][c]) + v[t][64 + c], stats [B][2][64] = mean | rstd from a3t_smg_stats.  mode 2 GATE (Cout = 128): y[t][c] =
+ *   g(v[t][:64])[c] * tanh(v[t][64 + c]) (+ R[t / ur][c], R may be NULL), g = softmax over the 64 channels with the maximum
+ *   subtracted, or (sigmoid != 0) the logistic function.  y [B*Tw][64]; Cin a multiple of 16, taps odd <= 9, dil, up, ux, ur >= 1;
+ *   x and wt 16-byte aligned; y must be neither x nor m.  bias [Cout] may be NULL.
+ * a3t_smg_stats: stats [B][2][64] = per (row, channel) the mean and 1 / sqrt(biased variance + eps) of x [B*Tw][64] over the row's
+ *   own W_b samples (torch.nn.InstanceNorm1d), from per-tile (mean, M2) merged in an order fixed by the row's number of tiles:
+ *   no atomics, and a row's result does not depend on the other rows or on its place in the batch.  part: scratch of
+ *   128 floats per tile (ntiles, or B * ceil(Tw / 256) for the dense form).  A row without a tile gets mean 0, rstd 0.
+ * Rows behind W_b are neither read nor written.  A3T_EINVAL for anything outside these contracts. */
+int a3t_smg_conv(const float* x, const float* wt, const float* bias, const float* m, const float* stats, const float* R, float* y,
+                 int mode, int sigmoid, const int32_t* tiles, int ntiles, int B, int Tw, int Cin, int Cout, int taps, int dil,
+                 int up, int ux, int ur, void* stream);
+int a3t_smg_stats(const float* x, float* part, float* stats, float eps, const int32_t* tiles, int ntiles, int B, int Tw, int C,
+                  void* stream);
 
 /* On-device half of MLMCollateFn (espnet2/train/collate_fn.py:330-385): masked_position, speech / text segment ids and the
  * two padding masks painted from integer span lists.  fs / fe [B][P] int32: frame span of phone j (floor(fs * t / hop) taken
