@@ -126,6 +126,11 @@ _SIGS = {
     "a3t_gst_conv_bn_relu": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "a3t_gst_gru_stl": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "a3t_gst_add_style": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
+    "a3t_fs2_variance_embed": [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
+    "a3t_length_offsets": [_P, _P, c_float, _P, _P, _P, c_int, c_int, _P],
+    "a3t_length_expand": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P],
+    "a3t_fs2_finish": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P],
+    "a3t_fs2_mvn": [_P, _P, _P, _P, c_int64, c_int, _P],
     "a3t_dropout": [_P, c_int, _P, c_int, c_int64, c_float, ctypes.c_uint32, c_float, _P],
     "a3t_collate_paint": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "a3t_segment_colsum": [_P, _P, c_int, c_int, c_int, _P],

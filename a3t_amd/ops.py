@@ -942,6 +942,75 @@ def gst_add_style(hs, style, B, T, rows=None):
                                        style.shape[0], _stream()), "gst_add_style")
 
 
+def _lens_ptr(lens, B, what):
+    if lens is None:
+        return None
+    if _i32(lens, "lens").numel() != B:
+        raise ValueError(f"{what}: {lens.numel()} lengths for {B} rows")
+    return _ptr(lens)
+
+
+def fs2_variance_embed(hs, pitch, energy, wp, bp, we, be, lens, B, T):
+    """hs [B*T][d] (or [B][T][d]) += pitch and energy embeddings of pitch / energy [B*T]: Conv1d(1 -> d) with weights wp
+    [kp][d], we [ke][d] and biases bp, be [d]; lens (device int32 [B] or None): rows t >= lens[b] are left alone and the
+    convolutions read zeros there."""
+    _ragged_f32("fs2_variance_embed", hs, pitch, energy, wp, bp, we, be)
+    d = hs.shape[-1]
+    if hs.numel() != B * T * d or pitch.numel() != B * T or energy.numel() != B * T or wp.dim() != 2 or we.dim() != 2 or \
+            wp.shape[1] != d or we.shape[1] != d or bp.numel() != d or be.numel() != d:
+        raise ValueError("fs2_variance_embed: shapes do not fit")
+    L.check(L.load().a3t_fs2_variance_embed(_ptr(hs), _ptr(pitch), _ptr(energy), _ptr(wp), _ptr(bp), _ptr(we), _ptr(be),
+                                            _lens_ptr(lens, B, "fs2_variance_embed"), B, T, d, wp.shape[0], we.shape[0],
+                                            _stream()), "fs2_variance_embed")
+
+
+def length_offsets(frames, lens, alpha, offsets, frame_lens, scaled=None):
+    """frames int64 [B][T] -> offsets int32 [B][T + 1] (exclusive prefix sums of the durations, scaled by alpha and rounded
+    half to even when alpha != 1; entries behind lens[b] count as 0), frame_lens int32 [B], scaled int64 [B][T] (or None)."""
+    B, T = frames.shape
+    if frames.dtype != torch.int64 or not frames.is_contiguous() or tuple(_i32(offsets, "offsets").shape) != (B, T + 1) or \
+            _i32(frame_lens, "frame_lens").numel() != B or \
+            (scaled is not None and (scaled.dtype != torch.int64 or not scaled.is_contiguous() or scaled.numel() != B * T)):
+        raise ValueError("length_offsets: shapes do not fit")
+    L.check(L.load().a3t_length_offsets(_ptr(frames), _lens_ptr(lens, B, "length_offsets"), float(alpha), _ptr(offsets),
+                                        _ptr(frame_lens), _ptr(scaled), B, T, _stream()), "length_offsets")
+
+
+def length_expand(hs, offsets, lens, frame_lens, out, scale_=1.0):
+    """The length regulator: hs [B][T][d], offsets / frame_lens of length_offsets -> out [B][Fp][d], row b holding scale_ *
+    hs[b][token of frame f] for f < frame_lens[b] and 0 behind."""
+    _ragged_f32("length_expand", hs, out)
+    B, T, d = hs.shape
+    if out.dim() != 3 or out.shape[0] != B or out.shape[2] != d or tuple(_i32(offsets, "offsets").shape) != (B, T + 1) or \
+            _i32(frame_lens, "frame_lens").numel() != B:
+        raise ValueError("length_expand: shapes do not fit")
+    L.check(L.load().a3t_length_expand(_ptr(hs), _ptr(offsets), _lens_ptr(lens, B, "length_expand"), _ptr(frame_lens),
+                                       _ptr(out), B, T, out.shape[1], d, scale_, _stream()), "length_expand")
+
+
+def fs2_finish(before, post, after, lens=None, mean=None, std=None, denorm=None):
+    """[B][F][C]: after = before + post (post None: before); denorm (or None) = after * std + mean; rows f >= lens[b]: 0."""
+    _ragged_f32("fs2_finish", before, post, after, mean, std, denorm)
+    B, F, C = before.shape
+    for t in (post, after, denorm):
+        if t is not None and t.shape != before.shape:
+            raise ValueError("fs2_finish: shapes do not fit")
+    for t in (mean, std):
+        if t is not None and t.numel() != C:
+            raise ValueError("fs2_finish: statistics do not fit")
+    L.check(L.load().a3t_fs2_finish(_ptr(before), _ptr(post), _ptr(mean), _ptr(std), _ptr(after), _ptr(denorm),
+                                    _lens_ptr(lens, B, "fs2_finish"), B, F, C, _stream()), "fs2_finish")
+
+
+def fs2_mvn(x, mean, std, y):
+    """y [M][C] = (x - mean) / std (GlobalMVN; mean / std [C] or None)."""
+    _ragged_f32("fs2_mvn", x, mean, std, y)
+    C = x.shape[-1]
+    if y.shape != x.shape or any(t is not None and t.numel() != C for t in (mean, std)):
+        raise ValueError("fs2_mvn: shapes do not fit")
+    L.check(L.load().a3t_fs2_mvn(_ptr(x), _ptr(mean), _ptr(std), _ptr(y), x.numel() // C, C, _stream()), "fs2_mvn")
+
+
 def dropout(x, y, p, key, scale=1.0):
     L.check(L.load().a3t_dropout(_ptr(x), _dt(x), _ptr(y), _dt(y), x.numel(), p, key, scale, _stream()), "dropout")
 

@@ -442,6 +442,33 @@ int a3t_gst_gru_stl(const float* gi, const float* w_hh, const float* b_hh, const
                     float* ref_embs, float* style, int B, int T, int H, int d, int heads, int tokens, void* stream);
 int a3t_gst_add_style(float* hs, const float* style, const int32_t* rows, int B, int T, int d, int S, void* stream);
 
+/* FastSpeech2 text-to-mel inference behind the duration predictor (csrc/fs2_tts.hip; fastspeech2.py:662-699,
+ * fastspeech/length_regulator.py, espnet2/layers/global_mvn.py).  fp32, padded [B][T] rows; lens: int32 [B] on the device
+ * (clamped to 0..T) or NULL for full rows; row b is computed as if alone and nothing behind its length is read.
+ * a3t_fs2_variance_embed: hs [B][T][d], t < n_b: hs[b][t] += Conv1d(1 -> d, kp)(pitch[b])[t] + Conv1d(1 -> d, ke)(energy[b])[t]
+ *   with both biases; wp [kp][d], we [ke][d] (taps outermost), padding (k - 1) / 2, pitch / energy [B][T] read as 0 outside
+ *   [0, n_b).  Rows t >= n_b stay as they are.  d % 4 == 0, kp and ke odd, 1..9; A3T_EINVAL otherwise.
+ * a3t_length_offsets: one wave per row.  d'[t] = frames[b][t] for t < n_b (0 behind), with alpha != 1
+ *   (int) rintf((float) d * alpha) (torch.round(ds.float() * alpha): half to even); offsets [B][T + 1] int32 = exclusive
+ *   prefix sums of d' (offsets[b][T] = the row's frame count, also frame_lens[b]); scaled [B][T] int64 = d' (may be NULL).
+ *   Deterministic, no atomics.  A d' above 2^18 is saturated there.  alpha > 0.
+ * a3t_length_expand: out [B][Fp][d]: out[b][f] = scale * hs[b][tok(f)] for f < min(frame_lens[b], Fp), tok(f) the token with
+ *   offsets[b][tok] <= f < offsets[b][tok + 1] (tokens of duration 0 are never taken), 0 for the frames behind.  offsets and
+ *   frame_lens as a3t_length_offsets wrote them with the same lens.  d % 4 == 0, T <= 12000.
+ * a3t_fs2_finish: [B][F][C]: after = before + post (post NULL: before), denorm = after * std + mean (std, mean [C], each may be
+ *   NULL; denorm NULL: not written); rows f >= lens[b] are written as 0.
+ * a3t_fs2_mvn: y [M][C] = (x - mean) / std (mean, std [C], each may be NULL): GlobalMVN on a prompt's log-mel. */
+int a3t_fs2_variance_embed(float* hs, const float* pitch, const float* energy, const float* wp, const float* bp,
+                           const float* we, const float* be, const int32_t* lens, int B, int T, int d, int kp, int ke,
+                           void* stream);
+int a3t_length_offsets(const int64_t* frames, const int32_t* lens, float alpha, int32_t* offsets, int32_t* frame_lens,
+                       int64_t* scaled, int B, int T, void* stream);
+int a3t_length_expand(const float* hs, const int32_t* offsets, const int32_t* lens, const int32_t* frame_lens, float* out,
+                      int B, int T, int Fp, int d, float scale, void* stream);
+int a3t_fs2_finish(const float* before, const float* post, const float* mean, const float* std_, float* after, float* denorm,
+                   const int32_t* lens, int B, int F, int C, void* stream);
+int a3t_fs2_mvn(const float* x, const float* mean, const float* std_, float* y, int64_t M, int C, void* stream);
+
 /* Dropout (torch.nn.Dropout sites of the path).  Counter-based: keep = f(key, element index), so the
  * same key reproduces the mask in the backward pass and inside GEMM epilogues; no mask tensors.
  * y = scale * x * keep/(1-p); in place allowed; x / y may be fp32 or bf16. */
