@@ -79,6 +79,8 @@ _SIGS = {
     "a3t_attn_bias_fold": [_P, c_int32, c_int32, _P, _P, _P, _P],
     "a3t_scale_dev": [_P, _P, c_int64, _P, _P],
     "a3t_slice_rows": [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
+    "a3t_concat_rows": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
+    "a3t_split_rows": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_cast_bf16": [_P, _P, c_int64, _P],
     "a3t_cast_bf16_conv_t": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_split_bf16": [_P, _P, _P, c_int64, _P],

@@ -32,6 +32,10 @@ class A3TConfig:
     # after the embedding prologue.  The reference accepts `spembs` and ignores it (sedit_model.py:246): this is an
     # extension with no reference behaviour (parity unpinned); 0 = off, the reference's behaviour.
     spk_embed_dim: int = 0
+    # model variants the reference's MLMTask builds besides the recipe's (conformer/encoder.py:386-398, :502-516; tasks/mlm.py:405-413)
+    segment_emb: bool = True     # input_layer 'sega_mlm'; False = 'mlm': no segment table, segment ids are not read
+    pre_blocks: int = 0          # pre_speech_layer: conformer blocks over the speech tokens alone, before the text joins
+    has_decoder: bool = True     # False = decoder 'no_decoder': the head reads encoder.after_norm (no sqrt(d) scale, no decoder.after_norm)
     # feature extraction
     fs: int = 24000
     n_fft: int = 2048
@@ -50,19 +54,32 @@ class A3TConfig:
 
     @staticmethod
     def from_espnet(encoder_conf: Dict[str, Any], decoder_conf: Dict[str, Any], model_conf: Dict[str, Any],
-                    input_size: int, odim: int, vocab: int, feats_conf: Dict[str, Any] = None) -> "A3TConfig":
-        """Translate the recipe's encoder_conf/decoder_conf/model_conf dictionaries."""
-        e, d, m = encoder_conf, decoder_conf, model_conf
-        if e.get("input_layer", "sega_mlm") != "sega_mlm":
-            raise NotImplementedError("only input_layer='sega_mlm' (the A3T recipe) is implemented")
-        if e.get("positionwise_layer_type", "conv1d") != "conv1d" or not e.get("macaron_style", True) \
-                or not e.get("use_cnn_module", True):
-            raise NotImplementedError("only the recipe's conformer layout (conv1d FFN, macaron, cnn module)")
+                    input_size: int, odim: int, vocab: int, feats_conf: Dict[str, Any] = None,
+                    has_decoder: bool = True) -> "A3TConfig":
+        """Translate the recipe's encoder_conf/decoder_conf/model_conf dictionaries.  has_decoder=False (decoder: no_decoder):
+        decoder_conf is not read."""
+        e, m = encoder_conf, model_conf
+        d = decoder_conf if has_decoder else {}          # (left alone without a decoder, tasks/mlm.py:393-395)
+        input_layer = e.get("input_layer", "sega_mlm")
+        if input_layer not in ("sega_mlm", "mlm"):
+            raise NotImplementedError(f"input_layer={input_layer!r}: only 'sega_mlm' (the A3T recipe) and 'mlm' are implemented")
+        pre_blocks = int(e.get("pre_speech_layer", 0) or 0)
+        if pre_blocks < 0:
+            raise ValueError(f"pre_speech_layer={pre_blocks}: expected 0 or more")
+        for conf, who in ((e, "encoder_conf"), (d, "decoder_conf")):
+            if conf.get("positionwise_layer_type", "conv1d") != "conv1d":
+                raise NotImplementedError(f"{who}.positionwise_layer_type={conf['positionwise_layer_type']!r}: only 'conv1d' "
+                                          "(the recipe's MultiLayeredConv1d) is implemented")
+            for k in ("macaron_style", "use_cnn_module"):
+                if not conf.get(k, True):
+                    raise NotImplementedError(f"{who}.{k}=False: only the recipe's conformer block (macaron FFN pair, "
+                                              "convolution module) is implemented")
         c = A3TConfig(
             idim=input_size, odim=odim, vocab=vocab, adim=e["attention_dim"], heads=e["attention_heads"],
             ff=e["linear_units"], ff_kernel=e.get("positionwise_conv_kernel_size", 3), enc_blocks=e["num_blocks"],
-            dec_blocks=d["num_blocks"], enc_kernel=e.get("cnn_module_kernel", 31),
-            dec_kernel=d.get("cnn_module_kernel", 31), postnet_layers=m.get("postnet_layers", 0),
+            dec_blocks=d["num_blocks"] if has_decoder else 0, enc_kernel=e.get("cnn_module_kernel", 31),
+            dec_kernel=d.get("cnn_module_kernel", 31), segment_emb=(input_layer == "sega_mlm"), pre_blocks=pre_blocks,
+            has_decoder=bool(has_decoder), postnet_layers=m.get("postnet_layers", 0),
             postnet_chans=m.get("postnet_chans", 0), postnet_filts=m.get("postnet_filts", 0),
             lsm_weight=m.get("lsm_weight", 0.0), dropout_rate=e.get("dropout_rate", 0.1),
             positional_dropout_rate=e.get("positional_dropout_rate", 0.1),

@@ -45,11 +45,11 @@ __global__ void embed_finish_fwd_kernel(const float* __restrict__ e, const float
         if (t < Tm) {
             int64_t r = (int64_t)b * Tm + t;
             v = fmaxf(e[r * D + c], 0.f) * xscale;
-            sg = seg[spos[r] * D + c];
+            sg = seg ? seg[spos[r] * D + c] : 0.f;      // (no segment table, input_layer 'mlm': the ids are not read)
         } else {
             int64_t r = (int64_t)b * Tp + (t - Tm);
             v = emb[text[r] * D + c] * xscale;
-            sg = seg[tpos[r] * D + c];
+            sg = seg ? seg[tpos[r] * D + c] : 0.f;
         }
         if (inv > 0.f) v = rng_keep(key, (unsigned int)i, thr) ? v * inv : 0.f;   // positional dropout, before + seg
         if (spk) sg += spk[(int64_t)b * D + c];     // projected speaker embedding, the same vector for every token of b
@@ -83,14 +83,18 @@ __global__ void embed_finish_bwd_kernel(const float* __restrict__ dxs, const flo
         if (t < Tm) {
             int64_t r = (int64_t)b * Tm + t;
             de[r * D + c] = (e[r * D + c] > 0.f) ? gd * xscale : 0.f;
-            int64_t s = spos[r];
-            if (s != nseg - 1) atomicAdd(&dseg[s * D + c], g);  // padding_idx=-1 -> last row gets no grad
+            if (dseg) {
+                int64_t s = spos[r];
+                if (s != nseg - 1) atomicAdd(&dseg[s * D + c], g);  // padding_idx=-1 -> last row gets no grad
+            }
         } else {
             int64_t r = (int64_t)b * Tp + (t - Tm);
             int64_t tok = text[r];
             if (tok != V - 1) atomicAdd(&demb[tok * D + c], gd * xscale);
-            int64_t s = tpos[r];
-            if (s != nseg - 1) atomicAdd(&dseg[s * D + c], g);
+            if (dseg) {
+                int64_t s = tpos[r];
+                if (s != nseg - 1) atomicAdd(&dseg[s * D + c], g);
+            }
         }
     }
 }
@@ -235,6 +239,51 @@ extern "C" int a3t_slice_rows(const float* x, void* y, int y_dtype, int B, int T
     int64_t n = (int64_t)B * Tm * D;
     hipLaunchKernelGGL(slice_rows_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, x, y, y_dtype, B, T, Tm,
                        D, reverse_add);
+    return (int)hipGetLastError();
+}
+// Time concatenation of the speech tokens (after the pre-speech blocks) and the text tokens, conformer/encoder.py:550-551:
+// xs[b][t] = t < Tm ? speech[b][t] : text[b][t - Tm], in 16-byte granules (D % 4 == 0)
+__global__ void concat_rows_kernel(const float4* __restrict__ speech, const float4* __restrict__ text, float4* __restrict__ xs,
+                                   int B, int Tm, int Tp, int D4) {
+    const int T = Tm + Tp;
+    const int64_t n = (int64_t)B * T * D4;
+    GRID_STRIDE(i, n) {
+        const int64_t row = i / D4;
+        const int c = (int)(i - row * D4);
+        const int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
+        xs[i] = t < Tm ? speech[((int64_t)b * Tm + t) * D4 + c] : text[((int64_t)b * Tp + (t - Tm)) * D4 + c];
+    }
+}
+extern "C" int a3t_concat_rows(const float* speech, const float* text, float* xs, int B, int Tm, int Tp, int D, void* stream) {
+    if (B <= 0 || Tm < 0 || Tp < 0 || Tm + Tp <= 0 || D <= 0 || D % 4) return A3T_EINVAL;
+    if (((uintptr_t)xs & 15) || (Tm > 0 && ((uintptr_t)speech & 15)) || (Tp > 0 && ((uintptr_t)text & 15))) return A3T_EINVAL;
+    const int64_t n = (int64_t)B * (Tm + Tp) * (D / 4);
+    hipLaunchKernelGGL(concat_rows_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, (const float4*)speech,
+                       (const float4*)text, (float4*)xs, B, Tm, Tp, D / 4);
+    return (int)hipGetLastError();
+}
+// ... and its backward: the gradient of xs split into the two parts (plain stores, every element of both outputs is written)
+__global__ void split_rows_kernel(const float4* __restrict__ dxs, float4* __restrict__ dspeech, float4* __restrict__ dtext,
+                                  int B, int Tm, int Tp, int D4) {
+    const int T = Tm + Tp;
+    const int64_t n = (int64_t)B * T * D4;
+    GRID_STRIDE(i, n) {
+        const int64_t row = i / D4;
+        const int c = (int)(i - row * D4);
+        const int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
+        const float4 g = dxs[i];
+        if (t < Tm)
+            dspeech[((int64_t)b * Tm + t) * D4 + c] = g;
+        else
+            dtext[((int64_t)b * Tp + (t - Tm)) * D4 + c] = g;
+    }
+}
+extern "C" int a3t_split_rows(const float* dxs, float* dspeech, float* dtext, int B, int Tm, int Tp, int D, void* stream) {
+    if (B <= 0 || Tm < 0 || Tp < 0 || Tm + Tp <= 0 || D <= 0 || D % 4) return A3T_EINVAL;
+    if (((uintptr_t)dxs & 15) || (Tm > 0 && ((uintptr_t)dspeech & 15)) || (Tp > 0 && ((uintptr_t)dtext & 15))) return A3T_EINVAL;
+    const int64_t n = (int64_t)B * (Tm + Tp) * (D / 4);
+    hipLaunchKernelGGL(split_rows_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, (const float4*)dxs,
+                       (float4*)dspeech, (float4*)dtext, B, Tm, Tp, D / 4);
     return (int)hipGetLastError();
 }
 

@@ -231,6 +231,10 @@ class MLMEngine:
         self.fused_attn_train_min = 1 if os.environ.get("A3T_FUSED_ATTN_TRAIN", "1") == "2" else 64
         self._fused_now = False
         self._fused_train_now = False
+        # which attention forward each block of the last forward() took ("fwd" = a3t_attn_fwd, "train" = a3t_attn_fwd_train,
+        # "mat" = the materialised one), and the (B, T) it ran at: the pre-speech blocks run at T_mel, the others at T_mel + T_phn
+        self.attn_path = {}
+        self.block_dims = {}
         self._need_grad = training
         self._mode_tag = None
         if self.bf16:
@@ -649,6 +653,8 @@ class MLMEngine:
         else:
             P = self._act(tag + ".P", (T, d))
             ops.linear_fwd(pos, self.W(pre + ".wpos"), P, compute=cmp)
+        self.attn_path[tag[:-4]] = "fwd" if (self._fused_now and fused) else "train" if (self._fused_train_now and fused) else "mat"
+        self.block_dims[tag[:-4]] = (B, T)
         if self._fused_now and fused:
             adr = self._drop(c.attention_dropout_rate, tag + ".att")
             ctx = self._act(tag + ".ctx", (M, d))
@@ -970,6 +976,16 @@ class MLMEngine:
         return g
 
     # ------------------------------------------------------------------ whole model
+    def _attn_choice(self, B, T, need_grad):
+        """(forward-only fused, fused training forward) for the blocks that run at T tokens per utterance: decided once per
+        forward() and block shape.  The backward follows what the forward saved under the block's tag."""
+        nblk = B * self.c.heads * ((T + 127) // 128)
+        fused_now = (self.fused_attn_fwd_only and not need_grad) or \
+            (self.fused_attn_auto and not need_grad and nblk >= 64)
+        fused_train_now = self.fused_attn_train and need_grad and not fused_now and \
+            self.fused_attn_train_min <= nblk <= 65536 and T <= 2048
+        return fused_now, fused_train_now
+
     def forward(self, batch: Dict[str, torch.Tensor], need_grad: bool = True, gscale: float = 1.0):
         c, p, ws = self.c, self.store.p, self.ws
         speech = batch["speech"].contiguous()
@@ -981,11 +997,8 @@ class MLMEngine:
         if self.bf16 and (T % 8 or Tm % 8):
             raise ValueError(f"compute='bf16' needs T_mel and T_mel+T_phn to be multiples of 8, got {Tm}, {T}")
         self.dims = (B, Tm, Tp, T)
-        self._fused_now = (self.fused_attn_fwd_only and not need_grad) or \
-            (self.fused_attn_auto and not need_grad and B * c.heads * ((T + 127) // 128) >= 64)
-        nblk = B * c.heads * ((T + 127) // 128)
-        self._fused_train_now = self.fused_attn_train and need_grad and not self._fused_now and \
-            self.fused_attn_train_min <= nblk <= 65536 and T <= 2048
+        self._fused_now, self._fused_train_now = main_path = self._attn_choice(B, T, need_grad)
+        self.attn_path, self.block_dims = {}, {}
         self._need_grad = bool(need_grad)
         self._mode_tag = ops.gemm_mode_tag()
         self.step_seed += 1
@@ -1007,6 +1020,7 @@ class MLMEngine:
         e = self._ln_fwd("emb.ln", e0, "emb.ln", eps=1e-5, out_dtype=torch.float32)
         xs = ws.get("emb.xs", (B * T, d))
         xscale = math.sqrt(d)
+        seg = p["seg"] if c.segment_emb else None      # (None: the kernels read no segment ids)
         spk = None
         if c.spk_embed_dim > 0 and batch.get("spembs") is not None:
             # x-vector conditioning (configs[3]): Linear(spembs) added to every token of the utterance, fused into the
@@ -1017,8 +1031,18 @@ class MLMEngine:
             self.sv["spk"] = se
         else:
             self.sv.pop("spk", None)
-        ops.embed_finish_fwd(e, p["temb"], p["seg"], text, spos, tpos, xs, B, Tm, Tp, d, xscale,
-                             drop=self._drop(pp, "emb.x") or (0.0, 0), spk=spk)
+        xsp = xst = None
+        if c.pre_blocks > 0:
+            # pre-speech blocks (conformer/encoder.py:547-551): speech and text tokens are finished into buffers of their own, the
+            # speech side goes through the pre.{i} blocks at T = T_mel, then the two are joined along time
+            xsp, xst = ws.get("emb.xsp", (B * Tm, d)), ws.get("emb.xst", (B * Tp, d))
+            ops.embed_finish_fwd(e, p["temb"], seg, text, spos, tpos, xsp, B, Tm, 0, d, xscale,
+                                 drop=self._drop(pp, "emb.x") or (0.0, 0), spk=spk)
+            ops.embed_finish_fwd(e, p["temb"], seg, text, spos, tpos, xst, B, 0, Tp, d, xscale,
+                                 drop=self._drop(pp, "emb.xt") or (0.0, 0), spk=spk)
+        else:
+            ops.embed_finish_fwd(e, p["temb"], seg, text, spos, tpos, xs, B, Tm, Tp, d, xscale,
+                                 drop=self._drop(pp, "emb.x") or (0.0, 0), spk=spk)
         pos_e = self._act("pos.enc", (T, d))
         pos_d = self._act("pos.dec", (T, d))
         pos_on_side = None
@@ -1046,35 +1070,51 @@ class MLMEngine:
         # them are projected up front on the side stream, which is idle in the forward (A3T_POS_AHEAD=0: inside each block)
         self._P_ahead, self._pos_ev = {}, None
         if self.side is not None and self._pos_ahead:
+            first = "pre" if c.pre_blocks > 0 else "enc"      # (the dropped tables are made in front of their first reader)
+
             def project(kind, posx, n):
                 def run():
-                    if kind == "enc" and pos_on_side is not None:
+                    if kind == first and pos_on_side is not None:
                         pos_on_side()
                     for i in range(n):
                         tag = f"{kind}.{i}.mha"
-                        P = self._act(tag + ".P", (T, d))
+                        P = self._act(tag + ".P", (posx.shape[0], d))
                         ops.linear_fwd(posx, self.W(tag + ".wpos"), P, compute=self.cmp)
                         self._P_ahead[tag] = P
                 return run
-            ev_e = self._side(project("enc", pos_e, c.enc_blocks), want_event="pos.enc")
-            ev_d = self._side(project("dec", pos_d, c.dec_blocks), want_event="pos.dec")     # (behind the decoder-side weight cast)
-            self._pos_ev = {"enc": ev_e, "dec": ev_d}
+            self._pos_ev = {}
+            if c.pre_blocks > 0:       # the speech tokens' own table: the first T_mel rows of the encoder's
+                self._pos_ev["pre"] = self._side(project("pre", pos_e[:Tm], c.pre_blocks), want_event="pos.pre")
+            self._pos_ev["enc"] = self._side(project("enc", pos_e, c.enc_blocks), want_event="pos.enc")
+            if c.has_decoder:
+                self._pos_ev["dec"] = self._side(project("dec", pos_d, c.dec_blocks), want_event="pos.dec")     # (behind the decoder-side weight cast)
+        if c.pre_blocks > 0:
+            kms = ws.get("keymask.pre", (B, Tm), torch.uint8)
+            kms.copy_(batch["speech_mask"].reshape(B, Tm).view(torch.uint8))
+            self._fused_now, self._fused_train_now = self._attn_choice(B, Tm, need_grad)
+            x = xsp
+            for i in range(c.pre_blocks):
+                x = self.block_fwd(f"pre.{i}", x, pos_e[:Tm], kms, B, Tm)
+            self._fused_now, self._fused_train_now = main_path
+            ops.concat_rows(x, xst, xs, B, Tm, Tp, d)
         x = xs
         for i in range(c.enc_blocks):
             x = self.block_fwd(f"enc.{i}", x, pos_e, keymask, B, T)
         x = self._ln_fwd("enc.after", x, "enc.after", out_dtype=torch.float32)
-        # --- decoder (conformer/encoder.py:568-614): x*sqrt(d), contiguous rel-pos table
-        xd = ws.get("dec.in", (B * T, d))
-        dd = self._drop(pp, "dec.x")
-        if dd:
-            ops.dropout(x, xd, dd[0], dd[1], scale=xscale)
-        else:
-            ops.scale(x, xd, xscale)
-        x = xd
-        self._wait_cast("_cast_ev")       # decoder / head shadows cast on the side stream (refresh_weights)
-        for i in range(c.dec_blocks):
-            x = self.block_fwd(f"dec.{i}", x, pos_d, keymask, B, T)
-        x = self._ln_fwd("dec.after", x, "dec.after", out_dtype=torch.float32)
+        if c.has_decoder:
+            # --- decoder (conformer/encoder.py:568-614): x*sqrt(d), contiguous rel-pos table
+            xd = ws.get("dec.in", (B * T, d))
+            dd = self._drop(pp, "dec.x")
+            if dd:
+                ops.dropout(x, xd, dd[0], dd[1], scale=xscale)
+            else:
+                ops.scale(x, xd, xscale)
+            x = xd
+            self._wait_cast("_cast_ev")       # decoder / head shadows cast on the side stream (refresh_weights)
+            for i in range(c.dec_blocks):
+                x = self.block_fwd(f"dec.{i}", x, pos_d, keymask, B, T)
+            x = self._ln_fwd("dec.after", x, "dec.after", out_dtype=torch.float32)
+        # (no_decoder, sedit_model.py:356-362: the head reads encoder.after_norm's output as it is)
         # --- head: slice speech frames, sfc, postnet, loss (sedit_model.py:363-372,320-340)
         hs = self._act("head.hs", (B * Tm, d))
         ops.slice_rows(x, hs, B, T, Tm, d)
@@ -1185,30 +1225,51 @@ class MLMEngine:
         g = ws.get("grad.x", (B * T, d), zero=True)
         g16 = self._g16(g)
         ops.slice_rows(g, dhs, B, T, Tm, d, reverse_add=True)
-        self._ln_bwd("dec.after", g, "dec.after", None, g, g16)
-        for i in reversed(range(c.dec_blocks)):
-            self.block_bwd(f"dec.{i}", g, B, T)
-            done(f"dec.{i}.ffm.ln.g")
-        dd = self._drop(c.positional_dropout_rate, "dec.x")
-        if dd:
-            ops.dropout(g, g, dd[0], dd[1], scale=math.sqrt(d))
-        else:
-            ops.scale(g, g, math.sqrt(d))
+        if c.has_decoder:
+            self._ln_bwd("dec.after", g, "dec.after", None, g, g16)
+            for i in reversed(range(c.dec_blocks)):
+                self.block_bwd(f"dec.{i}", g, B, T)
+                done(f"dec.{i}.ffm.ln.g")
+            dd = self._drop(c.positional_dropout_rate, "dec.x")
+            if dd:
+                ops.dropout(g, g, dd[0], dd[1], scale=math.sqrt(d))
+            else:
+                ops.scale(g, g, math.sqrt(d))
         self._ln_bwd("enc.after", g, "enc.after", None, g, g16)
         for i in reversed(range(c.enc_blocks)):
             self.block_bwd(f"enc.{i}", g, B, T)
             done(f"enc.{i}.ffm.ln.g")
+        gs = gt = None
+        if c.pre_blocks > 0:     # the gradient of the concatenation: the speech part goes back through the pre-speech blocks
+            gs, gt = ws.get("grad.xsp", (B * Tm, d)), ws.get("grad.xst", (B * Tp, d))
+            ops.split_rows(g, gs, gt, B, Tm, Tp, d)
+            for i in reversed(range(c.pre_blocks)):
+                self.block_bwd(f"pre.{i}", gs, B, Tm)
+                done(f"pre.{i}.ffm.ln.g")
         # --- prologue backward
         if "spk" in self.sv:     # d Linear(spembs): per-utterance column sums of the gradient of the token stream
             se = self.sv["spk"]
             dspk = ws.get("tmp.dspk", (B, d), zero=True)
-            ops.segment_colsum(g, dspk, B, T)
+            if gs is None:
+                ops.segment_colsum(g, dspk, B, T)
+            else:                # (added to both parts at the prologue: speech-side + text-side sums)
+                ops.segment_colsum(gs, dspk, B, Tm)
+                if Tp > 0:
+                    ops.segment_colsum(gt, dspk, B, Tp)
             ops.linear_bwd_weight(dspk, se, gr["spk.w"], compute=F32)
             self._bias_grad(dspk, gr["spk.b"])
         xm, e, text, spos, tpos, masked, speech2 = self.sv["embed"]
         de = ws.get("tmp.de", (B * Tm, d))
-        ops.embed_finish_bwd(g, e, text, spos, tpos, de, gr["temb"], gr["seg"], B, Tm, Tp, d, c.vocab, c.seg_table,
-                             math.sqrt(d), drop=self._drop(c.positional_dropout_rate, "emb.x") or (0.0, 0))
+        dseg = gr["seg"] if c.segment_emb else None
+        pdrop = c.positional_dropout_rate
+        if gs is None:
+            ops.embed_finish_bwd(g, e, text, spos, tpos, de, gr["temb"], dseg, B, Tm, Tp, d, c.vocab, c.seg_table,
+                                 math.sqrt(d), drop=self._drop(pdrop, "emb.x") or (0.0, 0))
+        else:
+            ops.embed_finish_bwd(gs, e, text, spos, tpos, de, gr["temb"], dseg, B, Tm, 0, d, c.vocab, c.seg_table,
+                                 math.sqrt(d), drop=self._drop(pdrop, "emb.x") or (0.0, 0))
+            ops.embed_finish_bwd(gt, e, text, spos, tpos, de, gr["temb"], dseg, B, 0, Tp, d, c.vocab, c.seg_table,
+                                 math.sqrt(d), drop=self._drop(pdrop, "emb.xt") or (0.0, 0))
         de0 = ws.get("tmp.de0", (B * Tm, d))
         de16 = ws.get("tmp.de016", (B * Tm, d), torch.bfloat16) if self.bf16 else None
         self._ln_bwd("emb.ln", de, "emb.ln", None, de0, de16, (gr["emb.b"], 1.0))
@@ -1220,5 +1281,5 @@ class MLMEngine:
         s64.zero_()
         ops.col_reduce(dxm, s64, rowmask=masked.view(-1), mode=0)
         ops.f64_to_f32_add(s64, gr["mask_feature"], 1.0)
-        done("seg")
+        done(next(iter(self.store.offsets)))      # (the first entry of the layout: "seg", or "mask_feature" without a segment table)
         self._side_join()        # every gradient is final on the caller's stream when backward returns

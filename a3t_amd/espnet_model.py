@@ -65,9 +65,9 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
         self.ignore_id = -1
         self.encoder = _Namespace()           # attributes read by callers
         self.encoder._output_size = config.adim
-        self.encoder.segment_emb = True
-        self.encoder.pre_speech_layer = 0
-        self.decoder = _Namespace()
+        self.encoder.segment_emb = True if config.segment_emb else None      # (input_layer 'mlm': conformer/encoder.py:387)
+        self.encoder.pre_speech_layer = config.pre_blocks
+        self.decoder = _Namespace() if config.has_decoder else None           # (no_decoder: tasks/mlm.py:412-413)
         self._eng = {}
         self._last = None
         self._build_store(device)

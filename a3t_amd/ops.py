@@ -475,6 +475,16 @@ def slice_rows(x, y, B, T, Tm, D, reverse_add=False):
     L.check(L.load().a3t_slice_rows(_ptr(x), _ptr(y), _dt(y), B, T, Tm, D, int(reverse_add), _stream()), "slice_rows")
 
 
+def concat_rows(speech, text, xs, B, Tm, Tp, D):
+    """xs[B][Tm+Tp][D] = speech[B][Tm][D] | text[B][Tp][D] along time (fp32)."""
+    L.check(L.load().a3t_concat_rows(_ptr(speech), _ptr(text), _ptr(xs), B, Tm, Tp, D, _stream()), "concat_rows")
+
+
+def split_rows(dxs, dspeech, dtext, B, Tm, Tp, D):
+    """The backward of concat_rows: dspeech / dtext = the two parts of dxs (stored)."""
+    L.check(L.load().a3t_split_rows(_ptr(dxs), _ptr(dspeech), _ptr(dtext), B, Tm, Tp, D, _stream()), "split_rows")
+
+
 def reflect_pad(x, out, pad):
     B, N = x.shape
     L.check(L.load().a3t_reflect_pad(_ptr(x), _ptr(out), B, N, pad, out.shape[1], _stream()), "reflect_pad")

@@ -36,7 +36,8 @@ def _block_layout(c: A3TConfig, K: int) -> List[Tuple[str, tuple]]:
 def param_layout(c: A3TConfig) -> "OrderedDict[str, tuple]":
     d = c.adim
     lay = OrderedDict()
-    lay["seg"] = (c.seg_table, d)
+    if c.segment_emb:
+        lay["seg"] = (c.seg_table, d)
     lay["mask_feature"] = (c.idim,)
     lay["emb.w"] = (d, c.idim)
     lay["emb.b"] = (d,)
@@ -46,16 +47,20 @@ def param_layout(c: A3TConfig) -> "OrderedDict[str, tuple]":
     if c.spk_embed_dim > 0:
         lay["spk.w"] = (d, c.spk_embed_dim)
         lay["spk.b"] = (d,)
+    for i in range(c.pre_blocks):       # pre_speech_encoders: the encoder's block, over the speech tokens only
+        for n, s in _block_layout(c, c.enc_kernel):
+            lay[f"pre.{i}.{n}"] = s
     for i in range(c.enc_blocks):
         for n, s in _block_layout(c, c.enc_kernel):
             lay[f"enc.{i}.{n}"] = s
     lay["enc.after.g"] = (d,)
     lay["enc.after.b"] = (d,)
-    for i in range(c.dec_blocks):
-        for n, s in _block_layout(c, c.dec_kernel):
-            lay[f"dec.{i}.{n}"] = s
-    lay["dec.after.g"] = (d,)
-    lay["dec.after.b"] = (d,)
+    if c.has_decoder:
+        for i in range(c.dec_blocks):
+            for n, s in _block_layout(c, c.dec_kernel):
+                lay[f"dec.{i}.{n}"] = s
+        lay["dec.after.g"] = (d,)
+        lay["dec.after.b"] = (d,)
     lay["sfc.w"] = (c.odim, d)
     lay["sfc.b"] = (c.odim,)
     for l in range(c.postnet_layers):
@@ -70,7 +75,7 @@ def param_layout(c: A3TConfig) -> "OrderedDict[str, tuple]":
 def buffer_layout(c: A3TConfig) -> "OrderedDict[str, tuple]":
     """BatchNorm running statistics (not trained, part of the checkpoint)."""
     lay = OrderedDict()
-    for st, n in (("enc", c.enc_blocks), ("dec", c.dec_blocks)):
+    for st, n in (("pre", c.pre_blocks), ("enc", c.enc_blocks), ("dec", c.dec_blocks if c.has_decoder else 0)):
         for i in range(n):
             lay[f"{st}.{i}.cnv.bn.rm"] = (c.adim,)
             lay[f"{st}.{i}.cnv.bn.rv"] = (c.adim,)
@@ -118,8 +123,8 @@ def _ref_block_map(ref: str, mine: str, c: A3TConfig):
 
 
 def reference_key_map(c: A3TConfig):
-    m = [("encoder.segment_emb.weight", "seg", None, "reshape"),
-         ("encoder.speech_embed.0.mask_feature", "mask_feature", None, "reshape"),
+    m = [("encoder.segment_emb.weight", "seg", None, "reshape")] if c.segment_emb else []
+    m += [("encoder.speech_embed.0.mask_feature", "mask_feature", None, "reshape"),
          ("encoder.speech_embed.1.weight", "emb.w", None, "reshape"),
          ("encoder.speech_embed.1.bias", "emb.b", None, "reshape"),
          ("encoder.speech_embed.2.weight", "emb.ln.g", None, "reshape"),
@@ -127,15 +132,18 @@ def reference_key_map(c: A3TConfig):
          ("encoder.text_embed.0.weight", "temb", None, "reshape")]
     if c.spk_embed_dim > 0:    # extension keys (no reference counterpart): optional when loading a reference checkpoint
         m += [("spk_proj.weight", "spk.w", None, "optional"), ("spk_proj.bias", "spk.b", None, "optional")]
+    for i in range(c.pre_blocks):
+        m += _ref_block_map(f"encoder.pre_speech_encoders.{i}.", f"pre.{i}.", c)
     for i in range(c.enc_blocks):
         m += _ref_block_map(f"encoder.encoders.{i}.", f"enc.{i}.", c)
     m += [("encoder.after_norm.weight", "enc.after.g", None, "reshape"),
           ("encoder.after_norm.bias", "enc.after.b", None, "reshape")]
-    for i in range(c.dec_blocks):
-        m += _ref_block_map(f"decoder.encoders.{i}.", f"dec.{i}.", c)
-    m += [("decoder.after_norm.weight", "dec.after.g", None, "reshape"),
-          ("decoder.after_norm.bias", "dec.after.b", None, "reshape"),
-          ("sfc.weight", "sfc.w", None, "reshape"), ("sfc.bias", "sfc.b", None, "reshape")]
+    if c.has_decoder:
+        for i in range(c.dec_blocks):
+            m += _ref_block_map(f"decoder.encoders.{i}.", f"dec.{i}.", c)
+        m += [("decoder.after_norm.weight", "dec.after.g", None, "reshape"),
+              ("decoder.after_norm.bias", "dec.after.b", None, "reshape")]
+    m += [("sfc.weight", "sfc.w", None, "reshape"), ("sfc.bias", "sfc.b", None, "reshape")]
     for l in range(c.postnet_layers):
         p = f"postnet.postnet.{l}."
         m += [(p + "0.weight", f"post.{l}.w", None, "conv"), (p + "1.weight", f"post.{l}.bn.g", None, "reshape"),

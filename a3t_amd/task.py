@@ -104,10 +104,14 @@ class MLMTask:
             args.feats_extract = args.feats_extract_conf = None
         if getattr(args, "normalize", None) is not None:
             logging.warning("normalize is built but never applied by the reference model (SURVEY §0); ignored")
-        if args.encoder != "conformer" or args.decoder not in ("conformer",):
-            raise NotImplementedError("only encoder=conformer + decoder=conformer (the A3T recipe) is implemented")
-        # the reference force-selects the legacy rel-pos implementation and writes it back into args
-        for conf in (args.encoder_conf, args.decoder_conf):
+        if args.encoder != "conformer":
+            raise NotImplementedError(f"encoder={args.encoder!r}: only encoder=conformer is implemented")
+        if args.decoder not in ("conformer", "no_decoder"):
+            raise NotImplementedError(f"decoder={args.decoder!r}: only decoder=conformer and decoder=no_decoder are implemented")
+        has_decoder = args.decoder != "no_decoder"
+        # the reference force-selects the legacy rel-pos implementation and writes it back into args (decoder_conf only when
+        # there is a conformer decoder, tasks/mlm.py:393-395)
+        for conf in (args.encoder_conf, args.decoder_conf) if has_decoder else (args.encoder_conf,):
             if conf.get("pos_enc_layer_type", "rel_pos") == "rel_pos":
                 conf["pos_enc_layer_type"] = "legacy_rel_pos"
             if conf.get("selfattention_layer_type", "rel_selfattn") == "rel_selfattn":
@@ -117,7 +121,7 @@ class MLMTask:
         if args.model_conf.get("duration_predictor_layers", 0) > 0:
             raise NotImplementedError("ESPnetMLMTTSModel (duration predictor variant) is listed as 'next' (SURVEY §8f)")
         cfg = A3TConfig.from_espnet(args.encoder_conf, args.decoder_conf, args.model_conf, args.input_size, odim,
-                                    vocab_size, getattr(args, "feats_extract_conf", None))
+                                    vocab_size, getattr(args, "feats_extract_conf", None), has_decoder=has_decoder)
         model = ESPnetMLMEncAsDecoderModel(token_list=token_list, odim=odim, feats_extract=feats_extract,
                                            normalize=None, config=cfg, device=device, compute=compute,
                                            **args.model_conf)

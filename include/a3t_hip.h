@@ -297,6 +297,8 @@ int a3t_mask_fill(const float* speech, const uint8_t* masked, const float* mask_
 /* xs[b][t] (t<Tm): relu(e[b*Tm+t]) * xscale + seg[spos];  (t>=Tm): emb[text]*xscale + seg[tpos];
  * spk (optional, [B][D]): projected speaker embedding added to every token of utterance b (x-vector conditioning of
  * BASELINE configs[3]; no reference behaviour: sedit_model.py:246 ignores spembs) */
+/* seg == NULL (fwd) / dseg == NULL (bwd): a model without segment embedding (input_layer 'mlm', conformer/encoder.py:386-398):
+ * no segment term, spos / tpos are not read.  Tm == 0 or Tp == 0: one side alone (xs / dxs is [B][Tp][D] or [B][Tm][D]). */
 int a3t_embed_finish_fwd(const float* e, const float* emb, const float* seg, const int64_t* text,
                          const int64_t* spos, const int64_t* tpos, float* xs, int B, int Tm, int Tp, int D,
                          float xscale, float drop_p, uint32_t drop_key, const float* spk, void* stream);
@@ -314,6 +316,11 @@ int a3t_scale_dev(const float* x, float* y, int64_t n, const float* s, void* str
 /* copy rows [b][0:Tm] of x[B][T][D] into y[B][Tm][D] (sedit_model.py:363) and the reverse scatter-add */
 int a3t_slice_rows(const float* x, void* y, int y_dtype, int B, int T, int Tm, int D, int reverse_add,
                    void* stream);
+/* xs[B][Tm+Tp][D] = speech[B][Tm][D] and text[B][Tp][D] joined along time (conformer/encoder.py:550-551, behind the
+ * pre-speech blocks), and the backward: dxs split into dspeech / dtext (stored, not accumulated).  fp32, D % 4 == 0,
+ * 16-byte aligned pointers; Tm == 0 or Tp == 0 is allowed (that side's pointer is not touched). */
+int a3t_concat_rows(const float* speech, const float* text, float* xs, int B, int Tm, int Tp, int D, void* stream);
+int a3t_split_rows(const float* dxs, float* dspeech, float* dtext, int B, int Tm, int Tp, int D, void* stream);
 /* fp32 -> bf16 (round to nearest even); n % 4 == 0 (the flat parameter buffer once per step) */
 int a3t_cast_bf16(const float* x, void* y, int64_t n, void* stream);
 /* Transposed bf16 shadows of `count` Conv1d weights W[N][taps][C] (multi_layer_conv.py:36-50) living at element offsets
