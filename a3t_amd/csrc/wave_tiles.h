@@ -1,5 +1,5 @@
 // wave_tiles.h -- the tile contract of the waveform kernels (pwg_fused.hip, pwg_fused_f16.hip, hifigan.hip,
-// hifigan_f16.hip), device and host side.
+// hifigan_f16.hip, melgan.hip, stylemelgan.hip), device and host side.
 //
 // A [B][Tw] batch of samples is cut into tiles of 256.  Dense form (tiles == NULL): the grid is all B * ceil(Tw / 256) tiles and
 // every row is Tw samples long.  Ragged form: the grid is a host-built device list, int32 [ntiles][4] = {row b, first sample t0

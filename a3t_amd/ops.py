@@ -688,6 +688,24 @@ def leaky_relu(x, y, slope):
     L.check(L.load().a3t_leaky_relu(_ptr(x), _ptr(y), x.numel(), slope, _stream()), "leaky_relu")
 
 
+def _hfg_conv_args(what, x, bias, R, y, acc, B, Tw, tiles):
+    """What hfg_conv and hfg_conv_f16 check alike: x / R / y / acc fp32 [B*Tw][C], x overlapping neither y nor acc, y not acc, a
+    bias of C entries -> (C, tile pointer, ntiles) as _tile_list."""
+    C = x.shape[-1]
+    for name, t in (("x", x), ("R", R), ("y", y), ("acc", acc)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != C or t.numel() != B * Tw * C):
+            raise ValueError(f"{what}: {name} must be a contiguous fp32 [{B * Tw}][{C}] tensor")
+    nbytes = 4 * B * Tw * C
+    for name, t in (("y", y), ("acc", acc)):      # other tiles read x[t +- halo]: no output may overlap the input, or the other
+        for oname, o in (("x", x), ("acc", acc if name == "y" else None)):
+            if t is not None and o is not None and abs(t.data_ptr() - o.data_ptr()) < nbytes:
+                raise ValueError(f"{what}: {name} overlaps {oname}")
+    _ragged_f32(what, bias)
+    if bias is not None and bias.numel() != C:
+        raise ValueError(f"{what}: bias must have {C} entries")
+    return (C,) + _tile_list(what, tiles, B, Tw)
+
+
 def hfg_conv(x, wt, bias, y, B, Tw, dil, slope, R=None, acc=None, alpha=1.0, acc_add=False, tiles=None):
     """One HiFi-GAN residual-unit convolution (a3t_hfg_conv): v = bias + conv(leaky(x, slope)) (+ R); y = v (y may be None) and
     acc = alpha * v or, with acc_add, acc += alpha * v (acc may be None).  x / R / y / acc fp32 [B*Tw][C], C in {32, 64};
@@ -696,18 +714,8 @@ def hfg_conv(x, wt, bias, y, B, Tw, dil, slope, R=None, acc=None, alpha=1.0, acc
     C = x.shape[-1]
     if wt.dim() != 2 or wt.shape[1] != C or wt.shape[0] % C:
         raise ValueError(f"hfg_conv: wt must be [taps*{C}][{C}], got {tuple(wt.shape)}")
-    for name, t in (("x", x), ("R", R), ("y", y), ("acc", acc)):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != C or t.numel() != B * Tw * C):
-            raise ValueError(f"hfg_conv: {name} must be a contiguous fp32 [{B * Tw}][{C}] tensor")
-    nbytes = 4 * B * Tw * C
-    for name, t in (("y", y), ("acc", acc)):      # other tiles read x[t +- halo]: no output may overlap the input, or the other
-        for oname, o in (("x", x), ("acc", acc if name == "y" else None)):
-            if t is not None and o is not None and abs(t.data_ptr() - o.data_ptr()) < nbytes:
-                raise ValueError(f"hfg_conv: {name} overlaps {oname}")
-    _ragged_f32("hfg_conv", wt, bias)
-    if bias is not None and bias.numel() != C:
-        raise ValueError(f"hfg_conv: bias must have {C} entries")
-    tp, nt = _tile_list("hfg_conv", tiles, B, Tw)
+    C, tp, nt = _hfg_conv_args("hfg_conv", x, bias, R, y, acc, B, Tw, tiles)
+    _ragged_f32("hfg_conv", wt)
     if nt < 0:
         return
     L.check(L.load().a3t_hfg_conv(_ptr(x), _ptr(wt), _ptr(bias), _ptr(R), _ptr(y), _ptr(acc), alpha, int(bool(acc_add)), slope,
@@ -723,18 +731,7 @@ def hfg_conv_f16(x, wf, bias, y, B, Tw, dil, slope, R=None, acc=None, alpha=1.0,
             or wf.shape[0] % (C // 16):
         raise ValueError(f"hfg_conv_f16: wf must be a contiguous fp16 [taps*{C // 16}][{C // 32}][64][8] tensor, got "
                          f"{wf.dtype} {tuple(wf.shape)}")
-    for name, t in (("x", x), ("R", R), ("y", y), ("acc", acc)):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != C or t.numel() != B * Tw * C):
-            raise ValueError(f"hfg_conv_f16: {name} must be a contiguous fp32 [{B * Tw}][{C}] tensor")
-    nbytes = 4 * B * Tw * C
-    for name, t in (("y", y), ("acc", acc)):      # as hfg_conv: no output may overlap the input, or the other output
-        for oname, o in (("x", x), ("acc", acc if name == "y" else None)):
-            if t is not None and o is not None and abs(t.data_ptr() - o.data_ptr()) < nbytes:
-                raise ValueError(f"hfg_conv_f16: {name} overlaps {oname}")
-    _ragged_f32("hfg_conv_f16", bias)
-    if bias is not None and bias.numel() != C:
-        raise ValueError(f"hfg_conv_f16: bias must have {C} entries")
-    tp, nt = _tile_list("hfg_conv_f16", tiles, B, Tw)
+    C, tp, nt = _hfg_conv_args("hfg_conv_f16", x, bias, R, y, acc, B, Tw, tiles)
     if nt < 0:
         return
     L.check(L.load().a3t_hfg_conv_f16(_ptr(x), _ptr(wf), _ptr(bias), _ptr(R), _ptr(y), _ptr(acc), alpha, int(bool(acc_add)), slope,

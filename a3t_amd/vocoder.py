@@ -1,6 +1,6 @@
-"""ParallelWaveGAN generator inference on the GPU (mel -> waveform).
+"""Neural vocoders on the GPU (mel -> waveform): the four generator families of the parallel_wavegan model zoo.
 
-Mirror of the vocoder the reference calls in ``sedit_inference.py:77,339-348`` through
+ParallelWaveGANGeneratorHIP mirrors the vocoder the reference calls in ``sedit_inference.py:77,339-348`` through
 ``ParallelWaveGANPretrainedVocoder`` (espnet2/tts/utils/parallel_wavegan_pretrained_vocoder.py:49-63);
 the network restated is the vendored twin ``ParallelWaveGANGenerator``
 (espnet2/gan_tts/parallel_wavegan/parallel_wavegan.py:136-229, wavenet/residual_block.py:114-169,
@@ -8,9 +8,10 @@ parallel_wavegan/upsample.py:22-189), weight-norm removed.  Layout is channels-l
 Conv1d (dilated k=3, 1x1) is the shared implicit-im2col MFMA GEMM; the gated activation, residual /
 skip update and nearest-neighbour upsampling+smoothing are element-wise HIP kernels.
 
-HiFiGANGeneratorHIP and MelGANGeneratorHIP (below) are the second and third generator family of the same model zoo, with the
-same inference interface; generator_from_config picks the class from a checkpoint's config.  StyleMelGANGeneratorHIP is the
-fourth (built through its own from_config; generator_from_config does not dispatch to it yet).
+HiFiGANGeneratorHIP, MelGANGeneratorHIP (MelGAN and multi-band MelGAN) and StyleMelGANGeneratorHIP have the same inference
+interface.  _WaveGeneratorHIP holds what the four share: the weight loader, the preamble of inference and the stage helpers;
+_config_params is the one reading of a checkpoint's generator_params.  generator_from_config picks the class from a checkpoint's
+config (StyleMelGANGeneratorHIP is built through its own from_config; generator_from_config does not dispatch to it yet).
 """
 import math
 import os
@@ -91,20 +92,65 @@ def pack_pwg_block_f16(conv_w, conv_b, aux_w, out_w):
     return _pack_pwg_block(conv_w, conv_b, aux_w, out_w, lambda t: t.clamp(-F16_MAX, F16_MAX).to(torch.float16).contiguous())
 
 
-class _WaveGeneratorHIP:
-    """What the generators share: the device, the statistics of normalize_before and the preamble of inference."""
+def _check_compute(compute: str) -> str:
+    if compute not in ("f32", "f16"):
+        raise ValueError(f"compute must be 'f32' or 'f16', got {compute!r}")
+    return compute
 
-    def _setup(self, device, aux_channels, stats):
+
+def _tap_major(t: torch.Tensor, device) -> torch.Tensor:
+    """Conv1d weight (out, in, taps) -> the operand [out][tap][in] of ops.conv_fwd, on the device."""
+    return t.permute(0, 2, 1).contiguous().to(device)
+
+
+def _config_params(p: Dict, known: Sequence[str], fixed: Dict) -> Dict:
+    """What is left of p, a copy of a config's generator_params, for a constructor that takes the `known` keys.  fixed
+    {field: (the only value built here, the refusal's text)}: such a field is dropped, or refused by name
+    (NotImplementedError; {!r} in the text is the value asked for), and so is every key that is not known.  use_weight_norm is
+    dropped: the state dict says which form it holds."""
+    p.pop("use_weight_norm", None)
+    for k, (v, msg) in fixed.items():
+        if k in p and p[k] != v:
+            raise NotImplementedError(msg.format(p[k]))
+        p.pop(k, None)
+    unknown = sorted(set(p) - set(known))
+    if unknown:
+        raise NotImplementedError(f"generator_params {unknown} are not understood")
+    return p
+
+
+_LRELU_ONLY = ("LeakyReLU", "nonlinear_activation {!r}: only LeakyReLU is built into the kernels")
+_NOT_CAUSAL = (False, "use_causal_conv is not supported")
+
+
+class _WaveGeneratorHIP:
+    """What the generators share: the device, the statistics of normalize_before, the weight loader (_w, _b over the state
+    dict that _setup is given), the preamble of inference (prepare = _check_input + _pack_meta) and the stage helpers."""
+
+    def _setup(self, device, aux_channels, stats, state_dict, bias=True):
         self.dev, self.A = torch.device(device), int(aux_channels)
+        self._sd, self._bias = state_dict, bool(bias)      # (for _w / _b; __init__ drops the state dict when it has loaded)
         self.stats = None
         if stats is not None:     # normalize_before of the pretrained wrapper (c - mean) / scale
             self.stats = (torch.as_tensor(stats["mean"], dtype=torch.float32, device=self.dev),
                           torch.as_tensor(stats["scale"], dtype=torch.float32, device=self.dev))
 
-    def prepare(self, c, normalize_before, lengths, rates):
-        """c (T_feats, aux) or (B, T_feats, aux) -> (c [B][Tf][A] fp32 on the device, single, lens, tiles).  lengths (host
-        integers, one per row): lens = the device int32 [B] of them and tiles = {rate: pwg_tile_list(lengths, rate) on the device}
-        for the samples-per-frame rates that fused kernels run at, else None and {}."""
+    def _w(self, p):
+        """`p`.weight as fp32 on the host, weight norm folded."""
+        return fold_weight_norm(self._sd, p)
+
+    def _b(self, p, n, rep=1):
+        """`p`.bias (n entries, checked) repeated rep times, on the device; None where a bias=False plan has none."""
+        if not self._bias and p + ".bias" not in self._sd:
+            return None
+        v = torch.as_tensor(np.asarray(self._sd[p + ".bias"]), dtype=torch.float32)
+        if v.numel() != n:
+            raise ValueError(f"{p}.bias has {v.numel()} entries, expected {n}")
+        return v.repeat(rep).contiguous().to(self.dev)
+
+    def _check_input(self, c, normalize_before, lengths):
+        """c (T_feats, aux) or (B, T_feats, aux) -> (c [B][Tf][A] fp32 on the device, normalised; single; lengths as a list of
+        B integers in [0, Tf], or None)."""
         single = (c.dim() == 2)
         c = c.to(self.dev, torch.float32)
         if single:
@@ -115,21 +161,85 @@ class _WaveGeneratorHIP:
         if normalize_before and self.stats is not None:
             c = (c - self.stats[0]) / self.stats[1]
         if lengths is None:
-            return c, single, None, {}
+            return c, single, None
         if single:
             raise ValueError("lengths= goes with a (B, Tmax, aux) batch")
         lengths = [int(x) for x in lengths]
         if len(lengths) != B or any(n < 0 or n > Tf for n in lengths):
             raise ValueError(f"lengths {lengths} do not fit a batch of {B} rows of {Tf} frames")
-        # one H2D copy: lens [B] | one tile list [ntiles][4] = {b, t0, W_b, 0} per rate (offsets kept 16-byte aligned)
-        lists = [pwg_tile_list(lengths, r) for r in rates]
-        offs = np.cumsum([(B + 3) // 4 * 4] + [tl.size for tl in lists]).tolist()
+        return c, single, lengths
+
+    def _pack_meta(self, vectors, tile_lengths, rates):
+        """One H2D copy: the per-row int32 vectors [B] | one tile list [ntiles][4] = {b, t0, W_b, 0} per rate, pwg_tile_list(
+        tile_lengths, rate) (offsets kept 16-byte aligned) -> (the vectors on the device, {rate: its tile list on the device})."""
+        B = len(tile_lengths)
+        Bp = (B + 3) // 4 * 4
+        lists = [pwg_tile_list(tile_lengths, r) for r in rates]
+        offs = np.cumsum([len(vectors) * Bp] + [tl.size for tl in lists]).tolist()
         host = np.zeros(offs[-1], dtype=np.int32)
-        host[:B] = lengths
+        for i, v in enumerate(vectors):
+            host[i * Bp:i * Bp + B] = v
         for o, tl in zip(offs, lists):
             host[o:o + tl.size] = tl.reshape(-1)
         meta = torch.from_numpy(host).to(self.dev)
-        return c, single, meta[:B], {r: meta[o:o + tl.size].view(len(tl), 4) for r, o, tl in zip(rates, offs, lists)}
+        return ([meta[i * Bp:i * Bp + B] for i in range(len(vectors))],
+                {r: meta[o:o + tl.size].view(len(tl), 4) for r, o, tl in zip(rates, offs, lists)})
+
+    def prepare(self, c, normalize_before, lengths, rates):
+        """c (T_feats, aux) or (B, T_feats, aux) -> (c [B][Tf][A] fp32 on the device, single, lens, tiles).  lengths (host
+        integers, one per row): lens = the device int32 [B] of them and tiles = {rate: pwg_tile_list(lengths, rate) on the device}
+        for the samples-per-frame rates that fused kernels run at, else None and {}."""
+        c, single, lengths = self._check_input(c, normalize_before, lengths)
+        if lengths is None:
+            return c, single, None, {}
+        (lens,), tiles = self._pack_meta([lengths], lengths, rates)
+        return c, single, lens, tiles
+
+    # ---- stage helpers: lens None = all rows full length, and nothing is zeroed
+    def _lrelu(self, x, slope=None):
+        y = torch.empty_like(x)
+        ops.leaky_relu(x, y, self.slope if slope is None else slope)
+        return y
+
+    @staticmethod
+    def _zero_tail(x, lens, rate, B, T):
+        if lens is not None:
+            ops.zero_tail(x, lens, rate, B, T)
+
+    def _ragged_copy(self, c, lens):
+        """c [B][Tf][A] contiguous; of a ragged batch a copy (c may be the caller's tensor) that is zero behind each row's end."""
+        c = c.contiguous()
+        if lens is not None:
+            c = c.clone()
+            ops.zero_tail(c, lens, 1, c.shape[0], c.shape[1])
+        return c
+
+    def _tiled_rates(self, out=()):
+        """The samples-per-frame rates of the tiled kernels: those of the fused stages, then the last stage's times each of `out`."""
+        rates, r = [], 1
+        for st in self.stages:
+            r *= st["s"]
+            if st["fused"]:
+                rates.append(r)
+        return rates + [r * m for m in out if r * m not in rates]
+
+    def _upsample(self, x, w, b, B, T, s, C, lens, rate, slope, after=False):
+        """One transposed convolution of scale s as a 3-tap convolution (w, b: pack_hifigan_upsample and the bias repeated s times):
+        x [B*T][Cin] at `rate` -> [B*T*s][C], zero behind lens * rate * s.  The LeakyReLU runs in front of it, or with `after`
+        behind it, in place."""
+        up = torch.empty(B * T, s * C, device=self.dev)
+        ops.conv_fwd(x if after else self._lrelu(x, slope), w, up, T, 1, bias=b, compute=F32)
+        up = up.view(B * T * s, C)
+        if after:
+            ops.leaky_relu(up, up, slope)
+        self._zero_tail(up, lens, rate * s, B, T * s)
+        return up
+
+
+_PWG_KNOWN = ("layers", "stacks", "residual_channels", "gate_channels", "skip_channels", "aux_channels", "aux_context_window",
+              "upsample_params")
+_PWG_FIXED = dict(in_channels=1, out_channels=1, kernel_size=3, dropout=0.0, dropout_rate=0.0, bias=True,
+                  use_causal_conv=False, upsample_conditional_features=True, upsample_net="ConvInUpsampleNetwork")
 
 
 class ParallelWaveGANGeneratorHIP(_WaveGeneratorHIP):
@@ -141,33 +251,27 @@ class ParallelWaveGANGeneratorHIP(_WaveGeneratorHIP):
                  gate_channels=128, skip_channels=64, aux_channels=80, aux_context_window=2,
                  upsample_scales: Sequence[int] = (4, 5, 3, 5), stats: Optional[Dict[str, np.ndarray]] = None,
                  fused: Optional[bool] = None, compute: str = "f32"):
-        if compute not in ("f32", "f16"):
-            raise ValueError(f"compute must be 'f32' or 'f16', got {compute!r}")
+        self.compute = _check_compute(compute)
         if compute == "f16":
             if (residual_channels, gate_channels, skip_channels, aux_channels) != (64, 128, 64, 80):
                 raise ValueError("compute='f16' needs the v1 channel plan: 64 residual / 128 gate / 64 skip / 80 aux channels")
             if fused is not None and not fused:
                 raise ValueError("compute='f16' is a mode of the fused residual blocks: fused=False cannot be combined with it")
             fused = True
-        self.compute = compute
-        self._setup(device, aux_channels, stats)
+        self._setup(device, aux_channels, stats, state_dict)
         self.layers, self.stacks = layers, stacks
         self.R, self.G, self.S = residual_channels, gate_channels, skip_channels
         self.ctx = aux_context_window
         self.scales = tuple(upsample_scales)
         self.upsample_factor = int(np.prod(self.scales))
 
-        def t(k):
-            return torch.as_tensor(np.asarray(state_dict[k]), dtype=torch.float32).to(self.dev)
+        def w(p):
+            return self._w(p).to(self.dev)
 
-        def conv(k):              # (out, in, taps) -> [out][tap][in]
-            return t(k).permute(0, 2, 1).contiguous()
-
-        self.w_first = t("first_conv.weight").reshape(self.R, 1).contiguous()
-        self.b_first = t("first_conv.bias")
-        self.w_in = conv("upsample_net.conv_in.weight")
-        self.w_up = [t(f"upsample_net.upsample.up_layers.{2 * i + 1}.weight").reshape(-1).contiguous()
-                     for i in range(len(self.scales))]
+        self.w_first = w("first_conv").reshape(self.R, 1).contiguous()
+        self.b_first = self._b("first_conv", self.R)
+        self.w_in = _tap_major(w("upsample_net.conv_in"), self.dev)
+        self.w_up = [w(f"upsample_net.upsample.up_layers.{2 * i + 1}").reshape(-1).contiguous() for i in range(len(self.scales))]
         # fused residual-block kernels (pwg_fused.hip) need the v1 channel plan: 64 residual / 128 gate / 64 skip / 80 aux
         if fused is None:
             fused = os.environ.get("A3T_PWG_FUSED", "1") != "0"
@@ -175,20 +279,37 @@ class ParallelWaveGANGeneratorHIP(_WaveGeneratorHIP):
         self.blocks = []
         for l in range(layers):
             p = f"conv_layers.{l}."
-            blk = dict(w=conv(p + "conv.weight"), b=t(p + "conv.bias"),
-                       aux=t(p + "conv1x1_aux.weight").reshape(self.G, self.A).contiguous(),
-                       out=t(p + "conv1x1_out.weight").reshape(self.R + self.S, self.G // 2).contiguous(),
-                       bout=t(p + "conv1x1_out.bias"))
+            cw = w(p + "conv")
+            blk = dict(w=_tap_major(cw, self.dev), b=self._b(p + "conv", self.G),
+                       aux=w(p + "conv1x1_aux").reshape(self.G, self.A).contiguous(),
+                       out=w(p + "conv1x1_out").reshape(self.R + self.S, self.G // 2).contiguous(),
+                       bout=self._b(p + "conv1x1_out", self.R + self.S))
             if self.fused:      # wt0 [272][128] k-major in the gate permutation, wt1 [64][128]
-                raw = (t(p + "conv.weight"), blk["b"], blk["aux"], blk["out"])
+                raw = (cw, blk["b"], blk["aux"], blk["out"])
                 blk["wt0"], blk["b0"], blk["wt1"] = _pack_pwg_block(*raw)
                 if compute == "f16":
                     blk["w0h"], blk["b0h"], blk["w1h"] = pack_pwg_block_f16(*raw)
             self.blocks.append(blk)
-        self.w_l1 = t("last_conv_layers.1.weight").reshape(self.S, self.S).contiguous()
-        self.b_l1 = t("last_conv_layers.1.bias")
-        self.w_l3 = t("last_conv_layers.3.weight").reshape(1, self.S).contiguous()
-        self.b_l3 = t("last_conv_layers.3.bias")
+        self.w_l1 = w("last_conv_layers.1").reshape(self.S, self.S).contiguous()
+        self.b_l1 = self._b("last_conv_layers.1", self.S)
+        self.w_l3 = w("last_conv_layers.3").reshape(1, self.S).contiguous()
+        self.b_l3 = self._b("last_conv_layers.3", 1)
+        del self._sd
+
+    @classmethod
+    def from_config(cls, state_dict, generator_params: Dict, generator_type: str = "ParallelWaveGANGenerator", **kw):
+        """From the `generator_params` (and `generator_type`) of a parallel_wavegan config.yml and the checkpoint's
+        model["generator"] state dict.  kw: device, stats, fused, compute."""
+        if generator_type != "ParallelWaveGANGenerator":
+            raise NotImplementedError(f"generator_type {generator_type!r}: ParallelWaveGANGeneratorHIP builds ParallelWaveGANGenerator only")
+        fixed = {k: (v, f"generator_params.{k}: only {v!r} is built into ParallelWaveGANGeneratorHIP") for k, v in _PWG_FIXED.items()}
+        p = _config_params(dict(generator_params), _PWG_KNOWN, fixed)
+        up = dict(p.pop("upsample_params", None) or {})
+        if "upsample_scales" in up:
+            p["upsample_scales"] = up.pop("upsample_scales")
+        if up:
+            raise NotImplementedError(f"generator_params.upsample_params {sorted(up)} are not understood")
+        return cls(state_dict, **p, **kw)
 
     @torch.no_grad()
     def inference(self, c: torch.Tensor, z: Optional[torch.Tensor] = None, normalize_before: bool = False,
@@ -236,8 +357,7 @@ class ParallelWaveGANGeneratorHIP(_WaveGeneratorHIP):
         ops.linear_fwd(skips, self.w_l1, h, bias=self.b_l1, act=ACT_RELU, compute=F32)
         wav = torch.empty(B * Tw, 1, device=dev)
         ops.linear_fwd(h, self.w_l3, wav, bias=self.b_l3, compute=F32)
-        if lens is not None:
-            ops.zero_tail(wav, lens, hop, B, Tw)
+        self._zero_tail(wav, lens, hop, B, Tw)
         wav = wav.view(B, Tw, 1)
         return wav[0] if single else wav
 
@@ -278,8 +398,7 @@ class ParallelWaveGANGeneratorHIP(_WaveGeneratorHIP):
                 ops.pwg_gate(s["y"], s["ca"], s["g"])
                 ops.linear_fwd(s["g"], blk["out"], s["o"], bias=blk["bout"], compute=F32)
                 ops.pwg_res_skip(s["o"], x, skips)
-                if lens is not None:
-                    ops.zero_tail(x, lens, hop, B, Tw)
+                self._zero_tail(x, lens, hop, B, Tw)
 
     @property
     def margin_frames(self) -> int:
@@ -385,11 +504,9 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
                  resblock_kernel_sizes: Sequence[int] = (3, 7, 11), resblock_dilations=((1, 3, 5),) * 3,
                  use_additional_convs=True, bias=True, negative_slope=0.1, stats: Optional[Dict[str, np.ndarray]] = None,
                  fused=True, compute="f32"):
-        if compute not in ("f32", "f16"):
-            raise ValueError(f"compute must be 'f32' or 'f16', got {compute!r}")
+        self.compute = _check_compute(compute)
         if compute == "f16" and not fused:
             raise ValueError("compute='f16' is a mode of the fused kernels: it needs fused=True")
-        self.compute = compute
         self.scales = tuple(int(s) for s in upsample_scales)
         self.rk = tuple(int(k) for k in resblock_kernel_sizes)
         self.rd = tuple(tuple(int(d) for d in ds) for ds in resblock_dilations)
@@ -403,27 +520,12 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
             raise ValueError("resblock_dilations must have one list per entry of resblock_kernel_sizes")
         if channels % (2 ** len(self.scales)):
             raise ValueError(f"channels {channels} must be divisible by 2^{len(self.scales)}")
-        self._setup(device, in_channels, stats)
+        self._setup(device, in_channels, stats, state_dict, bias)
         self.C0, self.K = int(channels), int(kernel_size)
         self.add, self.slope = bool(use_additional_convs), float(negative_slope)
         self.upsample_factor = int(np.prod(self.scales))
-
-        def w(p):
-            return fold_weight_norm(state_dict, p)
-
-        def b(p, n, rep=1):
-            if not bias and p + ".bias" not in state_dict:
-                return None
-            v = torch.as_tensor(np.asarray(state_dict[p + ".bias"]), dtype=torch.float32)
-            if v.numel() != n:
-                raise ValueError(f"{p}.bias has {v.numel()} entries, expected {n}")
-            return v.repeat(rep).contiguous().to(self.dev)
-
-        def conv(t):              # (out, in, taps) -> [out][tap][in]
-            return t.permute(0, 2, 1).contiguous().to(self.dev)
-
-        self.w_in, self.b_in = conv(w("input_conv")), torch.as_tensor(np.asarray(state_dict["input_conv.bias"]),
-                                                                      dtype=torch.float32).to(self.dev)
+        w, b = self._w, self._b
+        self.w_in, self.b_in = _tap_major(w("input_conv"), self.dev), b("input_conv", self.C0)
         if tuple(self.w_in.shape) != (self.C0, self.K, self.A):
             raise ValueError(f"input_conv.weight {tuple(self.w_in.shape)} does not fit channels / kernel_size / in_channels")
         self.stages = []
@@ -431,7 +533,7 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
             C = self.C0 >> (i + 1)
             f16 = compute == "f16" and C in F16_WIDTHS and max(self.rk) <= 11
             st = dict(C=C, s=s, f16=f16, w_up=pack_hifigan_upsample(w(f"upsamples.{i}.1"), s).to(self.dev),
-                      b_up=torch.as_tensor(np.asarray(state_dict[f"upsamples.{i}.1.bias"]), dtype=torch.float32).repeat(s).to(self.dev),
+                      b_up=b(f"upsamples.{i}.1", C, s),
                       fused=f16 or (bool(fused) and C in (32, 64) and max(self.rk) <= 11), blocks=[])
             for j, (k, dils) in enumerate(zip(self.rk, self.rd)):
                 units = []
@@ -441,17 +543,18 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
                     ws = [w(n) for n in names]
                     units.append(dict(dil=dils[d], b=[b(n, C) for n in names],
                                       w=[(pack_hifigan_conv_f16(t).to(self.dev) if f16 else
-                                          pack_hifigan_conv(t).to(self.dev) if st["fused"] else conv(t)) for t in ws]))
+                                          pack_hifigan_conv(t).to(self.dev) if st["fused"] else _tap_major(t, self.dev)) for t in ws]))
                 st["blocks"].append(dict(k=k, units=units))
             self.stages.append(st)
         Cl = self.C0 >> len(self.scales)
         w_out = w("output_conv.1")
         if tuple(w_out.shape) != (1, Cl, self.K):
             raise NotImplementedError(f"out_channels: output_conv.1.weight {tuple(w_out.shape)} is not (1, {Cl}, {self.K})")
-        self.w_out = conv(w_out)                                      # [1][K][Cl]
-        self.b_out = torch.as_tensor(np.asarray(state_dict["output_conv.1.bias"]), dtype=torch.float32).to(self.dev)
+        self.w_out = _tap_major(w_out, self.dev)                      # [1][K][Cl]
+        self.b_out = b("output_conv.1", 1)
         self.fused_out = bool(fused) and Cl <= 64 and Cl % 4 == 0 and self.K <= 11
         self.fused = any(st["fused"] for st in self.stages)
+        del self._sd
 
     @classmethod
     def from_config(cls, state_dict, generator_params: Dict, generator_type: str = "HiFiGANGenerator", **kw):
@@ -464,30 +567,17 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
             raise NotImplementedError("out_channels != 1 is not supported (no multi-band / PQMF synthesis)")
         if int(p.pop("global_channels", -1)) > 0:
             raise NotImplementedError("global_channels > 0 (global conditioning) is not supported")
-        act = p.pop("nonlinear_activation", "LeakyReLU")
-        if act != "LeakyReLU":
-            raise NotImplementedError(f"nonlinear_activation {act!r}: only LeakyReLU is built into the kernels")
-        if p.pop("use_causal_conv", False):
-            raise NotImplementedError("use_causal_conv is not supported")
         ap = dict(p.pop("nonlinear_activation_params", None) or {"negative_slope": 0.1})
-        p.pop("use_weight_norm", None)      # the state dict says which form it holds
         if "upsample_kernal_sizes" in p:    # (the zoo's older configs spell it so)
             p["upsample_kernel_sizes"] = p.pop("upsample_kernal_sizes")
         known = ("in_channels", "channels", "kernel_size", "upsample_scales", "upsample_kernel_sizes", "resblock_kernel_sizes",
                  "resblock_dilations", "use_additional_convs", "bias")
-        unknown = sorted(set(p) - set(known))
-        if unknown:
-            raise NotImplementedError(f"generator_params {unknown} are not understood")
+        p = _config_params(p, known, dict(nonlinear_activation=_LRELU_ONLY, use_causal_conv=_NOT_CAUSAL))
         return cls(state_dict, negative_slope=float(ap.get("negative_slope", 0.01)), **p, **kw)
 
     @property
     def margin_frames(self) -> int:
         return hifigan_margin_frames(self.scales, self.rk, self.rd, self.K, self.add)
-
-    def _lrelu(self, x, slope=None):
-        y = torch.empty_like(x)
-        ops.leaky_relu(x, y, self.slope if slope is None else slope)
-        return y
 
     @torch.no_grad()
     def inference(self, c: torch.Tensor, z: Optional[torch.Tensor] = None, normalize_before: bool = False,
@@ -499,36 +589,17 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
         result (B, Tmax * hop, 1) is zero behind L_b * hop.  What the padding of c holds reaches no valid sample."""
         if z is not None:
             raise ValueError("HiFiGANGeneratorHIP.inference: z must be None, the HiFi-GAN generator has no noise input")
-        rates, r = [], 1      # the rates of the fused kernels
-        for st in self.stages:
-            r *= st["s"]
-            if st["fused"]:
-                rates.append(r)
-        if self.fused_out and r not in rates:
-            rates.append(r)
-        c, single, lens, tiles = self.prepare(c, normalize_before, lengths, rates)
+        c, single, lens, tiles = self.prepare(c, normalize_before, lengths, self._tiled_rates((1,) if self.fused_out else ()))
         B, Tf, A = c.shape
         dev = self.dev
-
-        def tail(x, rate, T):
-            if lens is not None:
-                ops.zero_tail(x, lens, rate, B, T)
-
-        c = c.contiguous()
-        if lens is not None:      # (a copy: c may be the caller's tensor)
-            c = c.clone()
-            tail(c, 1, Tf)
+        c = self._ragged_copy(c, lens)
         x = torch.empty(B * Tf, self.C0, device=dev)
         ops.conv_fwd(c.view(B * Tf, A), self.w_in, x, Tf, (self.K - 1) // 2, bias=self.b_in, compute=F32)
-        tail(x, 1, Tf)
+        self._zero_tail(x, lens, 1, B, Tf)
         T, rate = Tf, 1
         for st in self.stages:
-            C, s = st["C"], st["s"]
-            up = torch.empty(B * T, s * C, device=dev)
-            ops.conv_fwd(self._lrelu(x), st["w_up"], up, T, 1, bias=st["b_up"], compute=F32)
-            T, rate = T * s, rate * s
-            up = up.view(B * T, C)
-            tail(up, rate, T)
+            up = self._upsample(x, st["w_up"], st["b_up"], B, T, st["s"], st["C"], lens, rate, self.slope)
+            T, rate = T * st["s"], rate * st["s"]
             run = self._stage_fused if st["fused"] else self._stage_layers
             x = run(st, up, B, T, rate, lens, tiles.get(rate))
         wav = torch.empty(B * T, 1, device=dev)
@@ -538,7 +609,7 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
             ops.hfg_out(x, self.w_out.view(self.K, -1), self.b_out, wav, B, T, 0.01, tiles.get(rate))
         else:
             ops.conv_fwd(self._lrelu(x, 0.01), self.w_out, wav, T, (self.K - 1) // 2, bias=self.b_out, act=ACT_TANH, compute=F32)
-            tail(wav, rate, T)
+            self._zero_tail(wav, lens, rate, B, T)
         wav = wav.view(B, T, 1)
         return wav[0] if single else wav
 
@@ -553,13 +624,11 @@ class HiFiGANGeneratorHIP(_WaveGeneratorHIP):
                 xn, xt = bufs[u % 2], bufs[2]
                 if self.add:
                     ops.conv_fwd(self._lrelu(x), unit["w"][0], xt, T, pad, unit["dil"], bias=unit["b"][0], compute=F32)
-                    if lens is not None:
-                        ops.zero_tail(xt, lens, rate, B, T)
+                    self._zero_tail(xt, lens, rate, B, T)
                     ops.conv_fwd(self._lrelu(xt), unit["w"][1], xn, T, pad, 1, bias=unit["b"][1], R=x, compute=F32)
                 else:
                     ops.conv_fwd(self._lrelu(x), unit["w"][0], xn, T, pad, unit["dil"], bias=unit["b"][0], R=x, compute=F32)
-                if lens is not None:
-                    ops.zero_tail(xn, lens, rate, B, T)
+                self._zero_tail(xn, lens, rate, B, T)
                 x = xn
             if j == 0:
                 cs.copy_(x)
@@ -707,7 +776,7 @@ class MelGANGeneratorHIP(_WaveGeneratorHIP):
             raise ValueError(f"channels {channels} must be divisible by 2^{len(self.scales)}")
         if self.O < 1:
             raise ValueError(f"out_channels {out_channels} must be positive")
-        self._setup(device, in_channels, stats)
+        self._setup(device, in_channels, stats, state_dict, bias)
         self.C0, self.slope, self.final_tanh = int(channels), float(negative_slope), bool(use_final_nonlinear_activation)
         self.upsample_factor = int(np.prod(self.scales)) * self.O
         self.pqmf = dict(dict(taps=62, cutoff_ratio=0.142, beta=9.0), **(pqmf or {})) if self.O > 1 else None
@@ -716,24 +785,10 @@ class MelGANGeneratorHIP(_WaveGeneratorHIP):
                 raise NotImplementedError(f"pqmf: {self.O} sub-bands / {self.pqmf['taps']} taps: a3t_pqmf_synthesis is built for <= 8 / <= 254")
             self.h_syn = torch.from_numpy(pqmf_synthesis_filter(self.O, **self.pqmf)).to(self.dev)
         self.min_frames = melgan_min_frames(self.scales, self.nstacks, self.ks, self.K)
-
-        def w(p):
-            return fold_weight_norm(state_dict, p)
-
-        def b(p, n, rep=1):
-            if not bias and p + ".bias" not in state_dict:
-                return None
-            v = torch.as_tensor(np.asarray(state_dict[p + ".bias"]), dtype=torch.float32)
-            if v.numel() != n:
-                raise ValueError(f"{p}.bias has {v.numel()} entries, expected {n}")
-            return v.repeat(rep).contiguous().to(self.dev)
-
-        def conv(t):              # (out, in, taps) -> [out][tap][in]
-            return t.permute(0, 2, 1).contiguous().to(self.dev)
-
+        w, b = self._w, self._b
         # the reference's Sequential: 0 pad, 1 conv | per stage: activation, transposed conv, `stacks` ResidualStacks | activation,
         # pad, conv (, tanh)
-        self.w_in, self.b_in = conv(w("melgan.1")), b("melgan.1", self.C0)
+        self.w_in, self.b_in = _tap_major(w("melgan.1"), self.dev), b("melgan.1", self.C0)
         if tuple(self.w_in.shape) != (self.C0, self.K, self.A):
             raise ValueError(f"melgan.1.weight {tuple(self.w_in.shape)} does not fit channels / kernel_size / in_channels")
         self.stages, idx = [], 2
@@ -751,17 +806,18 @@ class MelGANGeneratorHIP(_WaveGeneratorHIP):
                 if st["fused"]:
                     unit["w"], unit["b"] = (t.to(self.dev) for t in pack_melgan_stack(*raw))
                 else:
-                    unit.update(w1=conv(raw[0]), b1=raw[1], w2=raw[2].reshape(C, C).contiguous().to(self.dev), b2=raw[3],
+                    unit.update(w1=_tap_major(raw[0], self.dev), b1=raw[1], w2=raw[2].reshape(C, C).contiguous().to(self.dev), b2=raw[3],
                                 ws=raw[4].reshape(C, C).contiguous().to(self.dev), bs=raw[5])
                 st["stacks"].append(unit)
             self.stages.append(st)
             idx += 2 + self.nstacks
         Cl = self.C0 >> len(self.scales)
-        self.w_out, self.b_out = conv(w(f"melgan.{idx + 2}")), b(f"melgan.{idx + 2}", self.O)      # [O][K][Cl]
+        self.w_out, self.b_out = _tap_major(w(f"melgan.{idx + 2}"), self.dev), b(f"melgan.{idx + 2}", self.O)      # [O][K][Cl]
         if tuple(self.w_out.shape) != (self.O, self.K, Cl):
             raise ValueError(f"melgan.{idx + 2}.weight {tuple(self.w_out.shape)} does not fit out_channels / kernel_size / channels")
         self.fused_out = bool(fused) and Cl <= 64 and Cl % 2 == 0 and self.O <= 4 and self.K <= 11
         self.fused = self.fused_out or any(st["fused"] for st in self.stages)
+        del self._sd
 
     @classmethod
     def from_config(cls, state_dict, generator_params: Dict, generator_type: str = "MelGANGenerator",
@@ -771,23 +827,14 @@ class MelGANGeneratorHIP(_WaveGeneratorHIP):
         if generator_type != "MelGANGenerator":
             raise NotImplementedError(f"generator_type {generator_type!r}: MelGANGeneratorHIP builds MelGANGenerator only")
         p = dict(generator_params)
-        pad = p.pop("pad", "ReflectionPad1d")
-        if pad != "ReflectionPad1d":
-            raise NotImplementedError(f"pad {pad!r}: only ReflectionPad1d is built into the kernels")
         if p.pop("pad_params", None):
             raise NotImplementedError("pad_params must be empty (ReflectionPad1d takes none)")
-        act = p.pop("nonlinear_activation", "LeakyReLU")
-        if act != "LeakyReLU":
-            raise NotImplementedError(f"nonlinear_activation {act!r}: only LeakyReLU is built into the kernels")
-        if p.pop("use_causal_conv", False):
-            raise NotImplementedError("use_causal_conv is not supported")
         ap = dict(p.pop("nonlinear_activation_params", None) or {"negative_slope": 0.2})
-        p.pop("use_weight_norm", None)      # the state dict says which form it holds
         known = ("in_channels", "out_channels", "kernel_size", "channels", "upsample_scales", "stack_kernel_size", "stacks", "bias",
                  "use_final_nonlinear_activation")
-        unknown = sorted(set(p) - set(known))
-        if unknown:
-            raise NotImplementedError(f"generator_params {unknown} are not understood")
+        fixed = dict(pad=("ReflectionPad1d", "pad {!r}: only ReflectionPad1d is built into the kernels"),
+                     nonlinear_activation=_LRELU_ONLY, use_causal_conv=_NOT_CAUSAL)
+        p = _config_params(p, known, fixed)
         p.setdefault("out_channels", 1)      # (the reference constructor's defaults, where they differ from this class's)
         p.setdefault("channels", 512)
         p.setdefault("upsample_scales", [8, 8, 2, 2])
@@ -820,41 +867,23 @@ class MelGANGeneratorHIP(_WaveGeneratorHIP):
         if short:
             raise ValueError(f"MelGANGeneratorHIP.inference: {short[0]} frames are fewer than min_frames = {self.min_frames} "
                              "(a reflection must be shorter than the signal it pads)")
-        rates, r = [], 1      # the rates of the tiled kernels
-        for st in self.stages:
-            r *= st["s"]
-            if st["fused"]:
-                rates.append(r)
-        if self.fused_out and r not in rates:
-            rates.append(r)
-        if self.pqmf is not None and r * self.O not in rates:
-            rates.append(r * self.O)
+        rates = self._tiled_rates(((1,) if self.fused_out else ()) + ((self.O,) if self.pqmf is not None else ()))
         c, single, lens, tiles = self.prepare(c, normalize_before, lengths, rates)
         B, Tf, A = c.shape
         dev, half = self.dev, (self.K - 1) // 2
         Lmin = min([int(n) for n in lengths if int(n) > 0], default=Tf) if lengths is not None else Tf
 
-        def tail(x, rate, T):
-            if lens is not None:
-                ops.zero_tail(x, lens, rate, B, T)
-
         def buf(T, C):      # the tiled kernels write nothing behind a row's end: what reads it next finds zeros there
             return (torch.zeros if lens is not None else torch.empty)(B * T, C, device=dev)
 
-        c = c.contiguous()
-        if lens is not None:      # (a copy: c may be the caller's tensor)
-            c = c.clone()
-            tail(c, 1, Tf)
+        c = self._ragged_copy(c, lens)
         x = self._conv_reflect(c.view(B * Tf, A), self.w_in, self.b_in, B, Tf, half, 1, lens, 1)
-        tail(x, 1, Tf)
+        self._zero_tail(x, lens, 1, B, Tf)
         T, rate = Tf, 1
         for st in self.stages:
-            C, s = st["C"], st["s"]
-            up = torch.empty(B * T, s * C, device=dev)
-            ops.conv_fwd(self._lrelu(x), st["w_up"], up, T, 1, bias=st["b_up"], compute=F32)
-            T, rate = T * s, rate * s
-            x = up.view(B * T, C)
-            tail(x, rate, T)
+            C = st["C"]
+            x = self._upsample(x, st["w_up"], st["b_up"], B, T, st["s"], C, lens, rate, self.slope)
+            T, rate = T * st["s"], rate * st["s"]
             pp = [buf(T, C), buf(T, C)] if st["fused"] else None
             for j, u in enumerate(st["stacks"]):
                 if st["fused"]:
@@ -863,14 +892,14 @@ class MelGANGeneratorHIP(_WaveGeneratorHIP):
                 else:
                     x = self._stack_layers(u, x, B, T, rate, lens)
             if not st["fused"]:
-                tail(x, rate, T)
+                self._zero_tail(x, lens, rate, B, T)
         if self.fused_out:
             y = buf(T, self.O)
             ops.mgan_out(x, self.w_out, self.b_out, y, B, T, self.slope, self.final_tanh, tiles.get(rate), Lmin * rate)
         else:
             y = self._conv_reflect(self._lrelu(x), self.w_out, self.b_out, B, T, half, 1, lens, rate,
                                    ACT_TANH if self.final_tanh else 0)
-            tail(y, rate, T)
+            self._zero_tail(y, lens, rate, B, T)
         if self.pqmf is not None:
             wav = buf(T * self.O, 1)
             ops.pqmf_synthesis(y, self.h_syn, wav, B, T, tiles.get(rate * self.O))
@@ -879,11 +908,6 @@ class MelGANGeneratorHIP(_WaveGeneratorHIP):
             wav = y
         wav = wav.view(B, T, 1)
         return wav[0] if single else wav
-
-    def _lrelu(self, x):
-        y = torch.empty_like(x)
-        ops.leaky_relu(x, y, self.slope)
-        return y
 
     def _conv_reflect(self, x, w, bias, B, T, half, dil, lens, rate, act=0):
         """conv(reflect_pad(x)) layer by layer, the convolution of 2 half + 1 taps at dilation dil: x [B*T][Cin] is padded by
@@ -951,22 +975,13 @@ class StyleMelGANGeneratorHIP(_WaveGeneratorHIP):
                                       "the reference cannot run either")
         if any(s < 1 for s in self.noise_scales + self.scales) or int(dilation) < 1:
             raise ValueError("scales and dilation must be positive")
-        self._setup(device, aux_channels, stats)
+        self._setup(device, aux_channels, stats, state_dict, bias)
         self.Z, self.C, self.K, self.dil = int(in_channels), 64, int(kernel_size), int(dilation)
         self.noise_slope, self.sigmoid = float(noise_upsample_negative_slope), gated_function == "sigmoid"
         self.noise_upsample_factor = int(np.prod(self.noise_scales))
         self.hop = self.upsample_factor = int(np.prod(self.scales))
 
-        def w(p):
-            return fold_weight_norm(state_dict, p)
-
-        def b(p, n, rep=1):
-            if not bias and p + ".bias" not in state_dict:
-                return None
-            v = torch.as_tensor(np.asarray(state_dict[p + ".bias"]), dtype=torch.float32)
-            if v.numel() != n:
-                raise ValueError(f"{p}.bias has {v.numel()} entries, expected {n}")
-            return v.repeat(rep).contiguous().to(self.dev)
+        w, b = self._w, self._b
 
         def conv(p, cout, cin):      # Conv1d [cout][cin][K] -> the k-major operand [K*cin][cout]
             t = w(p)
@@ -992,6 +1007,7 @@ class StyleMelGANGeneratorHIP(_WaveGeneratorHIP):
             raise ValueError(f"output_conv.0.weight {tuple(w_out.shape)} is not (1, {self.C}, {self.K})")
         self.w_out = w_out[0].t().contiguous().to(self.dev)      # [K][C]
         self.b_out = b("output_conv.0", 1)
+        del self._sd
 
     @classmethod
     def from_config(cls, state_dict, generator_params: Dict, generator_type: str = "StyleMelGANGenerator", **kw):
@@ -1000,20 +1016,13 @@ class StyleMelGANGeneratorHIP(_WaveGeneratorHIP):
         if generator_type != "StyleMelGANGenerator":
             raise NotImplementedError(f"generator_type {generator_type!r}: StyleMelGANGeneratorHIP builds StyleMelGANGenerator only")
         p = dict(generator_params)
-        mode = p.pop("upsample_mode", "nearest")
-        if mode != "nearest":
-            raise NotImplementedError(f"upsample_mode {mode!r}: only nearest is built into a3t_smg_conv")
-        act = p.pop("noise_upsample_activation", "LeakyReLU")
-        if act != "LeakyReLU":
-            raise NotImplementedError(f"noise_upsample_activation {act!r}: only LeakyReLU is built here")
         ap = p.pop("noise_upsample_activation_params", None)
         ap = {"negative_slope": 0.2} if ap is None else dict(ap)      # (given but empty: torch's own default, 0.01)
-        p.pop("use_weight_norm", None)      # the state dict says which form it holds
         known = ("in_channels", "aux_channels", "channels", "out_channels", "kernel_size", "dilation", "bias", "noise_upsample_scales",
                  "upsample_scales", "gated_function")
-        unknown = sorted(set(p) - set(known))
-        if unknown:
-            raise NotImplementedError(f"generator_params {unknown} are not understood")
+        fixed = dict(upsample_mode=("nearest", "upsample_mode {!r}: only nearest is built into a3t_smg_conv"),
+                     noise_upsample_activation=("LeakyReLU", "noise_upsample_activation {!r}: only LeakyReLU is built here"))
+        p = _config_params(p, known, fixed)
         p.setdefault("noise_upsample_scales", [11, 2, 2, 2])      # (the reference constructor's defaults, where they differ)
         p.setdefault("upsample_scales", [2, 2, 2, 2, 2, 2, 2, 2, 1])
         return cls(state_dict, noise_upsample_negative_slope=float(ap.get("negative_slope", 0.01)), **p, **kw)
@@ -1034,22 +1043,12 @@ class StyleMelGANGeneratorHIP(_WaveGeneratorHIP):
         over the row's own n_eff_b * rate samples, and the result (B, Tmax * hop, 1) is zero behind L_b * hop.  What the padding of
         c and z holds reaches no valid sample."""
         F, hop, dev = self.noise_upsample_factor, self.hop, self.dev
-        single = c.dim() == 2
-        c = c.to(dev, torch.float32)
-        if single:
-            if lengths is not None:
-                raise ValueError("lengths= goes with a (B, Tmax, aux) batch")
-            c = c[None]
+        c, single, rows = self._check_input(c, normalize_before, lengths)
         B, Tf, A = c.shape
-        if A != self.A:
-            raise ValueError(f"c has {A} channels, the generator {self.A}")
         if Tf < 1:
             raise ValueError("StyleMelGANGeneratorHIP.inference: c has no frames")
-        if normalize_before and self.stats is not None:
-            c = (c - self.stats[0]) / self.stats[1]
-        rows = [Tf] * B if lengths is None else [int(n) for n in lengths]
-        if len(rows) != B or any(n < 0 or n > Tf for n in rows):
-            raise ValueError(f"lengths {rows} do not fit a batch of {B} rows of {Tf} frames")
+        if rows is None:
+            rows = [Tf] * B
         msteps = [-(-n // F) for n in rows]
         M = -(-Tf // F)
         Te = M * F
@@ -1062,17 +1061,8 @@ class StyleMelGANGeneratorHIP(_WaveGeneratorHIP):
         rates = sorted(set(np.cumprod((1,) + self.scales).tolist()))
         lens = mlen = None
         tiles = {}
-        if lengths is not None:      # one H2D copy: lengths | noise steps | one tile list of the n_eff per rate
-            lists = [pwg_tile_list([m * F for m in msteps], r) for r in rates]
-            Bp = (B + 3) // 4 * 4
-            offs = np.cumsum([2 * Bp] + [tl.size for tl in lists]).tolist()
-            host = np.zeros(offs[-1], dtype=np.int32)
-            host[:B], host[Bp:Bp + B] = rows, msteps
-            for o, tl in zip(offs, lists):
-                host[o:o + tl.size] = tl.reshape(-1)
-            meta = torch.from_numpy(host).to(dev)
-            lens, mlen = meta[:B], meta[Bp:Bp + B]
-            tiles = {r: meta[o:o + tl.size].view(len(tl), 4) for r, o, tl in zip(rates, offs, lists)}
+        if lengths is not None:      # lengths | noise steps | one tile list of the n_eff per rate
+            (lens, mlen), tiles = self._pack_meta([rows, msteps], [m * F for m in msteps], rates)
             x = x.clone()
             ops.zero_tail(x, mlen, 1, B, M)
         # ---- c padded to n_eff frames with each row's own last frame (a gather of frame indices)
@@ -1082,13 +1072,8 @@ class StyleMelGANGeneratorHIP(_WaveGeneratorHIP):
         # ---- noise path: transposed convolutions as 3-tap convolutions, LeakyReLU behind each
         T = M
         for st in self.noise:
-            up = torch.empty(B * T, st["s"] * self.C, device=dev)
-            ops.conv_fwd(x, st["w"], up, T, 1, bias=st["b"], compute=F32)
+            x = self._upsample(x, st["w"], st["b"], B, T, st["s"], self.C, mlen, T // M, self.noise_slope, after=True)
             T *= st["s"]
-            x = up.view(B * T, self.C)
-            ops.leaky_relu(x, x, self.noise_slope)
-            if lens is not None:
-                ops.zero_tail(x, mlen, T // M, B, T)
         # ---- TADEResBlocks
         rate = 1
         for blk in self.blocks:
@@ -1096,8 +1081,7 @@ class StyleMelGANGeneratorHIP(_WaveGeneratorHIP):
         Tw = Te * hop
         wav = (torch.zeros if lens is not None else torch.empty)(B * Tw, 1, device=dev)
         ops.hfg_out(x, self.w_out, self.b_out, wav, B, Tw, 1.0, tiles.get(hop))      # slope 1: no activation in front
-        if lens is not None:
-            ops.zero_tail(wav, lens, hop, B, Tw)
+        self._zero_tail(wav, lens, hop, B, Tw)
         wav = wav.view(B, Tw, 1)[:, :Tf * hop]
         return wav[0] if single else wav.contiguous()
 
@@ -1128,36 +1112,17 @@ class StyleMelGANGeneratorHIP(_WaveGeneratorHIP):
 
 
 # ------------------------------------------------------------------------------------------ a generator from a config
-_PWG_KNOWN = ("layers", "stacks", "residual_channels", "gate_channels", "skip_channels", "aux_channels", "aux_context_window",
-              "upsample_params")
-_PWG_FIXED = dict(in_channels=1, out_channels=1, kernel_size=3, dropout=0.0, dropout_rate=0.0, bias=True,
-                  use_causal_conv=False, upsample_conditional_features=True, upsample_net="ConvInUpsampleNetwork")
-
-
 def generator_from_config(state_dict, config: Dict, **kw):
     """The generator class of a parallel_wavegan checkpoint's config (the dict of its config.yml: generator_type,
     generator_params and, for multi-band MelGAN, pqmf_params) over the checkpoint's model["generator"] state dict: what the
     reference driver's load_vocoder(tag) does once the files are on disk.  kw: device, stats, fused (and compute, where the class
     has it)."""
     gtype = config.get("generator_type", "ParallelWaveGANGenerator")
-    params = dict(config.get("generator_params") or {})
-    if gtype == "MelGANGenerator":
-        return MelGANGeneratorHIP.from_config(state_dict, params, gtype, pqmf_params=config.get("pqmf_params"), **kw)
-    if gtype == "HiFiGANGenerator":
-        return HiFiGANGeneratorHIP.from_config(state_dict, params, gtype, **kw)
-    if gtype != "ParallelWaveGANGenerator":
+    classes = dict(ParallelWaveGANGenerator=ParallelWaveGANGeneratorHIP, HiFiGANGenerator=HiFiGANGeneratorHIP,
+                   MelGANGenerator=MelGANGeneratorHIP)
+    if gtype not in classes:
         raise NotImplementedError(f"generator_type {gtype!r}: ParallelWaveGANGenerator, HiFiGANGenerator and MelGANGenerator are built here"
                                   + (" (a StyleMelGANGenerator: StyleMelGANGeneratorHIP.from_config)" if gtype == "StyleMelGANGenerator" else ""))
-    params.pop("use_weight_norm", None)
-    for k, v in _PWG_FIXED.items():
-        if k in params and params.pop(k) != v:
-            raise NotImplementedError(f"generator_params.{k}: only {v!r} is built into ParallelWaveGANGeneratorHIP")
-    unknown = sorted(set(params) - set(_PWG_KNOWN))
-    if unknown:
-        raise NotImplementedError(f"generator_params {unknown} are not understood")
-    up = dict(params.pop("upsample_params", None) or {})
-    if "upsample_scales" in up:
-        params["upsample_scales"] = up.pop("upsample_scales")
-    if up:
-        raise NotImplementedError(f"generator_params.upsample_params {sorted(up)} are not understood")
-    return ParallelWaveGANGeneratorHIP(state_dict, **params, **kw)
+    if gtype == "MelGANGenerator":
+        kw = dict(kw, pqmf_params=config.get("pqmf_params"))
+    return classes[gtype].from_config(state_dict, dict(config.get("generator_params") or {}), gtype, **kw)

@@ -1,8 +1,10 @@
 """Host-side tests of the StyleMelGAN generator (a3t_amd/vocoder.py::StyleMelGANGeneratorHIP): the torch restatement
 (tests/stylemelgan_ref.py) against the reference's outputs (tests/golden/stylemelgan.{npz,json}), its row rule, the noise-length
-arithmetic, the packed operands, every refusal by field name and SpeechEditor's whole-utterance fallback.  No GPU."""
+arithmetic, the packed operands, every refusal by field name, what a ragged batch hands its launches and SpeechEditor's
+whole-utterance fallback.  No GPU."""
 import json
 import os
+import re
 from types import SimpleNamespace
 
 import numpy as np
@@ -180,6 +182,53 @@ def test_a_noise_of_the_wrong_shape_is_refused_before_any_launch(states):
         gen.inference(torch.zeros(2, 13, 80), torch.zeros(2, 3, 32), lengths=(13, 14))
     with pytest.raises(ValueError, match="channels"):
         gen.inference(torch.zeros(13, 64), torch.zeros(3, 32))
+
+
+def test_a_ragged_batch_goes_through_the_shared_preamble(states, monkeypatch):
+    """What the launches of a ragged inference are given (every ops wrapper replaced by a recorder, so it runs without a GPU): the
+    rows' lengths, their noise steps and, at every rate, the tile list of the rows' network lengths n_eff = ceil(L / F) * F;
+    lengths are refused in prepare()'s words."""
+    from a3t_amd import ops
+    from a3t_amd.vocoder import StyleMelGANGeneratorHIP, pwg_tile_list
+    cfg = R.ODD
+    gen = StyleMelGANGeneratorHIP(states["odd"], device="cpu", **cfg)
+    assert gen.noise_upsample_factor == 6 and gen.scales == (3, 2, 1)
+    calls = []
+    for name in ("zero_tail", "conv_fwd", "leaky_relu", "smg_stats", "smg_conv", "hfg_out"):
+        monkeypatch.setattr(ops, name, lambda *a, _n=name, **kw: calls.append((_n, a, kw)))
+    c, z = torch.randn(2, 9, 80), torch.randn(2, 2, 32)
+    y = gen.inference(c, z, lengths=[9, 4])
+    assert gen.hop == 6 and y.shape == (2, 9 * 6, 1)
+    tails = [a for n, a, _ in calls if n == "zero_tail"]
+    assert tails[0][1].tolist() == [2, 1] and tails[0][2:] == (1, 2, 2)             # the noise: 2 and 1 steps of the 2
+    assert [t[1].tolist() for t in tails[1:3]] == [[2, 1]] * 2 and [t[2:] for t in tails[1:3]] == [(3, 2, 6), (6, 2, 12)]
+    assert tails[-1][1].tolist() == [9, 4] and tails[-1][2:] == (6, 2, 12 * 6) and len(tails) == 4
+    assert all(t[1].dtype == torch.int32 for t in tails)
+    seen = {}
+    for n, a, kw in calls:      # tiles of smg_conv (keyword; a = (x, w, b, y, B, T)), smg_stats (x, st, B, T, tiles), hfg_out
+        tl, T = (kw["tiles"], a[5]) if n == "smg_conv" else (a[4], a[3]) if n == "smg_stats" else (a[7], a[5]) if n == "hfg_out" else (None, 0)
+        if tl is not None:
+            assert T % 12 == 0 and tl.dtype == torch.int32 and tl.is_contiguous() and tl.storage_offset() % 4 == 0
+            assert tl.untyped_storage().data_ptr() == tails[-1][1].untyped_storage().data_ptr()      # one buffer, one copy
+            seen.setdefault(T // 12, tl)
+            assert tl is seen[T // 12]
+    assert sorted(seen) == sorted(set(np.cumprod([1] + cfg["upsample_scales"]).tolist())) == [1, 3, 6]
+    for rate, tl in seen.items():
+        assert np.array_equal(tl.numpy(), pwg_tile_list([12, 6], rate))
+    assert [n for n, _, _ in calls].count("smg_conv") == 18 and all(kw["tiles"] is not None for n, _, kw in calls if n == "smg_conv")
+    hfg = [a for n, a, _ in calls if n == "hfg_out"]
+    assert len(hfg) == 1 and hfg[0][7] is seen[6]
+    # the refusals of the shared input check, in its words
+    with pytest.raises(ValueError, match=re.escape("lengths= goes with a (B, Tmax, aux) batch")):
+        gen.inference(c[0], z[0], lengths=[9])
+    for bad in ([9], [9, 4, 1], [9, 10], [9, -1]):
+        with pytest.raises(ValueError, match=re.escape(f"lengths {bad} do not fit a batch of 2 rows of 9 frames")):
+            gen.inference(c, z, lengths=bad)
+    # a dense batch packs nothing: no list, no tail to zero
+    calls.clear()
+    assert gen.inference(c, z).shape == (2, 9 * 6, 1)
+    assert not [n for n, _, _ in calls if n == "zero_tail"]
+    assert all(kw["tiles"] is None for n, _, kw in calls if n == "smg_conv")
 
 
 # --------------------------------------------------------------------------------------------------------- SpeechEditor
