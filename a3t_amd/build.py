@@ -15,7 +15,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # The direct-to-LDS GEMM variants are tuned to a register budget (<= 128 VGPRs = 4 workgroups per CU); a harmless
 # looking edit can push one over the edge and cost 30-50 % on that GEMM class.  The build records what the compiler
 # allocated; tests/test_host_logic.py::test_gemm_register_budget checks it.
-RES_SOURCES = ("gemm_bf16.hip", "gemm_bf16_8p.hip", "gemm_bf16_tn.hip", "gemm_bf16_pn.hip", "gemm_bf16_tt.hip", "attn_fused.hip", "norm_reduce.hip")
+# The waveform kernels share their loops through headers (wave_conv.h, wave_tiles.h), where one edit moves the registers of
+# several kernels at once: test_wave_kernel_register_budget holds each to no scratch and to its occupancy.
+WAVE_SOURCES = ("pwg_fused.hip", "pwg_fused_f16.hip", "hifigan.hip", "hifigan_f16.hip", "melgan.hip", "stylemelgan.hip")
+RES_SOURCES = ("gemm_bf16.hip", "gemm_bf16_8p.hip", "gemm_bf16_tn.hip", "gemm_bf16_pn.hip", "gemm_bf16_tt.hip", "attn_fused.hip", "norm_reduce.hip") + WAVE_SOURCES
 RES_FLAG = ["-Rpass-analysis=kernel-resource-usage"]
 
 

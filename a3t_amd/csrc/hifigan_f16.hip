@@ -48,8 +48,6 @@
 #include "../../include/a3t_hip.h"
 #include "wave_tiles.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 struct HfgF16Args {
     const float* x;       // [B*Tw][C] conv input (read through LeakyReLU)
     const uint4* wf;      // [taps*C/16][C/32][64] fragments of 8 halves
@@ -62,20 +60,6 @@ struct HfgF16Args {
     int B, Tw, taps, dil, tiles_t;
     const int4* tiles;    // RAGGED: [ntiles] tile list (wave_tiles.h)
 };
-
-__device__ __forceinline__ float leaky_sat16(float v, float slope) {
-    v = v > 0.f ? v : v * slope;
-    return fminf(fmaxf(v, -65504.f), 65504.f);
-}
-
-// h(leaky()) of eight consecutive channels
-__device__ __forceinline__ f16x8 pack_leaky_f16(float4 v0, float4 v1, float s) {
-    f16x8 q;
-    q[0] = (_Float16)leaky_sat16(v0.x, s), q[1] = (_Float16)leaky_sat16(v0.y, s), q[2] = (_Float16)leaky_sat16(v0.z, s);
-    q[3] = (_Float16)leaky_sat16(v0.w, s), q[4] = (_Float16)leaky_sat16(v1.x, s), q[5] = (_Float16)leaky_sat16(v1.y, s);
-    q[6] = (_Float16)leaky_sat16(v1.z, s), q[7] = (_Float16)leaky_sat16(v1.w, s);
-    return q;
-}
 
 template <int C, bool RAGGED>
 __global__ __launch_bounds__(512, C <= 64 ? 2 : 1) void hfg_conv_f16_kernel(HfgF16Args a) {
@@ -116,7 +100,7 @@ __global__ __launch_bounds__(512, C <= 64 ? 2 : 1) void hfg_conv_f16_kernel(HfgF
         for (int i = 0; i < NQ; ++i)
             if (FR >= 8 || tid < FR * 64) Ws[buf][i * 512 + tid] = Q[i];
 #pragma unroll
-        for (int s = 0; s < KSC; ++s) bf[s] = pack_leaky_f16(P[s][0], P[s][1], a.slope);
+        for (int s = 0; s < KSC; ++s) bf[s] = pack_f16_sat(leaky(P[s][0], a.slope), leaky(P[s][1], a.slope));      // h(leaky())
     };
 
     f32x16 acc[MT];
@@ -176,11 +160,10 @@ __global__ __launch_bounds__(512, C <= 64 ? 2 : 1) void hfg_conv_f16_kernel(HfgF
 
 template <int C>
 static int hfg_conv_f16_launch(const HfgF16Args& a, int ntiles, void* stream) {
-    if (a.tiles)
-        hipLaunchKernelGGL((hfg_conv_f16_kernel<C, true>), dim3(ntiles), dim3(512), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((hfg_conv_f16_kernel<C, false>), dim3(ntiles), dim3(512), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    return wave_ragged(a.tiles, [&](auto ragged) {
+        hipLaunchKernelGGL((hfg_conv_f16_kernel<C, decltype(ragged)::value>), dim3(ntiles), dim3(512), 0, (hipStream_t)stream, a);
+        return (int)hipGetLastError();
+    });
 }
 
 // a3t_hfg_conv with fp16 operands.  wf: the fp16 fragments of vocoder.pack_hifigan_conv_f16, [taps*C/16][C/32][64][8]:

@@ -25,19 +25,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/a3t_hip.h"
-#include "wave_tiles.h"
+#include "wave_conv.h"
 
 namespace {
-
-__device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
-
-// ReflectionPad1d's index for a row of W samples, clamped so that an index outside the contract (|ts| beyond one reflection)
-// still stays inside the row
-__device__ __forceinline__ int64_t refl(int64_t ts, int64_t W) {
-    if (ts < 0) ts = -ts;
-    if (ts >= W) ts = 2 * (W - 1) - ts;
-    return ts < 0 ? 0 : (ts >= W ? W - 1 : ts);
-}
 
 struct MgsArgs {
     const float* x;       // [B*Tw][C]
@@ -175,11 +165,10 @@ __global__ __launch_bounds__(256) void mgan_stack_kernel(MgsArgs a) {
 
 template <int C>
 int mgan_stack_launch(const MgsArgs& a, int ntiles, void* stream) {
-    if (a.tiles)
-        hipLaunchKernelGGL((mgan_stack_kernel<C, true>), dim3(2 * ntiles), dim3(256), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((mgan_stack_kernel<C, false>), dim3(2 * ntiles), dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    return wave_ragged(a.tiles, [&](auto ragged) {
+        hipLaunchKernelGGL((mgan_stack_kernel<C, decltype(ragged)::value>), dim3(2 * ntiles), dim3(256), 0, (hipStream_t)stream, a);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace
@@ -198,70 +187,15 @@ extern "C" int a3t_mgan_stack(const float* x, const float* w, const float* bias,
                                                                    : mgan_stack_launch<192>(a, n, stream);
 }
 
-// ---------------------------------------------------------------- output convolution: C -> O <= 4, LeakyReLU in front, reflection
-// a3t_hfg_out's shape: one workgroup per 256-sample tile, the tile's rows with their (K-1)/2 halo (reflected at the row's own
-// ends) pass through LeakyReLU into LDS (row stride C + 1), one output sample per thread, two partial sums per output channel.
-namespace {
-template <bool RAGGED>
-__global__ __launch_bounds__(256) void mgan_out_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                       const float* __restrict__ bias, float* __restrict__ y, float slope, int C,
-                                                       int O, int K, int act_tanh, int Tw, int tiles_t,
-                                                       const int4* __restrict__ tiles) {
-    constexpr int TILE = 256;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int rows = TILE + K - 1, ld = C + 1, half = (K - 1) / 2;
-    float* Xs = lds;                   // [rows][C + 1]
-    float* Wk = lds + rows * ld;       // [O][K][C]
-    const int tid = threadIdx.x;
-    const auto [b, t0, Wb] = wave_tile<RAGGED>(tiles, blockIdx.x, tiles_t, Tw);
-    const float* xb = x + (int64_t)b * Tw * C;
-    for (int i = tid; i < rows * C; i += 256) {
-        const int r = i / C, c = i - r * C;
-        Xs[r * ld + c] = leaky(xb[refl((int64_t)t0 - half + r, Wb) * C + c], slope);
-    }
-    for (int i = tid; i < O * K * C; i += 256) Wk[i] = w[i];
-    __syncthreads();
-    const int t = t0 + tid;
-    if (t >= Wb) return;
-    float s[4][2] = {};
-    for (int tap = 0; tap < K; ++tap) {
-        const float* xr = Xs + (tid + tap) * ld;
-        for (int c = 0; c < C; c += 2) {
-            const float x0 = xr[c], x1 = xr[c + 1];
-#pragma unroll
-            for (int o = 0; o < 4; ++o)
-                if (o < O) {
-                    const float* wr = Wk + (o * K + tap) * C + c;
-                    s[o][0] = fmaf(x0, wr[0], s[o][0]);
-                    s[o][1] = fmaf(x1, wr[1], s[o][1]);
-                }
-        }
-    }
-#pragma unroll
-    for (int o = 0; o < 4; ++o)
-        if (o < O) {
-            const float v = (s[o][0] + s[o][1]) + (bias ? bias[o] : 0.f);
-            y[((int64_t)b * Tw + t) * O + o] = act_tanh ? tanhf(v) : v;
-        }
-}
-}  // namespace
-
+// Output convolution, C -> O <= 4, LeakyReLU in front: wave_out_kernel (wave_conv.h) with the halo reflected at the row's own
+// ends and two partial sums per output channel over c % 2.
 extern "C" int a3t_mgan_out(const float* x, const float* w, const float* bias, float* y, float slope, int act_tanh,
                             const int32_t* tiles, int ntiles, int wmin, int B, int Tw, int C, int O, int K, void* stream) {
     if (!x || !w || !y || C < 2 || C > 64 || (C & 1) || O < 1 || O > 4 || K < 1 || K > 11 || !(K & 1)) return A3T_EINVAL;
     const int n = wave_grid(tiles, ntiles, B, Tw);
     if (n <= 0) return n;
     if ((K - 1) / 2 >= (tiles ? wmin : Tw)) return A3T_EINVAL;      // the reflection needs (K-1)/2 < W_b
-    const int lds = ((256 + K - 1) * (C + 1) + O * K * C) * 4, tiles_t = wave_tiles_t(Tw);      // more than 64 KiB at C = 64
-    const hipError_t e = tiles ? wave_lds_opt_in<mgan_out_kernel<true>>(lds) : wave_lds_opt_in<mgan_out_kernel<false>>(lds);
-    if (e != hipSuccess) return (int)e;
-    if (tiles)
-        hipLaunchKernelGGL(mgan_out_kernel<true>, dim3(n), dim3(256), lds, (hipStream_t)stream, x, w, bias, y, slope, C, O, K,
-                           act_tanh, Tw, tiles_t, (const int4*)tiles);
-    else
-        hipLaunchKernelGGL(mgan_out_kernel<false>, dim3(n), dim3(256), lds, (hipStream_t)stream, x, w, bias, y, slope, C, O, K,
-                           act_tanh, Tw, tiles_t, (const int4*)nullptr);
-    return (int)hipGetLastError();
+    return wave_out_launch<true, 2, 4>(x, w, bias, y, slope, act_tanh, tiles, n, Tw, C, O, K, stream);
 }
 
 // ---------------------------------------------------------------- PQMF synthesis
@@ -319,13 +253,11 @@ extern "C" int a3t_pqmf_synthesis(const float* x, const float* h, float* y, cons
     const int n = wave_grid(tiles, ntiles, B, Tw);
     if (n <= 0) return n;
     const int lds = (((255 + taps) / S + 2) * S + S * (taps + 1)) * 4, tiles_t = wave_tiles_t(Tw);
-    if (tiles)
-        hipLaunchKernelGGL(pqmf_synthesis_kernel<true>, dim3(n), dim3(256), lds, (hipStream_t)stream, x, h, y, S, taps, Tw,
-                           tiles_t, (const int4*)tiles);
-    else
-        hipLaunchKernelGGL(pqmf_synthesis_kernel<false>, dim3(n), dim3(256), lds, (hipStream_t)stream, x, h, y, S, taps, Tw,
-                           tiles_t, (const int4*)nullptr);
-    return (int)hipGetLastError();
+    return wave_ragged(tiles, [&](auto ragged) {
+        hipLaunchKernelGGL(pqmf_synthesis_kernel<decltype(ragged)::value>, dim3(n), dim3(256), lds, (hipStream_t)stream, x, h, y,
+                           S, taps, Tw, tiles_t, (const int4*)tiles);
+        return (int)hipGetLastError();
+    });
 }
 
 // ---------------------------------------------------------------- reflection padding of rows, the twin of a3t_replicate_pad

@@ -190,22 +190,6 @@ __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
     }
 }
 
-template <bool RAGGED>
-static int pwg_launch(PwgArgs a, const float* wt0, const float* b0, const float* wt1, const float* b1, int ntiles, void* stream) {
-    constexpr int lds0 = (272 * 128 + 2 * 8 * 260) * 4, lds1 = (64 * 128 + 2 * 16 * 260) * 4;
-    hipError_t e = wave_lds_opt_in<pwg_stage_kernel<0, RAGGED>>(lds0);
-    if (e == hipSuccess) e = wave_lds_opt_in<pwg_stage_kernel<1, RAGGED>>(lds1);
-    if (e != hipSuccess) return (int)e;
-    const int cus = device_cus();
-    a.wt = wt0, a.bias = b0;
-    int g0 = ntiles < cus ? ntiles : cus;                 // stage 0: 153 KiB of LDS -> one persistent workgroup per CU
-    hipLaunchKernelGGL((pwg_stage_kernel<0, RAGGED>), dim3(g0), dim3(512), lds0, (hipStream_t)stream, a);
-    a.wt = wt1, a.bias = b1;
-    int g1 = ntiles < cus ? ntiles : cus;                 // stage 1: ~200 VGPRs x 8 waves -> one per CU as well
-    hipLaunchKernelGGL((pwg_stage_kernel<1, RAGGED>), dim3(g1), dim3(512), lds1, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
 // Both entry points: tiles == nullptr is the dense form, all B rows Tw samples long.
 static int pwg_block(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1, float* g,
                      float* skips, const int32_t* tiles, int ntiles, int B, int Tw, int dil, void* stream) {
@@ -216,7 +200,20 @@ static int pwg_block(float* x, const float* cu, const float* wt0, const float* b
     a.x_in = x, a.cu = cu, a.gin = g, a.g = g, a.x_out = x, a.skips = skips;
     a.B = B, a.Tw = Tw, a.dil = dil, a.tiles_t = wave_tiles_t(Tw);
     a.tiles = (const int4*)tiles, a.ntiles = ntiles;
-    return tiles ? pwg_launch<true>(a, wt0, b0, wt1, b1, n, stream) : pwg_launch<false>(a, wt0, b0, wt1, b1, n, stream);
+    return wave_ragged(tiles, [&](auto ragged) {
+        constexpr auto stage0 = pwg_stage_kernel<0, decltype(ragged)::value>, stage1 = pwg_stage_kernel<1, decltype(ragged)::value>;
+        constexpr int lds0 = (272 * 128 + 2 * 8 * 260) * 4, lds1 = (64 * 128 + 2 * 16 * 260) * 4;
+        hipError_t e = wave_lds_opt_in<stage0>(lds0);
+        if (e == hipSuccess) e = wave_lds_opt_in<stage1>(lds1);
+        if (e != hipSuccess) return (int)e;
+        // stage 0: 153 KiB of LDS -> one persistent workgroup per CU; stage 1: ~200 VGPRs x 8 waves -> one per CU as well
+        const int cus = device_cus(), grid = n < cus ? n : cus;
+        a.wt = wt0, a.bias = b0;
+        hipLaunchKernelGGL(stage0, dim3(grid), dim3(512), lds0, (hipStream_t)stream, a);
+        a.wt = wt1, a.bias = b1;
+        hipLaunchKernelGGL(stage1, dim3(grid), dim3(512), lds1, (hipStream_t)stream, a);
+        return (int)hipGetLastError();
+    });
 }
 
 // One residual block, in place on x and skips.  wt0: [272][128] (k = tap*64 + ch | 192 + aux ch; column n' = permuted

@@ -35,8 +35,6 @@
 #include "device_cus.h"
 #include "wave_tiles.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 struct PwgF16Args {
     const float* x_in;       // [B*Tw][64]
     float* x_out;            // [B*Tw][64], != x_in
@@ -49,16 +47,6 @@ struct PwgF16Args {
     const int4* tiles;       // RAGGED: [ntiles] tile list (wave_tiles.h)
     int ntiles, B, Tw, dil, tiles_t;
 };
-
-__device__ __forceinline__ float sat16(float v) { return fminf(fmaxf(v, -65504.f), 65504.f); }
-
-// h() of eight consecutive values
-__device__ __forceinline__ f16x8 pack_f16_sat(float4 v0, float4 v1) {
-    f16x8 q;
-    q[0] = (_Float16)sat16(v0.x), q[1] = (_Float16)sat16(v0.y), q[2] = (_Float16)sat16(v0.z), q[3] = (_Float16)sat16(v0.w);
-    q[4] = (_Float16)sat16(v1.x), q[5] = (_Float16)sat16(v1.y), q[6] = (_Float16)sat16(v1.z), q[7] = (_Float16)sat16(v1.w);
-    return q;
-}
 
 // channel of output row i (0..31) of M-tile mt (0..1) of the second product
 __device__ __forceinline__ int out_channel(int mt, int i) {
@@ -203,16 +191,6 @@ __global__ __launch_bounds__(512) void pwg_f16_kernel(PwgF16Args a) {
     }
 }
 
-template <bool RAGGED>
-static int pwg_f16_launch(const PwgF16Args& a, int ntiles, void* stream) {
-    constexpr int lds = (4 * 17 + 4 * 4) * 64 * 16 + 256 * 4;      // 87 040 B
-    const hipError_t e = wave_lds_opt_in<pwg_f16_kernel<RAGGED>>(lds);
-    if (e != hipSuccess) return (int)e;
-    const int cus = device_cus();
-    hipLaunchKernelGGL((pwg_f16_kernel<RAGGED>), dim3(ntiles < cus ? ntiles : cus), dim3(512), lds, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
 // One residual block on the 16-bit MFMA.  x_in -> x_out (two different buffers: the caller swaps them per layer), skips updated
 // in place.  cu16 [B*Tw][80] fp16 (a3t_cast_f16_sat of the upsampled mel); w0h [272][128] fp16, rows and columns as wt0 of
 // a3t_pwg_block; w1h [64][128] fp16 = conv1x1_out.weight^T; b0 / b1 fp32 as there.  tiles: the contract of wave_tiles.h.
@@ -232,7 +210,15 @@ extern "C" int a3t_pwg_block_f16(const float* x_in, float* x_out, const void* cu
     a.w1 = (const _Float16*)w1h, a.b1 = b1, a.skips = skips;
     a.B = B, a.Tw = Tw, a.dil = dil, a.tiles_t = wave_tiles_t(Tw);
     a.tiles = (const int4*)tiles, a.ntiles = ntiles;
-    return tiles ? pwg_f16_launch<true>(a, n, stream) : pwg_f16_launch<false>(a, n, stream);
+    return wave_ragged(tiles, [&](auto ragged) {
+        constexpr auto kernel = pwg_f16_kernel<decltype(ragged)::value>;
+        constexpr int lds = (4 * 17 + 4 * 4) * 64 * 16 + 256 * 4;      // 87 040 B
+        const hipError_t e = wave_lds_opt_in<kernel>(lds);
+        if (e != hipSuccess) return (int)e;
+        const int cus = device_cus();
+        hipLaunchKernelGGL(kernel, dim3(n < cus ? n : cus), dim3(512), lds, (hipStream_t)stream, a);
+        return (int)hipGetLastError();
+    });
 }
 
 __global__ void cast_f16_sat_kernel(const float* __restrict__ src, _Float16* __restrict__ dst, int64_t n) {

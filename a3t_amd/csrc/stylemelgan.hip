@@ -10,10 +10,10 @@
 //   a3t_smg_stats   mean and rstd = 1 / sqrt(var + eps) of every (row, channel) over the row's own W_b samples (InstanceNorm1d:
 //                   biased variance), C = 64.
 //
-// a3t_smg_conv has the structure of hfg_conv_kernel (hifigan.hip): an implicit-im2col GEMM on v_mfma_f32_32x32x2f32, one
-// 256-sample tile and all Cout columns per workgroup, K = taps * Cin tap-major in chunks of 16, activations and weights
-// double-buffered in LDS: 2 x (16 x 260 + 16 x 128) floats = 48.5 KiB at Cout = 128, 128 accumulator registers per wave; two
-// workgroups share a CU (186 registers, no scratch; three at Cout = 64).
+// a3t_smg_conv is the implicit-im2col GEMM of wave_conv.h (wave_conv_mainloop), as hfg_conv_kernel (hifigan.hip): one
+// 256-sample tile and all Cout columns per workgroup, K = taps * Cin tap-major in chunks of 16, the activations staged as they
+// are.  48.5 KiB of LDS at Cout = 128, 128 accumulator registers per wave; two workgroups share a CU (186 registers, no
+// scratch; three at Cout = 64).
 // Nearest-neighbour upsampling is an index map: the input holds ceil(Tw / up) rows per batch row and a tap at ts in [0, W_b)
 // reads row ts / up; m and R likewise with ux and ur.  Samples sit on the accumulator's rows and channels on its 32 columns =
 // the 32 lanes of a half wave, so column c (block j) and column 64 + c (block j + 2) are registers of the same lane -- the two
@@ -28,7 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/a3t_hip.h"
-#include "wave_tiles.h"
+#include "wave_conv.h"
 
 enum { SMG_PLAIN = 0, SMG_TADE = 1, SMG_GATE = 2 };
 
@@ -57,77 +57,23 @@ __device__ __forceinline__ float half_sum(float v) {
 
 template <int N, int MODE, bool RAGGED>
 __global__ __launch_bounds__(256, 2) void smg_conv_kernel(SmgArgs a) {
-    // 4 waves, each 64 samples x N channels: 2 x N/32 accumulator blocks
-    constexpr int BK = 16, TILE = 256, LD = TILE + 4, NJ = N / 32, WV = BK * N / 4 / 256;   // WV: weight float4 per thread
-    __shared__ __attribute__((aligned(16))) float As[2][BK][LD];
-    __shared__ __attribute__((aligned(16))) float Ws[2][BK * N];
-
+    constexpr int NJ = N / 32;
     const int tid = threadIdx.x, lane = tid & 63, wm = (tid >> 6) * 64, lr = lane & 31, lk = lane >> 5;
     const WaveTile at = wave_tile<RAGGED>(a.tiles, blockIdx.x, a.tiles_t, a.Tw);
     const int b = at.b, t0 = at.t0, Wb = at.Wb;
-    const int Cin = a.Cin, CPT = Cin / BK, nch = a.taps * CPT, half = (a.taps - 1) / 2;
+    const int Cin = a.Cin, CPT = Cin / 16, half = (a.taps - 1) / 2;      // CPT: chunks per tap
     const int t = t0 + tid;                                  // the row this thread stages
     const float* xb = a.x + (int64_t)b * ((a.Tw + a.up - 1) / a.up) * Cin;
 
-    float4 P[4], Q0, Q1;
-    auto load_chunk = [&](int kc) {
-        const int tap = kc / CPT, c0 = (kc - tap * CPT) * BK;
-        const int64_t ts = (int64_t)t + (int64_t)(tap - half) * a.dil;
-        if (t < Wb && ts >= 0 && ts < Wb) {
-            const float4* s = (const float4*)(xb + (ts / a.up) * Cin + c0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) P[i] = s[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) P[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        const float4* wsrc = (const float4*)(a.wt + (int64_t)kc * BK * N);
-        Q0 = wsrc[tid];
-        if constexpr (WV == 2) Q1 = wsrc[tid + 256];
-    };
-    auto store_chunk = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            As[buf][4 * i + 0][tid] = P[i].x;
-            As[buf][4 * i + 1][tid] = P[i].y;
-            As[buf][4 * i + 2][tid] = P[i].z;
-            As[buf][4 * i + 3][tid] = P[i].w;
-        }
-        ((float4*)Ws[buf])[tid] = Q0;
-        if constexpr (WV == 2) ((float4*)Ws[buf])[tid + 256] = Q1;
-    };
-
     f32x16 acc[2][NJ];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    load_chunk(0);
-    store_chunk(0);
-    __syncthreads();
-    int buf = 0;
-    for (int kc = 0; kc < nch; ++kc) {
-        const bool more = kc + 1 < nch;
-        load_chunk(more ? kc + 1 : kc);      // (unconditional: conditionally written prefetch registers go to scratch)
-#pragma unroll
-        for (int kk = 0; kk < BK / 2; ++kk) {
-            const int k = kk * 2 + lk;
-            const float a0 = As[buf][k][wm + lr], a1 = As[buf][k][wm + 32 + lr];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const float bj = Ws[buf][k * N + j * 32 + lr];
-                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bj, acc[0][j], 0, 0, 0);
-                acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bj, acc[1][j], 0, 0, 0);
-            }
-        }
-        // the other buffer was last read before the barrier that ended the previous chunk
-        if (more) store_chunk(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
+    wave_conv_mainloop<N>(
+        acc, a.wt, a.taps * CPT,
+        [&](int kc) -> const float4* {
+            const int tap = kc / CPT, c0 = (kc - tap * CPT) * 16;
+            const int64_t ts = (int64_t)t + (int64_t)(tap - half) * a.dil;
+            return t < Wb && ts >= 0 && ts < Wb ? (const float4*)(xb + (ts / a.up) * Cin + c0) : nullptr;
+        },
+        [](float v) { return v; });
 
     float bj[NJ];
 #pragma unroll
@@ -192,11 +138,10 @@ __global__ __launch_bounds__(256, 2) void smg_conv_kernel(SmgArgs a) {
 
 template <int N, int MODE>
 static int smg_conv_launch(const SmgArgs& a, int ntiles, void* stream) {
-    if (a.tiles)
-        hipLaunchKernelGGL((smg_conv_kernel<N, MODE, true>), dim3(ntiles), dim3(256), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((smg_conv_kernel<N, MODE, false>), dim3(ntiles), dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    return wave_ragged(a.tiles, [&](auto ragged) {
+        hipLaunchKernelGGL((smg_conv_kernel<N, MODE, decltype(ragged)::value>), dim3(ntiles), dim3(256), 0, (hipStream_t)stream, a);
+        return (int)hipGetLastError();
+    });
 }
 
 extern "C" int a3t_smg_conv(const float* x, const float* wt, const float* bias, const float* m, const float* stats,
@@ -241,10 +186,13 @@ __global__ __launch_bounds__(256) void smg_stats_tile_kernel(const float* __rest
     __syncthreads();
     const float mean = (((red[0][c] + red[1][c]) + red[2][c]) + red[3][c]) / (float)n;
     __syncthreads();
+    // (the valid rows counted, not "q + 4 i < n" again: the compiler keeps the first loop's 64 lane masks for a second use and
+    // spills SGPRs)
+    const int cnt = (n - q + 3) >> 2;
     float m2 = 0.f;
 #pragma unroll
     for (int i = 0; i < 64; ++i) {
-        const float d = q + 4 * i < n ? v[i] - mean : 0.f;
+        const float d = i < cnt ? v[i] - mean : 0.f;
         m2 += d * d;
     }
     red[q][c] = m2;
@@ -306,16 +254,13 @@ extern "C" int a3t_smg_stats(const float* x, float* part, float* stats, float ep
     const int n = wave_grid(tiles, ntiles, B, Tw);
     if (n < 0) return n;
     const int tiles_t = wave_tiles_t(Tw);
-    if (tiles && n) {
-        hipLaunchKernelGGL(smg_stats_tile_kernel<true>, dim3(n), dim3(256), 0, (hipStream_t)stream, x, part, Tw, tiles_t,
-                           (const int4*)tiles);
-        hipLaunchKernelGGL(smg_stats_merge_kernel<true>, dim3(B), dim3(1024), 0, (hipStream_t)stream, part, stats, Tw, tiles_t,
-                           (const int4*)tiles, n, eps);
-    } else if (n) {
-        hipLaunchKernelGGL(smg_stats_tile_kernel<false>, dim3(n), dim3(256), 0, (hipStream_t)stream, x, part, Tw, tiles_t,
-                           (const int4*)nullptr);
-        hipLaunchKernelGGL(smg_stats_merge_kernel<false>, dim3(B), dim3(1024), 0, (hipStream_t)stream, part, stats, Tw, tiles_t,
-                           (const int4*)nullptr, n, eps);
-    }
+    if (n)
+        wave_ragged(tiles, [&](auto ragged) {
+            constexpr bool R = decltype(ragged)::value;
+            hipLaunchKernelGGL(smg_stats_tile_kernel<R>, dim3(n), dim3(256), 0, (hipStream_t)stream, x, part, Tw, tiles_t,
+                               (const int4*)tiles);
+            hipLaunchKernelGGL(smg_stats_merge_kernel<R>, dim3(B), dim3(1024), 0, (hipStream_t)stream, part, stats, Tw, tiles_t,
+                               (const int4*)tiles, n, eps);
+        });
     return (int)hipGetLastError();
 }

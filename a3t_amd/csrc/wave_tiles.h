@@ -1,5 +1,6 @@
 // wave_tiles.h -- the tile contract of the waveform kernels (pwg_fused.hip, pwg_fused_f16.hip, hifigan.hip,
-// hifigan_f16.hip, melgan.hip, stylemelgan.hip), device and host side.
+// hifigan_f16.hip, melgan.hip, stylemelgan.hip; wave_conv.h: the fp32 convolution loop and the output convolution that the
+// last three share), device and host side, and the small functions that more than one of them uses.
 //
 // A [B][Tw] batch of samples is cut into tiles of 256.  Dense form (tiles == NULL): the grid is all B * ceil(Tw / 256) tiles and
 // every row is Tw samples long.  Ragged form: the grid is a host-built device list, int32 [ntiles][4] = {row b, first sample t0
@@ -10,9 +11,11 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/a3t_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct WaveTile { int b, t0, Wb; };      // row, first sample, valid samples of the row
 
@@ -39,6 +42,20 @@ __device__ __forceinline__ float pwg_gate(float ya, float yb) {
     return th * __frcp_rn(1.f + __expf(-yb));
 }
 
+__device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
+__device__ __forceinline__ float4 leaky(float4 v, float slope) {
+    return make_float4(leaky(v.x, slope), leaky(v.y, slope), leaky(v.z, slope), leaky(v.w, slope));
+}
+
+// h() = round to nearest even to fp16, saturated to +-65504, of eight consecutive values
+__device__ __forceinline__ float sat16(float v) { return fminf(fmaxf(v, -65504.f), 65504.f); }
+__device__ __forceinline__ f16x8 pack_f16_sat(float4 v0, float4 v1) {
+    f16x8 q;
+    q[0] = (_Float16)sat16(v0.x), q[1] = (_Float16)sat16(v0.y), q[2] = (_Float16)sat16(v0.z), q[3] = (_Float16)sat16(v0.w);
+    q[4] = (_Float16)sat16(v1.x), q[5] = (_Float16)sat16(v1.y), q[6] = (_Float16)sat16(v1.z), q[7] = (_Float16)sat16(v1.w);
+    return q;
+}
+
 inline int wave_tiles_t(int Tw) { return (int)(((int64_t)Tw + 255) / 256); }
 
 // The grid of an entry point: A3T_EINVAL (< 0) for arguments outside the contract, 0 for an empty list (nothing to launch,
@@ -49,6 +66,11 @@ inline int wave_grid(const int32_t* tiles, int ntiles, int B, int Tw) {
     const int64_t n = (int64_t)B * wave_tiles_t(Tw);
     return n > INT_MAX ? A3T_EINVAL : (int)n;
 }
+
+// The dense / ragged choice of an entry point: f(std::true_type) with a tile list, f(std::false_type) without, for a generic
+// lambda that launches kernel<..., decltype(ragged)::value>.
+template <typename F>
+inline auto wave_ragged(const void* tiles, F&& f) { return tiles ? f(std::true_type{}) : f(std::false_type{}); }
 
 // Dynamic LDS beyond 64 KiB has to be granted per kernel and per device.  Cached like device_cus(): the largest size granted
 // to KERNEL so far on each device (a kernel's size may depend on its arguments); the HIP status of a refusal is the caller's

@@ -184,6 +184,36 @@ def test_hfg_out(C, K, slope):
     assert torch.equal(xd, keep)
 
 
+def test_hfg_out_row_shorter_than_its_halo():
+    """A row of 2 samples under K = 7 (halo 3): every tap beyond the row is ZERO padding.  The kernel is shared with
+    a3t_mgan_out, whose taps reflect at the row's ends; on this row the two paddings differ at every sample."""
+    from a3t_amd import ops
+    C, K, slope, Bs, Ts, Ws = 32, 7, 0.1, 2, 300, (300, 2)
+    g = torch.Generator().manual_seed(C + K + Ts)
+    x = torch.randn(Bs, Ts, C, generator=g)
+    w = torch.randn(1, C, K, generator=g) / (C * K) ** 0.5
+    bias = torch.randn(1, generator=g) * 0.1
+
+    def run(xr, dt):
+        return torch.tanh(F.conv1d(_leaky(xr.to(dt), slope).t()[None], w.to(dt), bias.to(dt), padding=(K - 1) // 2))[0].t()
+
+    xd = x.to(DEV).view(Bs * Ts, C)
+    wk, bd = w[0].t().contiguous().to(DEV), bias.to(DEV)                # [K][C]
+    for ragged in (False, True):
+        ref = []
+        for dt in (torch.float64, torch.float32):
+            v = torch.stack([run(x[b], dt) for b in range(Bs)])
+            if ragged:
+                v[1, :Ws[1]] = run(x[1, :Ws[1]], dt)
+                v[1, Ws[1]:] = SENTINEL
+            ref.append(v)
+        y = torch.full((Bs * Ts,), SENTINEL, device=DEV)
+        ops.hfg_out(xd, wk, bd, y, Bs, Ts, slope, tiles=_tiles(Ws) if ragged else None)
+        _check(f"hfg_out short row {'ragged' if ragged else 'dense'}", y.view(Bs, Ts, 1), ref[0], ref[1], 1.0)
+        if ragged:
+            assert bool((y.view(Bs, Ts)[1, Ws[1]:] == SENTINEL).all())
+
+
 @pytest.mark.parametrize("slope", [0.1, 0.01])
 def test_leaky_relu(slope):
     """Exact: one fp32 multiplication.  A length that is no multiple of 4 (the 16-byte body and its tail), an unaligned view

@@ -190,6 +190,39 @@ def test_gemm_register_budget():
         assert r["VGPRs Spill"] == 0 and r["SGPRs Spill"] <= 24, (name, r)
 
 
+def test_wave_kernel_register_budget():
+    """The waveform kernels share their loops through headers (wave_conv.h, wave_tiles.h), so one edit there moves the
+    registers of several kernels at once.  Every kernel of the six sources: no scratch, no spills; and the MFMA kernels and
+    the output convolution keep at least the occupancy (waves / SIMD) they were measured with -- the figures of the commit
+    that introduced wave_conv.h, the same for the dense and the ragged instantiation."""
+    import json
+    import re
+    from a3t_amd import build
+    floors = {"hfg_conv_kernel": {32: 4, 64: 2}, "hfg_conv_f16_kernel": {32: 5, 64: 4, 128: 3, 256: 2},
+              "smg_conv_kernel": {64: 3, 128: 2}, "mgan_stack_kernel": {48: 3, 96: 2, 192: 1},
+              "pwg_stage_kernel": {0: 2, 1: 2}, "pwg_f16_kernel": 2, "wave_out_kernel": 6}
+    libdir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "a3t_amd", "lib")
+    paths = [os.path.join(libdir, s.replace(".hip", ".resources.json")) for s in build.WAVE_SOURCES]
+    assert len(paths) == 6
+    if not all(os.path.exists(p) for p in paths):
+        pytest.skip("library not built by a3t_amd.build in this tree")
+    seen = dict.fromkeys(floors, 0)
+    for path in paths:
+        rows = json.load(open(path))
+        assert rows, path
+        for name, r in rows.items():
+            assert r["ScratchSize [bytes/lane]"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, (name, r)
+            m = re.search(r"\d(%s)I(?:Li(\d+)E)?" % "|".join(floors), name)
+            if not m:
+                continue
+            floor = floors[m.group(1)]
+            seen[m.group(1)] += 1
+            assert r["Occupancy [waves/SIMD]"] >= (floor if isinstance(floor, int) else floor[int(m.group(2))]), (name, r)
+    # dense and ragged of every instantiation; smg_conv: PLAIN at 64, TADE and GATE at 128; wave_out: a3t_hfg_out, a3t_mgan_out
+    assert seen == {"hfg_conv_kernel": 4, "hfg_conv_f16_kernel": 8, "smg_conv_kernel": 6, "mgan_stack_kernel": 6,
+                    "pwg_stage_kernel": 4, "pwg_f16_kernel": 2, "wave_out_kernel": 4}, seen
+
+
 def test_sedit_driver_span_arithmetic_matches_reference():
     """a3t_amd.sedit (the product's mirror of espnet2/bin/sedit_inference.py's host logic) against the reference
     driver's own outputs (tests/golden/sedit.json, 40 edits) -- the same checker the oracle is held to -- and against
