@@ -535,6 +535,8 @@ static int gemm_plan(const a3t_gemm_desc* d, GP* gp, GemmPlan* pl) {
     if (p.accumulate == A3T_ACC_SOLE) p.accumulate = A3T_ACC_ATOMIC, p.sole_writer = 1;
     p.splitk = d->splitk < 1 ? 1 : d->splitk;
     if (p.splitk > 1 && p.accumulate != A3T_ACC_ATOMIC) return A3T_EINVAL;
+    // every split runs the epilogue on its partial sum: only its linear terms (mask, dropout, alpha) commute with the split
+    if (p.splitk > 1 && p.act != A3T_ACT_NONE) return A3T_EINVAL;
     p.c_dtype = d->c_dtype;
     p.s_dtype = d->s_dtype;
     p.colsum = d->colsum, p.colsum_bs1 = d->colsum_bs1, p.colsum_scale = d->colsum_scale;

@@ -94,7 +94,9 @@ class LogMelFbank:
         if lengths is None:
             lengths = torch.full((B,), N, dtype=torch.long)
         pad = self.n_fft // 2
-        F = 1 + N // self.hop_length
+        # frames of the centred STFT (stft.py:56-124): the padded row holds N + 2*pad samples; for odd n_fft that is one short
+        # of N + n_fft, so 1 + N // hop would read a last frame one sample past the row whenever hop divides N
+        F = 1 + (N + 2 * pad - self.n_fft) // self.hop_length
         row = (N + 2 * pad + 3) // 4 * 4
         xp = torch.empty(B, row, device=dev)
         ops.reflect_pad(x, xp, pad)

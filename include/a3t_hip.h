@@ -60,7 +60,8 @@ extern "C" {
  *          (k % Tseq) + kshift is outside [0,Tseq)   (Conv1d weight gradient, one tap per launch)
  * One of a_rs/a_cs (and of b_rs/b_cs) must be 1.
  * Batching: z in [0,batch): z0 = z / batch_inner, z1 = z % batch_inner; X += z0*x_bs0 + z1*x_bs1.
- * splitk>1 splits K over extra workgroups; requires accumulate == A3T_ACC_ATOMIC or A3T_ACC_SOLE.
+ * splitk>1 splits K over extra workgroups; requires accumulate == A3T_ACC_ATOMIC or A3T_ACC_SOLE and
+ * act == A3T_ACT_NONE (each split runs the epilogue on its partial sum; bias and R are added by the first split alone).
  * ZERO-INITIALISE the descriptor (`a3t_gemm_desc d = {0};`): optional fields are appended as the library grows (round 6: a_signmask,
  * keep_layout, A2 .. a_unaligned) and zero / NULL always means "off".
  */
