@@ -134,7 +134,8 @@ static int glu_dwconv_fwd_launch(const void* g, int g_dtype, const float* wdw, c
 
 extern "C" int a3t_glu_dwconv_fwd(const void* g, int g_dtype, const float* wdw, const float* bdw, void* glu,
                                   int glu_dtype, float* z, int M, int C, int K, int Tseq, void* stream) {
-    if (K > DW_KMAX || (K & 1) == 0 || Tseq <= 0 || M % Tseq) return A3T_EINVAL;
+    if (K > DW_KMAX || K <= 0 || (K & 1) == 0 || Tseq <= 0 || M <= 0 || C <= 0 || M % Tseq) return A3T_EINVAL;
+    if ((int64_t)(M / Tseq) * ((Tseq + DW_TT - 1) / DW_TT) > 65535) return A3T_EINVAL;      // grid.y (both kernels)
     if (g_dtype == A3T_BF16 && glu_dtype == A3T_BF16 && C % 64 == 0 && dw_al16(g) && dw_al16(glu) && dw_al16(z))
         return a3t_glu_dwconv_fwd_vec(g, wdw, bdw, glu, z, M, C, K, Tseq, (hipStream_t)stream);
     return glu_dwconv_fwd_launch<false>(g, g_dtype, wdw, bdw, glu, glu_dtype, z, M / Tseq, C, K, Tseq, nullptr,
@@ -311,7 +312,7 @@ __global__ __launch_bounds__(256, 3) void glu_dwconv_bwd_kernel(const float* __r
 extern "C" int a3t_glu_dwconv_bwd(const float* dz, const void* g, int g_dtype, const void* glu, int glu_dtype,
                                   const float* wdw, void* dg, int dg_dtype, float* dwdw, float* dbdw, float* dg_colsum,
                                   int M, int C, int K, int Tseq, void* stream) {
-    if (K > DW_KMAX || (K & 1) == 0 || Tseq <= 0 || M % Tseq) return A3T_EINVAL;
+    if (K > DW_KMAX || K <= 0 || (K & 1) == 0 || Tseq <= 0 || M <= 0 || C <= 0 || M % Tseq) return A3T_EINVAL;
     if (g_dtype == A3T_BF16 && glu_dtype == A3T_BF16 && dg_dtype == A3T_BF16 && C % 64 == 0 && dw_al16(g) &&
         dw_al16(glu) && dw_al16(dg) && dw_al16(dz))
         return a3t_glu_dwconv_bwd_vec(dz, g, glu, wdw, dg, dwdw, dbdw, dg_colsum, M, C, K, Tseq, (hipStream_t)stream);
@@ -322,6 +323,7 @@ extern "C" int a3t_glu_dwconv_bwd(const float* dz, const void* g, int g_dtype, c
     while (cb * B * chunks < 1024 && chunks < tiles_t) ++chunks;
     int tpb = (tiles_t + chunks - 1) / chunks;
     chunks = (tiles_t + tpb - 1) / tpb;
+    if ((int64_t)B * chunks > 65535) return A3T_EINVAL;      // grid.y
     dim3 grid(cb, B * chunks);
 #define DWB(KT)                                                                                                       \
     hipLaunchKernelGGL(glu_dwconv_bwd_kernel<KT>, grid, dim3(256), 0, (hipStream_t)stream, dz, g, g_dtype, glu, glu_dtype, \

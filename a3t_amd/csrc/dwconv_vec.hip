@@ -314,6 +314,7 @@ int a3t_glu_dwconv_bwd_vec(const float* dz, const void* g, const void* glu, cons
     while (cb * B * chunks < 640 && chunks < tiles_t) ++chunks;
     const int tpb = (tiles_t + chunks - 1) / chunks;
     chunks = (tiles_t + tpb - 1) / tpb;
+    if ((int64_t)B * chunks > 65535) return A3T_EINVAL;      // grid.y
     dim3 grid(cb, B * chunks);
 #define DWB(KT)                                                                                                       \
     hipLaunchKernelGGL(glu_dwconv_bwd_vec_kernel<KT>, grid, dim3(256), 0, stream, dz, (const u16*)g, (const u16*)glu, \

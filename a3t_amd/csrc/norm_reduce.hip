@@ -474,6 +474,7 @@ __global__ __launch_bounds__(256) void col_reduce_vec_kernel(const float* __rest
 extern "C" int a3t_col_reduce(const void* x, int x_dtype, const float* y, const uint8_t* rowmask, double* out0,
                               double* out1, int M, int C, int64_t ld, int mode, void* stream) {
     if (M <= 0 || C <= 0) return A3T_EINVAL;
+    if (((int64_t)M + 255) / 256 > 65535) return A3T_EINVAL;      // grid.y
     int rpb = 256;
     dim3 grid((C + 63) / 64, (M + rpb - 1) / rpb);
     if (x_dtype == A3T_F32 && !rowmask && C % 64 == 0 && ld % 4 == 0 && ((uintptr_t)x % 16 == 0) &&
@@ -673,6 +674,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_a_vec_kernel(const float* __re
 extern "C" int a3t_bn_act_bwd_a(const void* dy, int dy_dtype, const float* z, const float* mean, const float* rstd,
                                 const float* gamma, const float* beta, double* sums, int M, int C, int act,
                                 void* stream) {
+    if (M <= 0 || C <= 0 || ((int64_t)M + 255) / 256 > 65535) return A3T_EINVAL;      // grid.y
     int rpb = 256;
     dim3 grid((C + 63) / 64, (M + rpb - 1) / rpb);
     if (dy_dtype == A3T_F32 && C % 64 == 0 && ((uintptr_t)dy % 16 == 0) && ((uintptr_t)z % 16 == 0) &&

@@ -173,7 +173,8 @@ int a3t_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float*
  *   mode 0: out0[c] += sum x            (bias gradients)
  *   mode 1: out0 += sum x, out1 += sum x*x      (BatchNorm batch statistics)
  *   mode 2: out0 += sum x, out1 += sum x*y      (BatchNorm backward)
- * rowmask (optional, uint8 [M]): only rows with rowmask!=0 contribute. out are double[C]. */
+ * rowmask (optional, uint8 [M]): only rows with rowmask!=0 contribute. out are double[C].
+ * A3T_EINVAL beyond 65535 blocks of 256 rows (the grid's y extent); a3t_bn_act_bwd_a shares the limit. */
 int a3t_col_reduce(const void* x, int x_dtype, const float* y, const uint8_t* rowmask, double* out0,
                    double* out1, int M, int C, int64_t ld, int mode, void* stream);
 int a3t_f64_to_f32_add(const double* src, float* dst, int n, float scale, void* stream);
@@ -195,7 +196,9 @@ int a3t_bn_act_bwd_b(const void* dy, int dy_dtype, const float* z, const float* 
                      float* dbeta, int M, int C, int training, int act, void* stream);
 
 /* GLU + depthwise Conv1d (conformer/convolution.py:66-72): g[M][2C] -> glu[M][C] (saved) and
- * z[m][c] = bdw[c] + sum_k wdw[c][k] * glu[m+k-(K-1)/2][c], zero padded per utterance (Tseq). */
+ * z[m][c] = bdw[c] + sum_k wdw[c][k] * glu[m+k-(K-1)/2][c], zero padded per utterance (Tseq).
+ * A3T_EINVAL: K even, K > 31, M % Tseq != 0, or more than 65535 (utterance, 64-frame tile) pairs (the grid's y extent);
+ * the backward refuses the same once its (utterance, tile chunk) pairs pass 65535. */
 int a3t_glu_dwconv_fwd(const void* g, int g_dtype, const float* wdw, const float* bdw, void* glu,
                        int glu_dtype, float* z, int M, int C, int K, int Tseq, void* stream);
 /* dz -> dg[M][2C]; dwdw[C][K], dbdw[C] accumulated (atomics) */
