@@ -80,11 +80,13 @@ _SIGS = {
     "a3t_scale_dev": [_P, _P, c_int64, _P, _P],
     "a3t_slice_rows": [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "a3t_concat_rows": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
+    "a3t_concat_rows_ragged": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P],
     "a3t_split_rows": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_cast_bf16": [_P, _P, c_int64, _P],
     "a3t_cast_bf16_conv_t": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_split_bf16": [_P, _P, _P, c_int64, _P],
     "a3t_reflect_pad": [_P, _P, c_int, c_int, c_int, c_int, _P],
+    "a3t_reflect_pad_ragged": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_stft_amp": [_P, _P, c_int64, c_int, c_int, _P],
     "a3t_logmel_finish": [_P, _P, c_int, c_int, c_int, _P],
     "a3t_mlm_loss": [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P],

@@ -34,6 +34,33 @@ extern "C" int a3t_reflect_pad(const float* x, float* out, int B, int N, int pad
     return (int)hipGetLastError();
 }
 
+// The same with a length per row (device int32 lens[B]): row b is reflected about its OWN ends, sample 0 and sample lens[b] - 1,
+// and everything behind pad + lens[b] + pad is 0 -- what reflect_pad gives for x[b][0:lens[b]] passed alone, so the frames of the
+// STFT that lie inside a row's own extent do not see the batch's padding.  The host checks pad < lens[b] <= N (it has the lengths);
+// a row that breaks it anyway is stored as zeros, nothing is read out of bounds.
+__global__ void reflect_pad_ragged_kernel(const float* __restrict__ x, float* __restrict__ out, const int32_t* __restrict__ lens,
+                                          int B, int N, int pad, int ld) {
+    const int64_t n = (int64_t)B * ld;
+    GS(i, n) {
+        int b = (int)(i / ld), j = (int)(i - (int64_t)b * ld);
+        const int nb = lens[b];
+        float v = 0.f;
+        if (nb > pad && nb <= N && j < nb + 2 * pad) {
+            int s = j - pad;
+            if (s < 0) s = -s;
+            if (s >= nb) s = 2 * (nb - 1) - s;
+            v = x[(int64_t)b * N + s];
+        }
+        out[i] = v;
+    }
+}
+extern "C" int a3t_reflect_pad_ragged(const float* x, float* out, const int32_t* lens, int B, int N, int pad, int ld, void* stream) {
+    if (B <= 0 || pad < 0 || pad >= N || ld < N + 2 * pad || !lens) return A3T_EINVAL;
+    int64_t n = (int64_t)B * ld;
+    hipLaunchKernelGGL(reflect_pad_ragged_kernel, dim3(nb_(n)), dim3(256), 0, (hipStream_t)stream, x, out, lens, B, N, pad, ld);
+    return (int)hipGetLastError();
+}
+
 // S[row][0:nb] = re, S[row][nb:2nb] = im  ->  amp[row][f] = sqrt(max(re^2+im^2, 1e-10)); amp row stride ld
 // (columns nb..ld-1 zero so the mel GEMM can run on aligned K)
 __global__ void stft_amp_kernel(const float* __restrict__ S, float* __restrict__ amp, int64_t rows, int nb, int ld) {

@@ -262,7 +262,40 @@ extern "C" int a3t_concat_rows(const float* speech, const float* text, float* xs
                        (const float4*)text, (float4*)xs, B, Tm, Tp, D / 4);
     return (int)hipGetLastError();
 }
-// ... and its backward: the gradient of xs split into the two parts (plain stores, every element of both outputs is written)
+// The packed join of a ragged batch (forward only): row b of xs is speech[b][0:slens[b]], text[b][0:tlens[b]] directly behind it --
+// the sequence the row has when it is passed alone -- and zeros up to Tm + Tp.  speech_bs / text_bs: elements between the batch
+// rows of the two sources, 0 = one source for every row (the projected positional table).  Lengths are clamped to [0, Tm] / [0, Tp].
+__global__ void concat_rows_ragged_kernel(const float4* __restrict__ speech, const float4* __restrict__ text, float4* __restrict__ xs,
+                                          const int32_t* __restrict__ slens, const int32_t* __restrict__ tlens, int B, int Tm,
+                                          int Tp, int D4, int64_t speech_bs4, int64_t text_bs4) {
+    const int T = Tm + Tp;
+    const int64_t n = (int64_t)B * T * D4;
+    GRID_STRIDE(i, n) {
+        const int64_t row = i / D4;
+        const int c = (int)(i - row * D4);
+        const int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
+        int sl = slens[b], tl = tlens[b];
+        sl = sl < 0 ? 0 : (sl > Tm ? Tm : sl);
+        tl = tl < 0 ? 0 : (tl > Tp ? Tp : tl);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t < sl)
+            v = speech[b * speech_bs4 + (int64_t)t * D4 + c];
+        else if (t < sl + tl)
+            v = text[b * text_bs4 + (int64_t)(t - sl) * D4 + c];
+        xs[i] = v;
+    }
+}
+extern "C" int a3t_concat_rows_ragged(const float* speech, const float* text, float* xs, const int32_t* slens, const int32_t* tlens,
+                                      int B, int Tm, int Tp, int D, int64_t speech_bs, int64_t text_bs, void* stream) {
+    if (B <= 0 || Tm < 0 || Tp < 0 || Tm + Tp <= 0 || D <= 0 || D % 4 || !slens || !tlens) return A3T_EINVAL;
+    if (speech_bs < 0 || text_bs < 0 || speech_bs % 4 || text_bs % 4) return A3T_EINVAL;
+    if (((uintptr_t)xs & 15) || (Tm > 0 && ((uintptr_t)speech & 15)) || (Tp > 0 && ((uintptr_t)text & 15))) return A3T_EINVAL;
+    const int64_t n = (int64_t)B * (Tm + Tp) * (D / 4);
+    hipLaunchKernelGGL(concat_rows_ragged_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, (const float4*)speech,
+                       (const float4*)text, (float4*)xs, slens, tlens, B, Tm, Tp, D / 4, speech_bs / 4, text_bs / 4);
+    return (int)hipGetLastError();
+}
+// The backward of a3t_concat_rows: the gradient of xs split into the two parts (plain stores, every element of both outputs is written)
 __global__ void split_rows_kernel(const float4* __restrict__ dxs, float4* __restrict__ dspeech, float4* __restrict__ dtext,
                                   int B, int Tm, int Tp, int D4) {
     const int T = Tm + Tp;

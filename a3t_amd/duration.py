@@ -31,7 +31,7 @@ import torch
 from . import ops
 from ._lib import ACT_NONE, ACT_RELU, F32
 from .config import A3TConfig
-from .engine import MLMEngine, Workspace
+from .engine import MLMEngine, Workspace, score_chunks
 from .params import ParamStore, _block_layout, _ref_block_map
 
 # FastSpeech2.__init__ defaults (espnet2/tts/fastspeech2/fastspeech2.py) of the keys the duration path reads
@@ -585,16 +585,7 @@ class FS2DurationModel:
     def _chunks(self, lengths, max_score_elems):
         """Indices of `lengths` sorted by length and cut into consecutive chunks with B * H * Tmax^2 <= max_score_elems
         (Tmax = the chunk's longest = last row); a row too long for the cap runs alone."""
-        order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
-        H, out, cur = self.c.heads, [], []
-        for i in order:
-            if cur and (len(cur) + 1) * H * lengths[i] ** 2 > max_score_elems:
-                out.append(cur)
-                cur = []
-            cur.append(i)
-        if cur:
-            out.append(cur)
-        return out
+        return score_chunks(lengths, self.c.heads, max_score_elems)
 
     def predict_frames_batch(self, phn_lists, spk_bias=None, max_score_elems: int = 1 << 24, style=None,
                              style_rows=None) -> List[np.ndarray]:

@@ -125,6 +125,22 @@ def _new_event(owned=False):
 _FAST_EVENTS = True
 
 
+def score_chunks(lengths, heads, max_score_elems):
+    """Indices of `lengths` sorted by length and cut into consecutive chunks with B * heads * Tmax^2 <= max_score_elems (Tmax =
+    the chunk's longest = last row), the size of a score tensor of the materialised attention; a row too long for the cap runs
+    alone."""
+    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
+    out, cur = [], []
+    for i in order:
+        if cur and (len(cur) + 1) * heads * lengths[i] ** 2 > max_score_elems:
+            out.append(cur)
+            cur = []
+        cur.append(i)
+    if cur:
+        out.append(cur)
+    return out
+
+
 class Workspace:
     """Named device buffers, allocated on first use and reused every step (static shapes)."""
 
@@ -621,7 +637,7 @@ class MLMEngine:
         return g
 
     # ------------------------------------------------------------------ rel-pos self-attention
-    def _mha_fwd(self, tag, pre, x, pos, keymask, B, T, lens=None):
+    def _mha_fwd(self, tag, pre, x, pos, keymask, B, T, lens=None, pos_rows=None):
         p, c = self.store.p, self.c
         d, H, dk = c.adim, c.heads, c.dk
         M = B * T
@@ -636,6 +652,10 @@ class MLMEngine:
         # j < lens[b] and the legacy rel_shift taken at lens[b] (a3t_relpos_softmax_fwd_ragged).  P = linear_pos(pe[:T]) serves every
         # row: its first n rows are pe[:n] projected.  Query rows behind a row's length come out as 0 from the softmax, so the
         # probs @ V product and what follows stay finite there; no valid row reads them.
+        # pos_rows = (slens, tlens, Tm, Tp), with lens = slens + tlens (packed rows, forward(lens=)): row b's table is
+        # cat(pe[:sl_b], pe[:tl_b]), no prefix of one table.  linear_pos has no bias and works row by row, so
+        # pos = pe[:max(Tm, Tp)] is projected once and a3t_concat_rows_ragged gathers the projected rows per batch row; the
+        # position-score GEMM then reads a B operand of its own per row.
         ragged = lens is not None
         fused = (self._fused_now or self._fused_train_now) and ops.attn_fused_supported(dk, T) and not ragged
         pbias = (p[pre + ".u"], p[pre + ".v"])
@@ -650,6 +670,11 @@ class MLMEngine:
             if ev is not None:
                 ev.wait_on(torch.cuda.current_stream())
                 self._pos_ev[tag[:3]] = None
+        elif pos_rows is not None:
+            Pt = self._act(tag + ".Pt", (pos.shape[0], d))
+            ops.linear_fwd(pos, self.W(pre + ".wpos"), Pt, compute=cmp)
+            P = self._act(tag + ".Prow", (M, d))
+            ops.concat_rows_ragged(Pt, Pt, P, pos_rows[0], pos_rows[1], B, pos_rows[2], pos_rows[3], d, 0, 0)
         else:
             P = self._act(tag + ".P", (T, d))
             ops.linear_fwd(pos, self.W(pre + ".wpos"), P, compute=cmp)
@@ -700,8 +725,8 @@ class MLMEngine:
         # ac[b,h] = (q+u) k^T ; bd[b,h] = (q+v) P_h^T   (attention.py:190-203)
         ops.gemm(qu, kk, ac, T, T, dk, d, 1, 3 * d, 1, T, batch=B * H, batch_inner=H, a_bs=(T * d, dk),
                  b_bs=(T * 3 * d, dk), c_bs=(H * T * T, T * T), compute=cmp)
-        ops.gemm(qv, P, bd, T, T, dk, d, 1, d, 1, T, batch=B * H, batch_inner=H, a_bs=(T * d, dk), b_bs=(0, dk),
-                 c_bs=(H * T * T, T * T), compute=cmp)
+        ops.gemm(qv, P, bd, T, T, dk, d, 1, d, 1, T, batch=B * H, batch_inner=H, a_bs=(T * d, dk),
+                 b_bs=(T * d if pos_rows is not None else 0, dk), c_bs=(H * T * T, T * T), compute=cmp)
         probs = self._act(tag + ".probs", (B, H, T, T))
         adr = self._drop(c.attention_dropout_rate, tag + ".att")      # (None in eval mode, so with lens)
         pdrop = self._act(tag + ".pdrop", (B, H, T, T)) if adr else None
@@ -950,16 +975,16 @@ class MLMEngine:
         if lens.dtype != torch.int32 or lens.numel() != B or lens.device.type != self.dev.type:
             raise ValueError(f"lens must be an int32 tensor of {B} entries on {self.dev}")
 
-    def block_fwd(self, pre, x, pos, keymask, B, T, lens=None):
+    def block_fwd(self, pre, x, pos, keymask, B, T, lens=None, pos_rows=None):
         """lens (device int32 [B]): the rows of the padded [B][T] batch have their own lengths and row b comes out as if it had
         been passed alone at lens[b]: keys j >= lens[b] are masked (keymask is not read), the legacy rel_shift is taken at
         lens[b], and every convolution with more than one tap reads zeros behind lens[b].  Rows behind a length hold finite
-        values nobody reads.  fp32 compute, eval mode, forward only."""
+        values nobody reads.  fp32 compute, eval mode, forward only.  pos_rows: packed speech | text rows, see _mha_fwd."""
         # (encoder_layer.py:117-181)
         if lens is not None:
             self._check_ragged(lens, B)
         x = self._ffn_fwd(pre + ".ffm", pre + ".ffm", x, T, lens)
-        x = self._mha_fwd(pre + ".mha", pre + ".mha", x, pos, keymask, B, T, lens)
+        x = self._mha_fwd(pre + ".mha", pre + ".mha", x, pos, keymask, B, T, lens, pos_rows)
         x = self._conv_fwd(pre + ".cnv", pre + ".cnv", x, T, lens)
         x = self._ffn_fwd(pre + ".ff", pre + ".ff", x, T, lens)
         return self._ln_fwd(pre + ".fin", x, pre + ".fin.ln", out_dtype=torch.float32)
@@ -986,7 +1011,11 @@ class MLMEngine:
             self.fused_attn_train_min <= nblk <= 65536 and T <= 2048
         return fused_now, fused_train_now
 
-    def forward(self, batch: Dict[str, torch.Tensor], need_grad: bool = True, gscale: float = 1.0):
+    def forward(self, batch: Dict[str, torch.Tensor], need_grad: bool = True, gscale: float = 1.0, lens=None):
+        """lens = (slens, tlens), device int32 [B]: every row is computed as if it had been passed alone at slens[b] frames and
+        tlens[b] phones (_forward_rows_alone; fp32 compute, eval mode, forward only).  No loss is computed then."""
+        if lens is not None:
+            return self._forward_rows_alone(batch, need_grad, lens)
         c, p, ws = self.c, self.store.p, self.ws
         speech = batch["speech"].contiguous()
         B, Tm, idim = speech.shape
@@ -1167,6 +1196,94 @@ class MLMEngine:
         self.sv["head"] = (hs, before, after, db, da)
         return dict(loss=loss, before=before.view(B, Tm, c.odim),
                     after=(after if after is not None else before).view(B, Tm, c.odim))
+
+    def _forward_rows_alone(self, batch, need_grad, lens):
+        """forward() of a padded batch whose row b comes out as the reference gives it for that row passed ALONE (its driver is
+        B = 1 throughout): the pre-speech blocks run ragged at slens, then the rows are PACKED -- row b = its sl_b speech tokens
+        with its tl_b text tokens directly behind them (a3t_concat_rows_ragged), as in the row alone, where no padding separates
+        the two -- and every block runs ragged at n_b = sl_b + tl_b.  The encoder's positional rows are cat(pe[:sl_b], pe[:tl_b])
+        per row (block_fwd(pos_rows=)), the decoder's pe[:n_b] are a prefix of the shared table.  The speech and text masks are
+        not read: the lengths say the same.  In the head the postnet's k-tap convolutions read zeros behind sl_b (a3t_zero_tail
+        on its input and behind every BatchNorm, whose shift makes those rows non-zero).  Rows of before / after behind sl_b
+        are unspecified (finite).  No loss."""
+        c, p, ws = self.c, self.store.p, self.ws
+        slens, tlens = lens
+        speech = batch["speech"].contiguous()
+        B, Tm, idim = speech.shape
+        text = batch["text"].contiguous()
+        Tp = text.shape[1]
+        T = Tm + Tp
+        d = c.adim
+        self._need_grad = bool(need_grad)
+        self._check_ragged(slens, B)
+        self._check_ragged(tlens, B)
+        self.dims = (B, Tm, Tp, T)
+        self._fused_now = self._fused_train_now = False
+        self.attn_path, self.block_dims = {}, {}
+        self._mode_tag = ops.gemm_mode_tag()
+        self.step_seed += 1
+        self.refresh_weights()
+        self._arena_clear("fwd64")
+        self._P_ahead, self._pos_ev = {}, None      # every block projects its own positional rows, on the main stream
+        masked = batch["masked_position"].contiguous().view(torch.uint8)
+        spos = batch["speech_segment_pos"].contiguous()
+        tpos = batch["text_segment_pos"].contiguous()
+        # --- prologue: as forward()'s, the speech and the text tokens in buffers of their own
+        xm = self._act("emb.xm", (B * Tm, idim))
+        ops.mask_fill(speech.view(B * Tm, idim), masked, p["mask_feature"], xm)
+        e0 = ws.get("emb.e0", (B * Tm, d))
+        ops.linear_fwd(xm, self.W("emb.w"), e0, bias=p["emb.b"], compute=self.cmp)
+        e = self._ln_fwd("emb.ln", e0, "emb.ln", eps=1e-5, out_dtype=torch.float32)
+        xscale = math.sqrt(d)
+        seg = p["seg"] if c.segment_emb else None
+        spk = None
+        if c.spk_embed_dim > 0 and batch.get("spembs") is not None:
+            se = batch["spembs"].to(self.dev, torch.float32).contiguous()
+            spk = ws.get("emb.spk", (B, d))
+            ops.linear_fwd(se, p["spk.w"], spk, bias=p["spk.b"], compute=F32)
+        xsp, xst = ws.get("emb.xsp", (B * Tm, d)), ws.get("emb.xst", (B * Tp, d))
+        ops.embed_finish_fwd(e, p["temb"], seg, text, spos, tpos, xsp, B, Tm, 0, d, xscale, drop=(0.0, 0), spk=spk)
+        ops.embed_finish_fwd(e, p["temb"], seg, text, spos, tpos, xst, B, 0, Tp, d, xscale, drop=(0.0, 0), spk=spk)
+        x = xsp
+        for i in range(c.pre_blocks):
+            x = self.block_fwd(f"pre.{i}", x, self.pe[:Tm], None, B, Tm, lens=slens)
+        xs = ws.get("emb.xs", (B * T, d))
+        ops.concat_rows_ragged(x, xst, xs, slens, tlens, B, Tm, Tp, d)
+        n = ws.get("emb.nlens", (B,), torch.int32)
+        torch.add(slens, tlens, out=n)
+        x = xs
+        for i in range(c.enc_blocks):
+            x = self.block_fwd(f"enc.{i}", x, self.pe[:max(Tm, Tp)], None, B, T, lens=n, pos_rows=(slens, tlens, Tm, Tp))
+        x = self._ln_fwd("enc.after", x, "enc.after", out_dtype=torch.float32)
+        if c.has_decoder:
+            xd = ws.get("dec.in", (B * T, d))
+            ops.scale(x, xd, xscale)
+            x = xd
+            for i in range(c.dec_blocks):
+                x = self.block_fwd(f"dec.{i}", x, self.pe[:T], None, B, T, lens=n)
+            x = self._ln_fwd("dec.after", x, "dec.after", out_dtype=torch.float32)
+        # --- head: the first Tm rows of a packed row hold its speech frames, then text tokens or zeros
+        hs = self._act("head.hs", (B * Tm, d))
+        ops.slice_rows(x, hs, B, T, Tm, d)
+        before = ws.get("head.before", (B * Tm, c.odim))
+        ops.linear_fwd(hs, self.W("sfc.w"), before, bias=p["sfc.b"], compute=self.cmp)
+        if c.postnet_layers == 0:
+            return dict(loss=None, before=before.view(B, Tm, c.odim), after=before.view(B, Tm, c.odim))
+        ops.zero_tail(before, slens, 1, B, Tm)
+        y = before
+        pad = (c.postnet_filts - 1) // 2
+        for l in range(c.postnet_layers):
+            W = self.W(f"post.{l}.w")
+            last = (l == c.postnet_layers - 1)
+            z = ws.get(f"post.{l}.z", (B * Tm, W.shape[0]))
+            ops.conv_fwd(y, W, z, Tm, pad, compute=self.cmp)
+            y = ws.get(f"post.{l}.o", (B * Tm, W.shape[0]))
+            self._bn_fwd(f"post.{l}", z, f"post.{l}.bn", f"post.{l}.bn", ACT_NONE if last else ACT_TANH, y)
+            ops.zero_tail(y, slens, 1, B, Tm)
+        after = ws.get("head.after", (B * Tm, c.odim))
+        after.copy_(before)
+        ops.axpy(y, after, 1.0)
+        return dict(loss=None, before=before.view(B, Tm, c.odim), after=after.view(B, Tm, c.odim))
 
     def backward(self, on_group_done=None):
         """Accumulates d loss / d param (times the gscale given to forward) into store.grad.

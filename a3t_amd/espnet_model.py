@@ -194,29 +194,93 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
         return dict(feat_gen=[sp[:, :s], zs[0][s:e].clone(), sp[:, e:]])
 
     def inference_batch(self, speech, text, masked_position, speech_mask, text_mask, speech_segment_pos, text_segment_pos,
-                        span_boundary, spembs=None, use_teacher_forcing: bool = True):
+                        span_boundary, spembs=None, use_teacher_forcing: bool = True, rows: str = "batch",
+                        max_score_elems: int = 1 << 24):
         """Teacher-forced infill of a whole batch: one forward-only pass, then a3t_splice_spans writes, per row b,
         out[b][t] = after[b][t] for span_boundary[b][0] <= t < span_boundary[b][1], speech[b][t] for the other valid frames
         and 0 behind the row's length speech_mask[b].sum() (the batch's speech_lengths are raw samples, as in the reference).
         Returns (out (B, Tmax, odim) fp32, lengths (B,) int32), both on the device.
 
-        A row of a batch is what the reference's collate function and model give for that row IN that batch.  It is not
-        bit-identical to the same request run alone, in the reference either: the STFT reflects at the end of the padded
-        waveform, the convolution module does not mask padded frames and the legacy rel_shift depends on the padded length.
-        The model is trained on exactly such batches."""
+        rows="batch" (the default): a row is what the reference's collate function and model give for that row IN that batch.
+        That is not the same request run alone, in the reference either: the convolution module and the FFN convolutions do not
+        mask padded frames, padding separates a short row's speech and text tokens, and the legacy rel_shift and the encoder's
+        positional table depend on the padded lengths.  The model is trained on exactly such batches.
+
+        rows="alone": row b is computed as the reference's B = 1 driver computes it, from the row's own speech_mask / text_mask
+        lengths (prefix masks; MLMEngine._forward_rows_alone), to fp32 rounding -- not bit for bit.  fp32 compute, eval mode.
+        The rows are sorted by tokens n_b and cut into chunks with B * heads * n_max^2 <= max_score_elems (each of the three
+        score-sized tensors of the materialised attention); a chunk of one row takes the plain B = 1 pass at the row's exact
+        lengths.  The device lengths come from the masks without a host synchronisation; the chunking needs them on the host,
+        which is free when the masks arrive as host tensors and is skipped when the padded batch fits the cap as it is."""
         from . import ops
         if not use_teacher_forcing:
             raise NotImplementedError("only use_teacher_forcing=True is functional in the reference")
+        if rows not in ("batch", "alone"):
+            raise ValueError(f"rows must be 'batch' or 'alone', got {rows!r}")
         B, Tmax = speech.shape[0], speech.shape[1]
         sb = span_boundary if torch.is_tensor(span_boundary) else torch.tensor([[int(s), int(e)] for s, e in span_boundary])
         if sb.shape != (B, 2):
             raise ValueError(f"span_boundary must be (B, 2) = ({B}, 2), got {tuple(sb.shape)}")
+        if rows == "alone":
+            if self.compute != "f32" or self.training:
+                raise ValueError(f"rows='alone' needs a model built with compute='f32' in eval mode (compute={self.compute!r}, "
+                                 f"training={self.training}): the fused bf16 attention forward has no per-row rel_shift")
+            host = None
+            if not speech_mask.is_cuda and not text_mask.is_cuda:
+                host = (speech_mask.reshape(B, -1).sum(-1).tolist(), text_mask.reshape(B, -1).sum(-1).tolist())
         batch = self._batch(speech, text, masked_position, speech_mask, text_mask, speech_segment_pos, text_segment_pos, spembs)
         dev = self.store.device
         spans = sb.to(torch.int32).contiguous().to(dev, non_blocking=True)
+        if rows == "alone":
+            return self._infill_rows_alone(batch, spans, host, int(max_score_elems))
         out = self._engine().forward(batch, need_grad=False)
         sp = batch["speech"].contiguous()                     # (bf16 mode may have extended the padding)
         res = torch.empty(B, Tmax, sp.shape[2], dtype=torch.float32, device=dev)
         lens = torch.empty(B, dtype=torch.int32, device=dev)
         ops.splice_spans(out["after"].contiguous(), sp, batch["speech_mask"].contiguous().view(B, -1), spans, res, lens)
+        return res, lens
+
+    _ROW_KEYS = ("speech", "masked_position", "speech_mask", "speech_segment_pos")      # [B][T_mel]..., the rest [B][T_phn]...
+
+    def _infill_rows_alone(self, batch, spans, host, max_score_elems):
+        """inference_batch(rows="alone") behind the argument checks.  host: (frames, phones) per row as host lists, or None."""
+        from . import ops
+        from .engine import score_chunks
+        dev, eng = self.store.device, self._engine()
+        speech = batch["speech"]
+        B, Tm, odim = speech.shape
+        Tp = batch["text"].shape[1]
+        b = dict(batch, speech_mask=batch["speech_mask"].reshape(B, Tm), text_mask=batch["text_mask"].reshape(B, Tp))
+        slens = b["speech_mask"].sum(-1, dtype=torch.int32)
+        tlens = b["text_mask"].sum(-1, dtype=torch.int32)
+        res = torch.empty(B, Tm, odim, dtype=torch.float32, device=dev)
+        lens = torch.empty(B, dtype=torch.int32, device=dev)
+
+        def run(sub, sp, lp, out_rows, out_lens):
+            out = eng.forward(sub, need_grad=False, lens=lp)
+            ops.splice_spans(out["after"].contiguous(), sub["speech"].contiguous(), sub["speech_mask"].contiguous(), sp,
+                             out_rows, out_lens)
+
+        if B > 1 and host is None and B * self.cfg.heads * (Tm + Tp) ** 2 <= max_score_elems:
+            # one chunk as the batch stands: nobody needs the lengths on the host
+            run(b, spans, (slens, tlens), res, lens)
+            return res, lens
+        if host is None:
+            both = torch.stack([slens, tlens]).tolist()      # the one host synchronisation: the chunking needs the lengths
+            host = (both[0], both[1])
+        sl, tl = [int(x) for x in host[0]], [int(x) for x in host[1]]
+        for ch in score_chunks([s + t for s, t in zip(sl, tl)], self.cfg.heads, max_score_elems):
+            tm, tp = max(sl[i] for i in ch), max(tl[i] for i in ch)
+            idx = torch.tensor(ch, dtype=torch.long).to(dev, non_blocking=True)
+            sub = {}
+            for k, v in b.items():      # the chunk's rows, cut to the chunk's longest on both sides
+                v = v.index_select(0, idx)
+                sub[k] = v if k == "spembs" else v[:, :(tm if k in self._ROW_KEYS else tp)].contiguous()
+            r = torch.empty(len(ch), Tm, odim, dtype=torch.float32, device=dev)
+            ln = torch.empty(len(ch), dtype=torch.int32, device=dev)
+            # a chunk of one row: the plain B = 1 pass at the row's exact lengths
+            lp = None if len(ch) == 1 else (slens.index_select(0, idx), tlens.index_select(0, idx))
+            run(sub, spans.index_select(0, idx).contiguous(), lp, r, ln)
+            res.index_copy_(0, idx, r)
+            lens.index_copy_(0, idx, ln)
         return res, lens

@@ -86,7 +86,13 @@ class LogMelFbank:
             self._dev_tables = (torch.from_numpy(basis).to(self.device), torch.from_numpy(mel).to(self.device), nb, ld)
         return self._dev_tables
 
-    def __call__(self, wav: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def __call__(self, wav: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+                 rows: str = "batch") -> Tuple[torch.Tensor, torch.Tensor]:
+        """rows="batch": every row is reflected at the end of the PADDED waveform, as the reference's Stft does with a batch.
+        rows="alone": row b is reflected at its own last sample lengths[b] (a3t_reflect_pad_ragged), so its olens[b] frames are
+        those of wav[b, :lengths[b]] passed alone -- to the rounding of the GEMM kernel a3t_gemm_plan picks for the batch's M."""
+        if rows not in ("batch", "alone"):
+            raise ValueError(f"rows must be 'batch' or 'alone', got {rows!r}")
         basis, melT, nb, ld = self._tables()
         dev = self.device
         x = wav.to(dev, torch.float32).contiguous()
@@ -99,7 +105,11 @@ class LogMelFbank:
         F = 1 + (N + 2 * pad - self.n_fft) // self.hop_length
         row = (N + 2 * pad + 3) // 4 * 4
         xp = torch.empty(B, row, device=dev)
-        ops.reflect_pad(x, xp, pad)
+        if rows == "alone":
+            hl = lengths.tolist()
+            ops.reflect_pad_ragged(x, xp, pad, torch.tensor(hl, dtype=torch.int32).to(dev, non_blocking=True), hl)
+        else:
+            ops.reflect_pad(x, xp, pad)
         S = torch.empty(B * F, 2 * nb, device=dev)
         # frames are overlapping rows: A(m,k) = xp[b][m*hop + k]
         ops.gemm(xp, basis, S, F, 2 * nb, self.n_fft, self.hop_length, 1, self.n_fft, 1, 2 * nb, batch=B, batch_inner=1,

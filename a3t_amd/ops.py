@@ -480,6 +480,14 @@ def concat_rows(speech, text, xs, B, Tm, Tp, D):
     L.check(L.load().a3t_concat_rows(_ptr(speech), _ptr(text), _ptr(xs), B, Tm, Tp, D, _stream()), "concat_rows")
 
 
+def concat_rows_ragged(speech, text, xs, slens, tlens, B, Tm, Tp, D, speech_bs=None, text_bs=None):
+    """xs[B][Tm+Tp][D]: row b = speech[b][:slens[b]] | text[b][:tlens[b]] | zeros (fp32; slens / tlens device int32 [B]).
+    speech_bs / text_bs: elements between the sources' batch rows (default Tm * D / Tp * D); 0 = one source for every row."""
+    L.check(L.load().a3t_concat_rows_ragged(_ptr(speech), _ptr(text), _ptr(xs), _ptr(_i32(slens, "slens")),
+                                            _ptr(_i32(tlens, "tlens")), B, Tm, Tp, D, Tm * D if speech_bs is None else speech_bs,
+                                            Tp * D if text_bs is None else text_bs, _stream()), "concat_rows_ragged")
+
+
 def split_rows(dxs, dspeech, dtext, B, Tm, Tp, D):
     """The backward of concat_rows: dspeech / dtext = the two parts of dxs (stored)."""
     L.check(L.load().a3t_split_rows(_ptr(dxs), _ptr(dspeech), _ptr(dtext), B, Tm, Tp, D, _stream()), "split_rows")
@@ -488,6 +496,20 @@ def split_rows(dxs, dspeech, dtext, B, Tm, Tp, D):
 def reflect_pad(x, out, pad):
     B, N = x.shape
     L.check(L.load().a3t_reflect_pad(_ptr(x), _ptr(out), B, N, pad, out.shape[1], _stream()), "reflect_pad")
+
+
+def reflect_pad_ragged(x, out, pad, lens, host_lens):
+    """reflect_pad with each row reflected about its own ends (a3t_reflect_pad_ragged): lens = device int32 [B], host_lens
+    = the same lengths on the host, checked here -- torch.stft refuses a row that is not longer than the pad, and so does this."""
+    B, N = x.shape
+    host_lens = [int(n) for n in host_lens]
+    if len(host_lens) != B or lens.numel() != B:
+        raise ValueError(f"reflect_pad_ragged: {B} rows, {len(host_lens)} host lengths, {lens.numel()} device lengths")
+    for b, n in enumerate(host_lens):
+        if n <= pad or n > N:
+            raise ValueError(f"reflect_pad_ragged: row {b} has {n} samples; reflection by {pad} needs {pad} < n <= {N}")
+    L.check(L.load().a3t_reflect_pad_ragged(_ptr(x), _ptr(out), _ptr(_i32(lens, "lens")), B, N, pad, out.shape[1], _stream()),
+            "reflect_pad_ragged")
 
 
 def stft_amp(S, amp, nbins):

@@ -325,6 +325,13 @@ int a3t_slice_rows(const float* x, void* y, int y_dtype, int B, int T, int Tm, i
  * 16-byte aligned pointers; Tm == 0 or Tp == 0 is allowed (that side's pointer is not touched). */
 int a3t_concat_rows(const float* speech, const float* text, float* xs, int B, int Tm, int Tp, int D, void* stream);
 int a3t_split_rows(const float* dxs, float* dspeech, float* dtext, int B, int Tm, int Tp, int D, void* stream);
+/* The packed join of a ragged batch, forward only: row b of xs[B][Tm+Tp][D] = speech[b][0:slens[b]], then text[b][0:tlens[b]]
+ * directly behind it -- the token sequence of row b passed alone -- then zeros.  slens / tlens: device int32 [B], clamped to
+ * [0, Tm] / [0, Tp].  speech_bs / text_bs: elements between the batch rows of the two sources (multiples of 4); 0 = one source
+ * read by every row (linear_pos of the positional table, gathered to cat(pe[:sl_b], pe[:tl_b]) per row).  fp32, D % 4 == 0,
+ * 16-byte aligned pointers. */
+int a3t_concat_rows_ragged(const float* speech, const float* text, float* xs, const int32_t* slens, const int32_t* tlens, int B,
+                           int Tm, int Tp, int D, int64_t speech_bs, int64_t text_bs, void* stream);
 /* fp32 -> bf16 (round to nearest even); n % 4 == 0 (the flat parameter buffer once per step) */
 int a3t_cast_bf16(const float* x, void* y, int64_t n, void* stream);
 /* Transposed bf16 shadows of `count` Conv1d weights W[N][taps][C] (multi_layer_conv.py:36-50) living at element offsets
@@ -341,6 +348,10 @@ int a3t_split_bf16(const float* x, void* hi, void* lo, int64_t n, void* stream);
  * tts/feats_extract/log_mel_fbank.py:88-106).  The STFT is a GEMM of overlapping frames
  * (A row stride = hop) with the windowed DFT basis; these are the element-wise stages around it. */
 int a3t_reflect_pad(const float* x, float* out, int B, int N, int pad, int ld, void* stream);
+/* a3t_reflect_pad with a length per row (device int32 lens[B], pad < lens[b] <= N, checked by the caller who has them on the
+ * host): out[b][pad + i] = x[b][i] for i < lens[b], the pad samples in front mirrored about sample 0, the pad samples behind
+ * about sample lens[b] - 1, zeros from pad + lens[b] + pad to ld: the row as a3t_reflect_pad stores x[b][0:lens[b]] alone. */
+int a3t_reflect_pad_ragged(const float* x, float* out, const int32_t* lens, int B, int N, int pad, int ld, void* stream);
 int a3t_stft_amp(const float* S, float* amp, int64_t rows, int nbins, int ld, void* stream);
 int a3t_logmel_finish(float* mel, const int64_t* olens, int B, int F, int C, void* stream);
 

@@ -21,8 +21,14 @@ model would cost.
           median of --calls, on the padded 8 x 1000 frames and on the ragged lengths, with the bytes per second the f16 blocks
           reach against their HBM model (x read and written, cu16 read, skips read and written: 1184 B per sample and block).
 
+  --rows batch alone: the rows="alone" path of edit_batch (every row computed as the request alone, fp32 compute only) next to
+          the default, keys `<model>.f32.rows.n<N>`: order A, B = edit_batch(requests), C = edit_batch(requests, rows="alone"),
+          A again, full and span-only vocoding; the stages of B and of C one by one; and per request the largest distance of
+          B's and of C's mel to A's (the request edited alone), relative to the scale max(1, max |mel|), and of the collated
+          log-mels.  --compute is not read for these legs.
+
     python tools/sedit_batch_latency.py [--models c2] [--compute bf16 f32] [--n 1 4 8] [--calls 50] [--warmup 5] [--kernel]
-                                        [--vocoder-compute f32 f16]
+                                        [--vocoder-compute f32 f16] [--rows batch alone]
 """
 import argparse
 import json
@@ -86,12 +92,13 @@ def timed(fn, calls, warmup):
     return 1e3 * float(np.median(ts))
 
 
-def legs(ed, reqs, span_only, calls, warmup):
+def legs(ed, reqs, span_only, calls, warmup, rows="batch"):
     """The stages of edit_batch one by one, a synchronisation after each; ms per request."""
     from a3t_amd.sedit import plan_batch
     from a3t_amd.vocoder import span_window
     acc = {k: [] for k in ("plan", "duration_model", "collate", "infill", "vocoder", "splice_copy")}
     B, hop = len(reqs), ed.hop
+    alone = {"rows": rows} if rows != "batch" else {}
     for it in range(warmup + calls):
         t_dur = [0.0]
 
@@ -109,12 +116,12 @@ def legs(ed, reqs, span_only, calls, warmup):
 
         plans, data = plan_batch(reqs, ed.fs, hop, dur, ed.token_id_fn)
         lap()
-        feats = ed.collate_fn(data)[1]
+        feats = ed.collate_fn(data, **alone)[1]
         flen = [int(n) for n in feats["speech_mask"].reshape(B, -1).sum(-1).tolist()]
         feats = {k: v.to("cuda") for k, v in feats.items() if k not in ("span_boundary", "speech_lengths", "text_lengths")}
         lap()
         with torch.no_grad():
-            mel, _ = ed.model.inference_batch(**feats, span_boundary=[p.new_span_boundary for p in plans])
+            mel, _ = ed.model.inference_batch(**feats, span_boundary=[p.new_span_boundary for p in plans], **alone)
         lap()
         if span_only:
             m = ed.vocoder.margin_frames
@@ -233,6 +240,49 @@ def kernel_bench_f16(frames, lengths_sets, calls=50, warmup=3):
     return out
 
 
+def _of_scale(got, ref):
+    ref = ref.double()
+    return float((got.double() - ref).abs().max()) / max(1.0, float(ref.abs().max())) if ref.numel() else 0.0
+
+
+def rows_alone_legs(ed, oc, reqs, calls, warmup):
+    """A, B, C, A (module docstring, --rows) on one set of requests, fp32 compute; ms per request and mel distances."""
+    from a3t_amd.sedit import plan_batch
+    n = len(reqs)
+    args = [(r.wav_org, r.times2, r.word2phns, r.new_phns, r.new_word2phns, r.old_str, r.new_str) for r in reqs]
+    span = ("orgin_replaced",)
+
+    def loop():
+        for x in args:
+            ed.edit(*x)
+
+    r = {"A_loop_of_edit_ms": round(timed(loop, calls, warmup) / n, 3),
+         "B_full_ms": round(timed(lambda: ed.edit_batch(reqs), calls, warmup) / n, 3),
+         "B_span_only_ms": round(timed(lambda: ed.edit_batch(reqs, outputs=span), calls, warmup) / n, 3),
+         "C_full_ms": round(timed(lambda: ed.edit_batch(reqs, rows="alone"), calls, warmup) / n, 3),
+         "C_span_only_ms": round(timed(lambda: ed.edit_batch(reqs, outputs=span, rows="alone"), calls, warmup) / n, 3),
+         "A_again_ms": round(timed(loop, calls, warmup) / n, 3)}
+    ed.vocoder, voc = None, ed.vocoder
+    one = [ed.edit(*x)["feat"] for x in args]
+    got_b, got_c = ed.edit_batch(reqs), ed.edit_batch(reqs, rows="alone")
+    ed.vocoder = voc
+    r["frames"] = [int(f.shape[0]) for f in one]
+    r["span_frames"] = [int(g["new_span_boundary"][1] - g["new_span_boundary"][0]) for g in got_b]
+    r["mel_B_to_A_of_scale"] = [float(f"{_of_scale(g['feat'], f):.3e}") for g, f in zip(got_b, one)]
+    r["mel_C_to_A_of_scale"] = [float(f"{_of_scale(g['feat'], f):.3e}") for g, f in zip(got_c, one)]
+    data = plan_batch(reqs, ed.fs, ed.hop, ed.duration_fn, ed.token_id_fn)[1]
+    fb, fc = ed.collate_fn(data)[1]["speech"], ed.collate_fn(data, rows="alone")[1]["speech"]
+    lb, lc = [], []
+    for i, d in enumerate(data):
+        f1 = ed.collate_fn([d])[1]["speech"][0]
+        lb.append(float((fb[i, :f1.shape[0]] - f1).abs().max()))
+        lc.append(float((fc[i, :f1.shape[0]] - f1).abs().max()))
+    r["logmel_B_to_A_max"], r["logmel_C_to_A_max"] = float(f"{max(lb):.3e}"), float(f"{max(lc):.3e}")
+    k = max(5, calls // 5)
+    r["legs_B_full_ms"], r["legs_C_full_ms"] = legs(ed, reqs, False, k, 2), legs(ed, reqs, False, k, 2, rows="alone")
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", nargs="*", default=["c2"])      # (none given: the --kernel leg alone)
@@ -243,6 +293,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--kernel", action="store_true")
     ap.add_argument("--vocoder-compute", nargs="+", default=["f32"], choices=["f32", "f16"])
+    ap.add_argument("--rows", nargs="+", default=["batch"], choices=["batch", "alone"])
     a = ap.parse_args()
     prop = torch.cuda.get_device_properties(0)
     out = {"device": f"{prop.name} ({getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs)"}
@@ -253,6 +304,19 @@ def main():
         if "f16" in a.vocoder_compute:
             out["pwg_blocks_f16"] = kernel_bench_f16(1000, sets, a.calls)
             print(json.dumps({"pwg_blocks_f16": out["pwg_blocks_f16"]}), flush=True)
+    if "alone" in a.rows:
+        for which in a.models:
+            ed, oc = editor(which, "f32")
+            for n in a.n:
+                rs = np.random.RandomState(n)
+                lo, hi = a.frames_range
+                reqs = [request(int(f), int(k), oc, seed=10 * n + i)
+                        for i, (f, k) in enumerate(zip(np.linspace(hi, lo, n).astype(int) if n > 1 else [(lo + hi) // 2],
+                                                       rs.randint(3, 11, n)))]
+                out[f"{which}.f32.rows.n{n}"] = rows_alone_legs(ed, oc, reqs, a.calls, a.warmup)
+                print(json.dumps({f"{which}.f32.rows.n{n}": out[f"{which}.f32.rows.n{n}"]}), flush=True)
+        print(json.dumps({"sedit_batch_latency": out}))
+        return
     for which in a.models:
         for compute, vc in [(c, v) for c in a.compute for v in a.vocoder_compute]:
             ed, oc = editor(which, compute, vc)
