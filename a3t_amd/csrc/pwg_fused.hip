@@ -194,6 +194,10 @@ __global__ __launch_bounds__(512, 2) void pwg_stage_kernel(PwgArgs a) {
 static int pwg_block(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1, float* g,
                      float* skips, const int32_t* tiles, int ntiles, int B, int Tw, int dil, void* stream) {
     if (dil <= 0 || !x || !cu || !wt0 || !b0 || !wt1 || !b1 || !g || !skips) return A3T_EINVAL;
+    // x, cu, g and the two weight matrices are read as float4
+    if ((((uintptr_t)x | (uintptr_t)cu | (uintptr_t)g | (uintptr_t)wt0 | (uintptr_t)wt1) & 15) ||
+        (((uintptr_t)b0 | (uintptr_t)b1 | (uintptr_t)skips) & 3))
+        return A3T_EINVAL;
     const int n = wave_grid(tiles, ntiles, B, Tw);
     if (n <= 0) return n;
     PwgArgs a;

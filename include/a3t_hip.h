@@ -505,7 +505,8 @@ int a3t_dropout_bwd_cast(const float* g, void* gm, int gm_dtype, float* colsum, 
  * x [B*Tw][64], cu [B*Tw][80] (upsampled mel), g scratch [B*Tw][64], skips [B*Tw][64], all fp32 channels-last.
  * wt0 [272][128]: row k = tap*64 + in_channel (dilated k=3 conv, taps at t-dil, t, t+dil) | 192 + aux channel; column
  * n' = permuted gate channel: n' = 64*(c/32) + 32*half + c%32 for gate channel c (0..63), half 0 = tanh, 1 = sigmoid;
- * b0 [128] permuted the same way.  wt1 [64][128] = conv1x1_out.weight^T (columns 0..63 residual, 64..127 skip), b1 [128]. */
+ * b0 [128] permuted the same way.  wt1 [64][128] = conv1x1_out.weight^T (columns 0..63 residual, 64..127 skip), b1 [128].
+ * x, cu, g, wt0 and wt1 are read 16 bytes at a time: A3T_EINVAL unless they are 16-byte aligned (b0, b1, skips: 4-byte). */
 int a3t_pwg_block(float* x, const float* cu, const float* wt0, const float* b0, const float* wt1, const float* b1,
                   float* g, float* skips, int B, int Tw, int dil, void* stream);
 /* The tile contract of the waveform kernels (a3t_pwg_block_ragged, a3t_pwg_block_f16, a3t_hfg_conv, a3t_hfg_conv_f16, a3t_hfg_out, a3t_mgan_*, a3t_pqmf_synthesis, a3t_smg_*;
