@@ -197,6 +197,7 @@ __global__ __launch_bounds__(256) void cast_conv_t_kernel(const float* __restric
 extern "C" int a3t_cast_bf16_conv_t(const float* src, void* dst, const int64_t* src_off, const int64_t* dst_off, int count, int N,
                                     int taps, int C, void* stream) {
     if (count <= 0 || N <= 0 || taps <= 0 || C <= 0) return A3T_EINVAL;
+    if (taps > 65535 || count > 65535) return A3T_EINVAL;      // grid.y, grid.z
     dim3 grid((unsigned)(((N + 31) / 32) * ((C + 31) / 32)), (unsigned)taps, (unsigned)count);
     hipLaunchKernelGGL(cast_conv_t_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, (unsigned short*)dst, src_off, dst_off, N, taps, C);
     return (int)hipGetLastError();
@@ -410,6 +411,7 @@ extern "C" int a3t_mlm_loss_scratch_floats(int M) {
 extern "C" int a3t_mlm_loss(const float* before, const float* after, const float* target, const uint8_t* masked,
                             float* loss_out, float* d_before, float* d_after, float* scratch, int M, int C, int l2,
                             float gscale, void* stream) {
+    if (M <= 0 || C <= 0 || !before || !target || !masked || !loss_out || !scratch) return A3T_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     int nblk = (M + 3) / 4;
     if (nblk > LOSS_BLOCKS) nblk = LOSS_BLOCKS;
@@ -511,8 +513,10 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, c
 extern "C" int a3t_clip_adam(float* p, const float* g, float* m, float* v, const double* partial, float* norm_out,
                              int64_t n, float lr, float beta1, float beta2, float eps, int step, float clip,
                              float gscale, void* stream) {
-    float bc1 = 1.f - powf(beta1, (float)step);
-    float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+    // in double from the fp32 betas and the integer step, rounded once, as clip_adam_noam_kernel does: 1 - beta2^t in float
+    // loses up to 2^-24 / (1 - beta2^t) of bc2s at the first steps, ten times what one element update loses otherwise
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     hipLaunchKernelGGL(clip_adam_kernel, dim3(nblocks(n / 4, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, partial,
                        norm_out, n, lr, beta1, beta2, eps, bc1, bc2s, clip, gscale);
     return (int)hipGetLastError();
@@ -800,8 +804,9 @@ __global__ __launch_bounds__(256) void dropout_bwd_cast_kernel(const float* __re
 }
 extern "C" int a3t_dropout_bwd_cast(const float* g, void* gm, int gm_dtype, float* colsum, float colsum_scale, int M,
                                     int C, float p, uint32_t key, void* stream) {
-    if (p < 0.f || p >= 1.f) return A3T_EINVAL;
+    if (p < 0.f || p >= 1.f || M <= 0 || C <= 0) return A3T_EINVAL;
     int rpb = 128;
+    if ((M + rpb - 1) / rpb > 65535) return A3T_EINVAL;      // grid.y
     dim3 grid((C + 63) / 64, (M + rpb - 1) / rpb);
     hipLaunchKernelGGL(dropout_bwd_cast_kernel, grid, dim3(256), 0, (hipStream_t)stream, g, gm, gm_dtype, colsum,
                        colsum_scale, M, C, (unsigned int)((double)p * 4294967296.0), 1.f / (1.f - p), key, rpb);
