@@ -391,6 +391,32 @@ class FS2DurationModel:
         ops.linear_fwd(sn, self.store.p["spk.ws"], out, bias=self.store.p["spk.b"], compute=F32)
         return out
 
+    def speaker_bias_table(self, spembs_list):
+        """speaker_bias for several x-vectors: (table [S][d] on the device, rows), rows[i] the table row of spembs_list[i].
+        One row per distinct x-vector OBJECT, in first-use order (as batch(..., prompts=) finds distinct prompts); the S vectors
+        go up in one copy, through one normalisation and one GEMM."""
+        c = self.c
+        if c.spk_embed_dim <= 0:
+            raise ValueError("this checkpoint has no x-vector projection (spk_embed_dim is 0)")
+        first, host = {}, []
+        rows = []
+        for i, x in enumerate(spembs_list):
+            if id(x) not in first:
+                v = np.asarray(x, np.float32).reshape(-1)
+                if v.shape[0] != c.spk_embed_dim:
+                    raise ValueError(f"spembs has {v.shape[0]} values, the checkpoint expects {c.spk_embed_dim} (x-vector {i})")
+                first[id(x)] = len(host)
+                host.append(v)
+            rows.append(first[id(x)])
+        if not host:
+            raise ValueError("no x-vectors")
+        s = torch.from_numpy(np.stack(host)).to(self.dev)
+        sn = torch.empty_like(s)
+        ops.l2_normalize(s, sn)
+        table = torch.empty(len(host), c.adim, dtype=torch.float32, device=self.dev)
+        ops.linear_fwd(sn, self.store.p["spk.ws"], table, bias=self.store.p["spk.b"], compute=F32)
+        return table, rows
+
     # ---- the style encoder -----------------------------------------------------------------------------------------------
     def _gst_derived(self):
         """What depends on the weights only, once per load: BatchNorm2d's running statistics folded into (scale, shift) per
@@ -520,10 +546,11 @@ class FS2DurationModel:
         if rows is None and style.shape[0] not in (1, B):
             raise ValueError(f"style has {style.shape[0]} rows for {B} sequences")
 
-    def forward_ids_batch(self, ids, lens, spk_bias=None, style=None, style_rows=None):
+    def forward_ids_batch(self, ids, lens, spk_bias=None, style=None, style_rows=None, spk_rows=None):
         """ids: device int64 [B][Tmax] (eos included; entries behind a row's length: any valid id), lens: device int32 [B],
         1 <= lens[b] <= Tmax.  One padded forward whose row b is computed as forward_ids computes it alone at lens[b]
-        (MLMEngine.block_fwd with lens); one speaker bias for the whole call.  Returns device tensors (hs [B][Tmax][d],
+        (MLMEngine.block_fwd with lens); one speaker bias [1][d] for the whole call, or with spk_rows (device int32 [B]) a table
+        [S][d] of which sequence b takes row spk_rows[b] (speaker_bias_table).  Returns device tensors (hs [B][Tmax][d],
         logd [B][Tmax], frames [B][Tmax] int64) valid until the next call; entries behind lens[b] are finite and mean nothing
         (hs is 0 there when the predictor's convs have more than one tap).
         style: device [B][d] (row b for sequence b), [1][d] (one prompt for all), or any [S][d] with style_rows, device int32 [B]:
@@ -537,13 +564,21 @@ class FS2DurationModel:
             raise ValueError(f"sequence length {T} outside 1..{c.max_len}")
         if spk_bias is not None and c.spk_embed_dim <= 0:
             raise ValueError("spk_bias given but the checkpoint has no x-vector projection")
+        if spk_rows is not None:
+            if spk_bias is None or spk_bias.dim() != 2 or spk_bias.shape[1] != d or spk_bias.dtype != torch.float32 \
+                    or not spk_bias.is_contiguous():
+                raise ValueError(f"spk_rows needs spk_bias as a contiguous fp32 [speakers][{d}] table")
+            if spk_rows.numel() != B:
+                raise ValueError(f"spk_rows has {spk_rows.numel()} entries for {B} sequences")
         self._check_style(style, B, style_rows)
-        hs, logd, frames = self._forward(ids, B, T, lens, spk_bias, style, style_rows)
+        hs, logd, frames = self._forward(ids, B, T, lens, spk_bias, style, style_rows, spk_rows)
         return hs.view(B, T, d), logd.view(B, T), frames.view(B, T)
 
-    def _forward(self, ids, B, T, lens, spk_bias, style, style_rows):
+    def _forward(self, ids, B, T, lens, spk_bias, style, style_rows, spk_rows=None):
         """The body of forward_ids (lens None, B = 1: no padded keys, the plain kernels) and of forward_ids_batch (lens: row b
-        as if alone at lens[b]).  Returns (hs [B*T][d], logd [B*T], frames [B*T])."""
+        as if alone at lens[b]).  spk_rows (device int32 [B]): spk_bias is a table [S][d] and sequence b takes row spk_rows[b];
+        that add, like the style's, also lands behind a row's length, so zero_tail stays behind both.
+        Returns (hs [B*T][d], logd [B*T], frames [B*T])."""
         c, p, ws = self.c, self.store.p, self.ws
         eng, M, d = self.eng, B * T, c.adim
         if self._tpos0.numel() < M:
@@ -559,7 +594,15 @@ class FS2DurationModel:
         hs = eng._ln_fwd("enc.after", x, "enc.after", out_dtype=torch.float32)
         if style is not None:
             ops.gst_add_style(hs, style, B, T, rows=style_rows)
-        if spk_bias is not None:
+        if spk_bias is not None and spk_rows is not None:
+            if c.spk_integration == "add":
+                ops.gst_add_style(hs, spk_bias, B, T, rows=spk_rows)
+            else:       # projection(cat[hs, s_b]) = hs W_h^T + (W_s s_b + b): the GEMM without bias, then row b's own
+                hc = ws.get("spk.hs", (M, d))
+                ops.linear_fwd(hs, p["spk.wh"], hc, compute=F32)
+                ops.gst_add_style(hc, spk_bias, B, T, rows=spk_rows)
+                hs = hc
+        elif spk_bias is not None:
             if c.spk_integration == "add":
                 ops.bias_act(hs, spk_bias, ACT_NONE)
             else:
@@ -588,7 +631,7 @@ class FS2DurationModel:
         return score_chunks(lengths, self.c.heads, max_score_elems)
 
     def predict_frames_batch(self, phn_lists, spk_bias=None, max_score_elems: int = 1 << 24, style=None,
-                             style_rows=None) -> List[np.ndarray]:
+                             style_rows=None, spk_rows=None) -> List[np.ndarray]:
         """predict_frames for several phone lists: one int64 array per list (eos entry included), in the order given.
         The ids of all lists go up through one pinned buffer in one copy and all frames come down in one: one host
         synchronisation per call.  The lists are sorted by length and cut into chunks of B rows padded to the chunk's longest,
@@ -599,10 +642,20 @@ class FS2DurationModel:
         predict_frames; every row of a larger chunk is computed as if alone, so the frames do not depend on the chunking.
         style (a GST model): device [len(phn_lists)][d], or [1][d] for one prompt behind all lists, or [S][d] with style_rows, a
         host list naming the style row of every list; the row indices travel with the ids, so a list keeps its style wherever
-        the sorting and chunking put it."""
+        the sorting and chunking put it.
+        spk_rows (a host list, one entry per list): spk_bias is a table [S][d] (speaker_bias_table) and list i takes its row
+        spk_rows[i]; these indices travel the same way, and a chunk of one list runs with that list's row as its one bias."""
         lists = [self.tokens_to_ids(list(ph)) for ph in phn_lists]
         if not lists:
             return []
+        krow = None
+        if spk_rows is not None:
+            krow = [int(r) for r in spk_rows]
+            if spk_bias is None or spk_bias.dim() != 2:
+                raise ValueError("spk_rows needs spk_bias as a [speakers][d] table")
+            if len(krow) != len(lists) or min(krow) < 0 or max(krow) >= spk_bias.shape[0]:
+                raise ValueError("spk_rows does not fit the phone lists and the rows of the speaker table")
+        bias_of = lambda i: spk_bias if krow is None else spk_bias[krow[i]:krow[i] + 1]
         srow = None
         if style is not None:
             self._check_style(style, len(lists), style_rows)
@@ -612,18 +665,19 @@ class FS2DurationModel:
                 raise ValueError("style_rows does not fit the phone lists and the style rows")
         one = lambda i: None if style is None else style[srow[i]:srow[i] + 1]
         if len(lists) == 1:
-            return [self.predict_frames(list(phn_lists[0]), spk_bias, one(0))]
+            return [self.predict_frames(list(phn_lists[0]), bias_of(0), one(0))]
         lengths = [len(x) for x in lists]
         if max(lengths) > self.c.max_len:
             raise ValueError(f"{max(lengths)} tokens: more than max_len {self.c.max_len}")
         chunks = self._chunks(lengths, int(max_score_elems))
         # staging layout (int64 words): per chunk its padded ids [B][Tmax], then all lengths as int32 pairs (with a style:
-        # the style rows as int32 behind the lengths, in the same order)
+        # the style rows as int32 behind the lengths, in the same order; with spk_rows: those behind them again)
         offs, n_ids = [], 0
         for ch in chunks:
             offs.append(n_ids)
             n_ids += len(ch) * lengths[ch[-1]]
-        n_len = (len(lists) + 1) // 2 if style is None else len(lists)
+        o_spk = len(lists) * (1 if style is None else 2)        # (int32 index of the first speaker row)
+        n_len = (o_spk + (0 if krow is None else len(lists)) + 1) // 2
         total = n_ids + n_len
         if self._stage_host is None or self._stage_host.numel() < total:
             cap = max(total, 2 * (self._stage_host.numel() if self._stage_host is not None else 0))
@@ -641,6 +695,8 @@ class FS2DurationModel:
                 hl[r + k] = lengths[i]
                 if style is not None:
                     hl[len(lists) + r + k] = srow[i]
+                if krow is not None:
+                    hl[o_spk + r + k] = krow[i]
             r += len(ch)
         self._stage_host[:total].copy_(torch.from_numpy(host))
         dev = self._stage_dev[:total]
@@ -651,10 +707,12 @@ class FS2DurationModel:
         for ch, o in zip(chunks, offs):
             B, T = len(ch), lengths[ch[-1]]
             if B == 1:
-                _, _, frames = self.forward_ids(dev[o:o + T], spk_bias, one(ch[0]))
+                _, _, frames = self.forward_ids(dev[o:o + T], bias_of(ch[0]), one(ch[0]))
             else:
                 rows = None if style is None else dev_lens[len(lists) + r:len(lists) + r + B]
-                _, _, frames = self.forward_ids_batch(dev[o:o + B * T].view(B, T), dev_lens[r:r + B], spk_bias, style, rows)
+                krows = None if krow is None else dev_lens[o_spk + r:o_spk + r + B]
+                _, _, frames = self.forward_ids_batch(dev[o:o + B * T].view(B, T), dev_lens[r:r + B], spk_bias, style, rows,
+                                                      krows)
             out[o:o + B * T].copy_(frames.reshape(-1))
             r += B
         got = out.cpu().numpy()
@@ -689,19 +747,49 @@ class FS2DurationModel:
         refuses a bare fn(phns): fn.with_prompt(wav) computes the prompt's style embedding once and returns a plain
         phns -> seconds callable (with .batch) bound to it; fn.batch(phn_lists, prompts=[...]) takes one prompt per list and
         computes one style embedding per distinct prompt OBJECT, all of them in one ragged pass.  fs must be the sampling rate
-        of the model's own log-mel extractor."""
+        of the model's own log-mel extractor.
+
+        A checkpoint with an x-vector projection gives callables (this one, and a GST model's with_prompt one) with
+        takes_speaker = True: fn.with_speaker(spembs) is the same callable bound to that x-vector (a GST model's keeps
+        needs_prompt / with_prompt), and fn.batch(phn_lists, speakers=[...]) takes one x-vector per list -- one speaker bias per
+        distinct OBJECT (speaker_bias_table), all lists still in one ragged forward; an entry of None stands for the callable's
+        own spembs.  prompts= and speakers= of a GST model are independent lists of the same length.  speakers=None is the
+        one-bias call."""
         bias = self.speaker_bias(spembs) if spembs is not None else None
         hop, fs32 = int(hop_length), np.float32(fs)
+        takes = self.c.spk_embed_dim > 0
 
         def seconds(frames):
             return ((frames * hop).astype(np.float32) / fs32)[:-1].tolist()
+
+        def speaker_args(speakers, n):
+            """(spk_bias, spk_rows) of a batch call over n lists."""
+            if speakers is None:
+                return bias, None
+            if not takes:
+                raise ValueError("speakers= given, but this checkpoint has no x-vector projection (spk_embed_dim is 0)")
+            speakers = list(speakers)
+            if len(speakers) != n:
+                raise ValueError(f"speakers: {len(speakers)} x-vectors for {n} phone lists")
+            for i, x in enumerate(speakers):
+                if x is None and spembs is None:
+                    raise ValueError(f"speakers[{i}] is None, which stands for the callable's own spembs: it was built without one")
+            if not speakers:
+                return bias, None
+            return self.speaker_bias_table([spembs if x is None else x for x in speakers])
+
+        def speaker_attrs(f, rebind):
+            if takes:
+                f.takes_speaker = True
+                f.with_speaker = rebind
+            return f
 
         if self.c.use_gst:
             if int(fs) != self.feats.fs:
                 raise ValueError(f"fs {fs} is not the sampling rate of the checkpoint's log-mel extractor ({self.feats.fs})")
 
-            def with_prompt(wav):
-                cache = []
+            def with_prompt(wav, _style=None):
+                cache = [] if _style is None else _style        # (_style: with_speaker hands the prompt's cache on)
 
                 def style():        # on the first query: a plan that asks for no durations costs no style embedding
                     if not cache:
@@ -711,20 +799,26 @@ class FS2DurationModel:
                 def fn(phns):
                     return seconds(self.predict_frames(list(phns), bias, style()))
 
-                def batch(phn_lists, max_score_elems: int = 1 << 24):
-                    return [seconds(f) for f in self.predict_frames_batch(list(phn_lists), bias, max_score_elems, style())]
+                def batch(phn_lists, max_score_elems: int = 1 << 24, speakers=None):
+                    phn_lists = list(phn_lists)
+                    tab, rows = speaker_args(speakers, len(phn_lists))
+                    if rows is None:
+                        return [seconds(f) for f in self.predict_frames_batch(phn_lists, bias, max_score_elems, style())]
+                    return [seconds(f) for f in self.predict_frames_batch(phn_lists, tab, max_score_elems, style(), None, rows)]
                 fn.batch = batch
-                return fn
+                return speaker_attrs(fn, lambda x: self.duration_fn(fs, hop_length, x).with_prompt(wav, cache))
 
             def fn(phns):
                 raise ValueError("the durations of a GST model depend on the prompt: use with_prompt(wav)(phns) or "
                                  "batch(phn_lists, prompts=[...])")
 
-            def batch(phn_lists, prompts=None, max_score_elems: int = 1 << 24):
-                """One list of seconds per phone list; prompts: one waveform per list (the same object may repeat)."""
+            def batch(phn_lists, prompts=None, max_score_elems: int = 1 << 24, speakers=None):
+                """One list of seconds per phone list; prompts: one waveform per list (the same object may repeat); speakers:
+                one x-vector per list, likewise."""
                 phn_lists = list(phn_lists)
                 if prompts is None or len(prompts) != len(phn_lists):
                     raise ValueError("a GST model needs prompts=[...], one prompt waveform per phone list")
+                tab, srows = speaker_args(speakers, len(phn_lists))
                 if not phn_lists:
                     return []
                 first = {}
@@ -733,17 +827,25 @@ class FS2DurationModel:
                 for w, r in zip(prompts, rows):
                     distinct[r] = w
                 style = self.style_embedding_batch(distinct)
-                return [seconds(f) for f in self.predict_frames_batch(phn_lists, bias, max_score_elems, style, rows)]
+                if srows is None:
+                    return [seconds(f) for f in self.predict_frames_batch(phn_lists, bias, max_score_elems, style, rows)]
+                return [seconds(f) for f in self.predict_frames_batch(phn_lists, tab, max_score_elems, style, rows, srows)]
             fn.needs_prompt = True
             fn.with_prompt = with_prompt
             fn.batch = batch
-            return fn
+            return speaker_attrs(fn, lambda x: self.duration_fn(fs, hop_length, x))
 
         def fn(phns):
             return seconds(self.predict_frames(list(phns), bias))
 
-        def batch(phn_lists, max_score_elems: int = 1 << 24):
-            """One list of seconds per phone list, from one predict_frames_batch call (one host synchronisation)."""
-            return [seconds(f) for f in self.predict_frames_batch(list(phn_lists), bias, max_score_elems)]
+        def batch(phn_lists, max_score_elems: int = 1 << 24, speakers=None):
+            """One list of seconds per phone list, from one predict_frames_batch call (one host synchronisation); speakers:
+            one x-vector per list (the same object may repeat)."""
+            phn_lists = list(phn_lists)
+            tab, rows = speaker_args(speakers, len(phn_lists))
+            if rows is None:
+                return [seconds(f) for f in self.predict_frames_batch(phn_lists, bias, max_score_elems)]
+            return [seconds(f) for f in self.predict_frames_batch(phn_lists, tab, max_score_elems, None, None, rows)]
         fn.batch = batch
-        return fn
+        return speaker_attrs(fn, lambda x: self.duration_fn(fs, hop_length, x))
+

@@ -376,10 +376,11 @@ class FS2TTSModel(FS2DurationModel):
         ops.duration_head(z, p[f"{pre}.{l}.ln.g"], p[f"{pre}.{l}.ln.b"], p[f"{pre}.lin.w"], p[f"{pre}.lin.b"], out,
                           ws.get("tts.unused", (M,), torch.int64), eps=1e-12, offset=0.0)
 
-    def _text_side(self, ids, B, T, lens, spk_bias, style, style_rows, pitch, energy, frames_out, offsets, frame_lens, alpha):
+    def _text_side(self, ids, B, T, lens, spk_bias, style, style_rows, pitch, energy, frames_out, offsets, frame_lens, alpha,
+                   spk_rows=None):
         """Encoder to length offsets of one chunk.  Returns hs [B*T][d] with the embeddings added (a workspace view)."""
         c, p = self.c, self.store.p
-        hs, _, frames = self._forward(ids, B, T, lens, spk_bias, style, style_rows)
+        hs, _, frames = self._forward(ids, B, T, lens, spk_bias, style, style_rows, spk_rows)
         tail = None
         if lens is not None:
             tail = lens
@@ -427,19 +428,32 @@ class FS2TTSModel(FS2DurationModel):
         return before, after, denorm
 
     def synthesize_ids_batch(self, id_lists, spembs=None, style=None, style_rows=None, alpha: float = 1.0,
-                             max_score_elems: int = 1 << 24) -> List[Dict[str, torch.Tensor]]:
+                             max_score_elems: int = 1 << 24, speakers=None) -> List[Dict[str, torch.Tensor]]:
         """The body of synthesize_batch on token ids (eos included): one dict of device tensors per list.
-        style (a GST model): [len(id_lists)][d], [1][d], or [S][d] with style_rows (a host list), as predict_frames_batch."""
+        style (a GST model): [len(id_lists)][d], [1][d], or [S][d] with style_rows (a host list), as predict_frames_batch.
+        speakers (instead of spembs): one x-vector per list; see synthesize_batch."""
         c = self.c
         lists = [[int(i) for i in ids] for ids in id_lists]
         if not lists:
             return []
         if not (float(alpha) > 0.0):
             raise ValueError(f"alpha {alpha!r} must be positive")
-        if spembs is None and c.spk_embed_dim > 0:
-            raise ValueError("this checkpoint needs spembs (its x-vector projection is part of inference)")
-        bias = self.speaker_bias(spembs) if spembs is not None else None
+        if spembs is not None and speakers is not None:
+            raise ValueError("give spembs (one x-vector for all lists) or speakers (one per list), not both")
         n = len(lists)
+        krow = None
+        if speakers is not None:
+            speakers = list(speakers)
+            if len(speakers) != n:
+                raise ValueError(f"speakers: {len(speakers)} x-vectors for {n} phone lists")
+            for i, x in enumerate(speakers):
+                if x is None:
+                    raise ValueError(f"speakers[{i}] is None: synthesis needs an x-vector for every list")
+            bias, krow = self.speaker_bias_table(speakers)
+        else:
+            if spembs is None and c.spk_embed_dim > 0:
+                raise ValueError("this checkpoint needs spembs (its x-vector projection is part of inference)")
+            bias = self.speaker_bias(spembs) if spembs is not None else None
         srow = None
         self._check_style(style, n, style_rows)
         if style is not None:
@@ -451,12 +465,13 @@ class FS2TTSModel(FS2DurationModel):
         if min(lengths) < 1 or max(lengths) > c.max_len:
             raise ValueError(f"token counts {min(lengths)}..{max(lengths)} outside 1..{c.max_len}")
         chunks = self._chunks(lengths, int(max_score_elems))
-        # staging (int64 words): per chunk its padded ids [B][Tmax]; then the lengths and the style rows as int32
+        # staging (int64 words): per chunk its padded ids [B][Tmax]; then the lengths and the style rows as int32 (with
+        # speakers: their table rows as int32 behind those)
         offs, n_ids = [], 0
         for ch in chunks:
             offs.append(n_ids)
             n_ids += len(ch) * lengths[ch[-1]]
-        total = n_ids + n
+        total = n_ids + n + (0 if krow is None else (n + 1) // 2)
         if self._stage_host is None or self._stage_host.numel() < total:
             cap = max(total, 2 * (self._stage_host.numel() if self._stage_host is not None else 0))
             self._stage_host = torch.zeros(cap, dtype=torch.int64, pin_memory=self.dev.type == "cuda")
@@ -471,6 +486,8 @@ class FS2TTSModel(FS2DurationModel):
                 blk[k, :lengths[i]] = lists[i]
                 hl[r + k] = lengths[i]
                 hl[n + r + k] = 0 if srow is None else srow[i]
+                if krow is not None:
+                    hl[2 * n + r + k] = krow[i]
             r += len(ch)
         # the pinned staging buffer is free again: the previous call's copy finished before its result reached the host
         self._stage_host[:total].copy_(torch.from_numpy(host))
@@ -489,13 +506,15 @@ class FS2TTSModel(FS2DurationModel):
             B, T = len(ch), lengths[ch[-1]]
             sl = slice(o, o + B * T)
             off = offsets[o + r:o + r + B * (T + 1)].view(B, T + 1)
-            if B == 1:
-                hs = self._text_side(dev[sl], 1, T, None, bias, None if style is None else style[srow[ch[0]]:srow[ch[0]] + 1],
+            if B == 1:      # (with speakers: this list's own table row is the one bias of the B = 1 path)
+                hs = self._text_side(dev[sl], 1, T, None, bias if krow is None else bias[krow[ch[0]]:krow[ch[0]] + 1],
+                                     None if style is None else style[srow[ch[0]]:srow[ch[0]] + 1],
                                      None, pitch[sl], energy[sl], down[sl], off, flens_dev[r:r + 1], alpha)
             else:
                 rows = None if style is None else dev_lens[n + r:n + r + B]
+                krows = None if krow is None else dev_lens[2 * n + r:2 * n + r + B]
                 hs = self._text_side(dev[sl].view(B, T), B, T, dev_lens[r:r + B], bias, style, rows, pitch[sl], energy[sl],
-                                     down[sl], off, flens_dev[r:r + B], alpha)
+                                     down[sl], off, flens_dev[r:r + B], alpha, krows)
             if hs_all is None:
                 hs_one = hs
             else:
@@ -559,7 +578,7 @@ class FS2TTSModel(FS2DurationModel):
         return style, rows
 
     def synthesize_batch(self, lists, spembs=None, prompts=None, alpha: float = 1.0, prompt_mels=None,
-                         max_score_elems: int = 1 << 24) -> List[Dict[str, torch.Tensor]]:
+                         max_score_elems: int = 1 << 24, speakers=None) -> List[Dict[str, torch.Tensor]]:
         """ESPnetTTSModel.inference(text, speech=prompt, spembs=, use_teacher_forcing=False, alpha=) for several phone lists:
         one dict per list, in the order given, of device tensors feat_gen [F][odim], feat_gen_denorm (a normalising checkpoint
         only), duration [T] int64 (eos entry included; as the reference, not scaled by alpha), pitch [T], energy [T], and
@@ -569,10 +588,16 @@ class FS2TTSModel(FS2DurationModel):
         parts).  Every row is computed as if alone.  One copy to the host per call -- the durations and frame counts, which
         size the decoder's buffers; the number of launches of a chunk does not depend on its rows.
         prompts (a GST model): one waveform per list, or one for all; prompt_mels: raw log-mels [F][n_mels] instead.
+        spembs: one x-vector behind all lists; speakers: one per list instead (the same object may repeat: one speaker bias per
+        distinct OBJECT, FS2DurationModel.speaker_bias_table) -- the rows follow the lists through the text-side chunks, and the
+        decoder does not read the x-vector.  Giving both is an error.
         A list whose durations sum to 0 frames raises ValueError (after the copy): there is nothing to decode."""
         lists = [list(ph) for ph in lists]
+        if spembs is not None and speakers is not None:
+            raise ValueError("give spembs (one x-vector for all lists) or speakers (one per list), not both")
         style, rows = self._styles(len(lists), prompts, prompt_mels) if lists else (None, None)
-        return self.synthesize_ids_batch([self.tokens_to_ids(ph) for ph in lists], spembs, style, rows, alpha, max_score_elems)
+        return self.synthesize_ids_batch([self.tokens_to_ids(ph) for ph in lists], spembs, style, rows, alpha, max_score_elems,
+                                         speakers)
 
     def synthesize(self, phns, spembs=None, prompt=None, alpha: float = 1.0, prompt_mel=None) -> Dict[str, torch.Tensor]:
         """synthesize_batch for one phone list: at its exact lengths, on the plain kernels."""
