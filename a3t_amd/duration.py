@@ -3,7 +3,7 @@
 The reference asks the user's own torch FastSpeech2 for them (espnet2/bin/sedit_inference.py:398-425 duration_predict,
 twice per edit with duration_adjust).  Only the part of FastSpeech2 that duration_predict runs is built here:
   - the text encoder (espnet/nets/pytorch_backend/conformer/encoder.py with an Embedding input layer): Embedding * sqrt(d)
-    (LegacyRelPositionalEncoding), the Conformer blocks of MLMEngine.block_fwd, after_norm;
+    (LegacyRelPositionalEncoding), the Conformer blocks of ConformerStack.block_fwd, after_norm;
   - the x-vector integration (espnet2/tts/fastspeech2/fastspeech2.py:784-808, "add" or "concat");
   - the DurationPredictor (espnet/nets/pytorch_backend/fastspeech/duration_predictor.py) in inference mode: k-tap convs
     with ReLU and LayerNorm, then a3t_duration_head (last LayerNorm, Linear(C -> 1), clamp(round(exp(x) - offset), 0)).
@@ -31,8 +31,9 @@ import torch
 from . import ops
 from ._lib import ACT_NONE, ACT_RELU, F32
 from .config import A3TConfig
-from .engine import MLMEngine, Workspace, score_chunks
+from .conformer import ConformerStack, score_chunks
 from .params import ParamStore, _block_layout, _ref_block_map
+from .schedule import _RowWorkspace
 
 # FastSpeech2.__init__ defaults (espnet2/tts/fastspeech2/fastspeech2.py) of the keys the duration path reads
 _FS2_DEFAULTS = dict(adim=384, aheads=4, elayers=6, eunits=1536, positionwise_layer_type="conv1d",
@@ -300,29 +301,6 @@ def load_into(store: ParamStore, c: FS2DurationConfig, sd) -> None:
         dst.copy_(src.reshape(dst.shape).to(device=store.device, dtype=torch.float32))
 
 
-class _RowWorkspace(Workspace):
-    """Workspace whose buffers keep their storage across sequence lengths: one grow-only allocation per (name, dtype),
-    viewed at the requested shape (the engine's Workspace would keep one buffer set per distinct length)."""
-
-    def __init__(self, device):
-        super().__init__(device)
-        self.shapes = {}
-
-    def get(self, name, shape, dtype=torch.float32, zero=False, zero_once=False):
-        shape = tuple(shape)
-        n, key = math.prod(shape), (name, dtype)
-        t = self.bufs.get(key)
-        if t is None or t.numel() < n:
-            t = torch.zeros(max(n, 1), dtype=dtype, device=self.device)
-            self.bufs[key] = t
-            self.shapes.pop(key, None)
-        v = t[:n].view(shape)
-        if zero or (zero_once and self.shapes.get(key) != shape):
-            v.zero_()
-        self.shapes[key] = shape
-        return v
-
-
 class FS2DurationModel:
     """The duration path of a conformer FastSpeech2 checkpoint on one device (fp32, eval mode)."""
 
@@ -330,9 +308,8 @@ class FS2DurationModel:
         self.c = cfg
         self.store = ParamStore(cfg, device, layout=param_layout(cfg), buffers=buffer_layout(cfg), keymap=key_map(cfg))
         self.dev = self.store.device
-        self.eng = MLMEngine(cfg, self.store, compute="f32", training=False)
-        self.eng.ws = _RowWorkspace(self.dev)
-        self.ws = self.eng.ws
+        self.eng = ConformerStack(cfg, self.store, compute="f32", training=False)
+        self.eng.ws = self.ws = _RowWorkspace(self.dev)
         self.token2id = {}
         for i, t in enumerate(cfg.token_list):
             self.token2id.setdefault(t, i)
@@ -549,7 +526,7 @@ class FS2DurationModel:
     def forward_ids_batch(self, ids, lens, spk_bias=None, style=None, style_rows=None, spk_rows=None):
         """ids: device int64 [B][Tmax] (eos included; entries behind a row's length: any valid id), lens: device int32 [B],
         1 <= lens[b] <= Tmax.  One padded forward whose row b is computed as forward_ids computes it alone at lens[b]
-        (MLMEngine.block_fwd with lens); one speaker bias [1][d] for the whole call, or with spk_rows (device int32 [B]) a table
+        (ConformerStack.block_fwd with lens); one speaker bias [1][d] for the whole call, or with spk_rows (device int32 [B]) a table
         [S][d] of which sequence b takes row spk_rows[b] (speaker_bias_table).  Returns device tensors (hs [B][Tmax][d],
         logd [B][Tmax], frames [B][Tmax] int64) valid until the next call; entries behind lens[b] are finite and mean nothing
         (hs is 0 there when the predictor's convs have more than one tap).

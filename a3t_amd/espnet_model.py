@@ -245,7 +245,7 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
     def _infill_rows_alone(self, batch, spans, host, max_score_elems):
         """inference_batch(rows="alone") behind the argument checks.  host: (frames, phones) per row as host lists, or None."""
         from . import ops
-        from .engine import score_chunks
+        from .conformer import score_chunks
         dev, eng = self.store.device, self._engine()
         speech = batch["speech"]
         B, Tm, odim = speech.shape

@@ -8,7 +8,7 @@ predictor; this module adds what follows it:
     Linear(C -> 1), on a3t_gemm, the ragged LayerNorm and a3t_duration_head, whose frames output is not used here);
   - their embeddings, Conv1d(1 -> d), added to the encoder output (a3t_fs2_variance_embed);
   - the length regulator (a3t_length_offsets, a3t_length_expand, which also applies the decoder entry's x * sqrt(d));
-  - the decoder's Conformer blocks on MLMEngine.block_fwd, after_norm, feat_out;
+  - the decoder's Conformer blocks on ConformerStack.block_fwd, after_norm, feat_out;
   - the postnet (k-tap convs without bias, BatchNorm1d in eval mode folded in fp64 into the conv weights and a shift at
     load, tanh in the GEMM's epilogue; the last layer without tanh);
   - feat_gen = before + postnet(before) and, for a checkpoint with normalize: global_mvn, feat_gen_denorm (a3t_fs2_finish).
@@ -26,13 +26,14 @@ import torch
 
 from . import ops
 from ._lib import ACT_NONE, ACT_RELU, ACT_TANH, F32
-from .duration import FS2DurationConfig, FS2DurationModel, _RowWorkspace
+from .conformer import ConformerStack
+from .duration import FS2DurationConfig, FS2DurationModel
 from .duration import buffer_layout as _dur_buffer_layout
 from .duration import key_map as _dur_key_map
 from .duration import load_into as _dur_load_into
 from .duration import param_layout as _dur_param_layout
-from .engine import MLMEngine
 from .params import ParamStore, _block_layout, _ref_block_map
+from .schedule import _RowWorkspace
 
 # FastSpeech2.__init__ defaults of the keys the synthesis path reads beyond duration.py's
 _TTS_DEFAULTS = dict(dlayers=6, dunits=1536, postnet_layers=5, postnet_chans=512, postnet_filts=5, use_batch_norm=True,
@@ -253,10 +254,9 @@ class FS2TTSModel(FS2DurationModel):
         self.c = cfg
         self.store = ParamStore(cfg, device, layout=param_layout(cfg), buffers=buffer_layout(cfg), keymap=key_map(cfg))
         self.dev = self.store.device
-        self.eng = MLMEngine(cfg, self.store, compute="f32", training=False)
-        self.eng.ws = _RowWorkspace(self.dev)
-        self.ws = self.eng.ws
-        self.eng_dec = MLMEngine(cfg.decoder_config(), self.store, compute="f32", training=False)
+        self.eng = ConformerStack(cfg, self.store, compute="f32", training=False)
+        self.eng.ws = self.ws = _RowWorkspace(self.dev)
+        self.eng_dec = ConformerStack(cfg.decoder_config(), self.store, compute="f32", training=False)
         self.eng_dec.ws = self.ws
         self.token2id = {}
         for i, t in enumerate(cfg.token_list):

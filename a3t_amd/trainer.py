@@ -88,7 +88,7 @@ class FlatAllReduce:
         self.ranges = ranges
         self.cuda = flat_grad.is_cuda
         if self.cuda:
-            from .engine import shared_stream
+            from .schedule import shared_stream
             self.stream = shared_stream(flat_grad.device, "allreduce")
         else:
             self.stream = None
@@ -166,7 +166,7 @@ class A3TTrainer:
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         self._main = None
         if dev.type == "cuda":
-            from .engine import shared_stream
+            from .schedule import shared_stream
             self._main = shared_stream(dev, "main", high=True)
         self.reducer = None
         if self.world > 1 or (force_reducer and dist.is_available() and dist.is_initialized()):

@@ -256,7 +256,7 @@ def test_engine_training_step_with_the_fused_forward_matches_the_materialised_st
         store = ParamStore(c, DEV)
         store.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in state.items()})
         eng = MLMEngine(c, store, compute="bf16", training=True, dropout=dropout)
-        assert eng.fused_attn_train == (fused == "1") and eng.attn_bwd_ds == (bwd_ds == "1")
+        assert eng.fused_attn_train == (fused == "1") and eng.opt.attn_bwd_ds == (bwd_ds == "1")
         loss = float(eng.forward(batch)["loss"])
         assert sum(k.endswith(".rs") for k in eng.sv) == (3 if fused == "1" else 0)
         store.zero_grad()
@@ -704,7 +704,7 @@ def test_engine_step_with_one_saved_probability_tensor_matches_the_two_tensor_st
         store = ParamStore(c, DEV)
         store.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in state.items()})
         eng = MLMEngine(c, store, compute="bf16", training=True, dropout=True)
-        assert eng.attn_signed == (sg == "1")
+        assert eng.opt.attn_signed == (sg == "1")
         loss = float(eng.forward(batch)["loss"])
         n_pdrop = sum(1 for k, v in eng.sv.items() if isinstance(v, tuple) and len(v) == 9 and v[8] is not None)
         assert n_pdrop == (0 if sg == "1" else 3), n_pdrop

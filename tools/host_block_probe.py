@@ -4,7 +4,7 @@ import sys, os, time, collections
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
-from a3t_amd import ops, engine as E
+from a3t_amd import ops, schedule as E
 from a3t_amd.collate import synthetic_batch
 from a3t_amd.config import config_c2
 dev = torch.device("cuda", 0)
