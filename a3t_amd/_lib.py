@@ -110,6 +110,8 @@ _SIGS = {
     "a3t_relpos_softmax_fwd_ragged": [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_float,
                                       _P],
     "a3t_splice_spans": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
+    "a3t_splice_spans_multi": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
+    "a3t_gather_windows": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_pwg_block_ragged": [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_pwg_block_f16": [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_cast_f16_sat": [_P, _P, c_int64, _P],

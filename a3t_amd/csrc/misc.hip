@@ -747,6 +747,87 @@ extern "C" int a3t_splice_spans(const float* after, const float* speech, const u
                        out, lens, Tin, Tout, C);
     return (int)hipGetLastError();
 }
+// a3t_splice_spans with a list of spans per row: frame t of row b takes `after` iff it lies in one of the row's first
+// nspans[b] (clamped to [0, S]) spans [s, e).  V = float4 moves 16 bytes per lane (C % 4 == 0, Cv = C / 4: a lane's four
+// channels lie in one frame), V = float is the scalar path (Cv = C).  Same mask count and lens write as splice_spans_kernel.
+template <typename V>
+__global__ __launch_bounds__(256) void splice_spans_multi_kernel(const V* __restrict__ after, const V* __restrict__ speech,
+                                                                 const uint8_t* __restrict__ mask,
+                                                                 const int32_t* __restrict__ spans,
+                                                                 const int32_t* __restrict__ nspans, V* __restrict__ out,
+                                                                 int32_t* __restrict__ lens, int Tin, int Tout, int Cv, int S) {
+    __shared__ int cnt[4];
+    const int b = blockIdx.y;
+    int n = 0;
+    for (int t = threadIdx.x; t < Tin; t += 256) n += mask[(int64_t)b * Tin + t] ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o, 64);
+    if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = n;
+    __syncthreads();
+    const int L = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    if (blockIdx.x == 0 && threadIdx.x == 0) lens[b] = L;
+    const int K = min(max(nspans[b], 0), S);
+    const int32_t* sp = spans + (int64_t)b * S * 2;
+    const int64_t m = (int64_t)Tout * Cv;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) {
+        const int t = (int)(i / Cv), c = (int)(i - (int64_t)t * Cv);
+        V v = V();
+        if (t < L && t < Tin) {
+            bool in = false;
+            for (int k = 0; k < K; ++k) in = in || (t >= sp[2 * k] && t < sp[2 * k + 1]);
+            const int64_t j = ((int64_t)b * Tin + t) * Cv + c;
+            v = in ? after[j] : speech[j];
+        }
+        out[(int64_t)b * m + i] = v;
+    }
+}
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+extern "C" int a3t_splice_spans_multi(const float* after, const float* speech, const uint8_t* speech_mask, const int32_t* spans,
+                                      const int32_t* nspans, float* out, int32_t* lens, int B, int Tin, int Tout, int C, int S,
+                                      void* stream) {
+    if (B <= 0 || B > 65535 || Tin <= 0 || Tout <= 0 || C <= 0 || S <= 0) return A3T_EINVAL;
+    if (C % 4 == 0 && aligned16(after) && aligned16(speech) && aligned16(out)) {
+        const int gx = nblocks((int64_t)Tout * (C / 4), 64);
+        hipLaunchKernelGGL(splice_spans_multi_kernel<float4>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream,
+                           (const float4*)after, (const float4*)speech, speech_mask, spans, nspans, (float4*)out, lens, Tin, Tout,
+                           C / 4, S);
+    } else {
+        const int gx = nblocks((int64_t)Tout * C, 64);
+        hipLaunchKernelGGL(splice_spans_multi_kernel<float>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, after, speech,
+                           speech_mask, spans, nspans, out, lens, Tin, Tout, C, S);
+    }
+    return (int)hipGetLastError();
+}
+// Window gather (the vocoder's ragged rows of the speech editor): dst[r][w] = src[row_r][first_r + w] for w < frames_r, 0
+// behind, table[r] = {row_r, first_r, frames_r}; the caller vouches for 0 <= row_r < B (ops.gather_windows checks its host
+// table).  A frame outside the source row's T frames and a row below 0 are stored as 0, never read.
+template <typename V>
+__global__ __launch_bounds__(256) void gather_windows_kernel(const V* __restrict__ src, const int32_t* __restrict__ table,
+                                                             V* __restrict__ dst, int T, int Wmax, int Cv) {
+    const int r = blockIdx.y;
+    const int row = table[3 * r], first = table[3 * r + 1], frames = min(table[3 * r + 2], Wmax);
+    const int64_t m = (int64_t)Wmax * Cv;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) {
+        const int w = (int)(i / Cv), c = (int)(i - (int64_t)w * Cv);
+        const int64_t t = (int64_t)first + w;
+        V v = V();
+        if (w < frames && row >= 0 && t >= 0 && t < T) v = src[((int64_t)row * T + t) * Cv + c];
+        dst[(int64_t)r * m + i] = v;
+    }
+}
+extern "C" int a3t_gather_windows(const float* src, const int32_t* table, float* dst, int R, int T, int Wmax, int C,
+                                  void* stream) {
+    if (R <= 0 || R > 65535 || T <= 0 || Wmax <= 0 || C <= 0) return A3T_EINVAL;
+    if (C % 4 == 0 && aligned16(src) && aligned16(dst)) {
+        const int gx = nblocks((int64_t)Wmax * (C / 4), 64);
+        hipLaunchKernelGGL(gather_windows_kernel<float4>, dim3(gx, R), dim3(256), 0, (hipStream_t)stream, (const float4*)src,
+                           table, (float4*)dst, T, Wmax, C / 4);
+    } else {
+        const int gx = nblocks((int64_t)Wmax * C, 64);
+        hipLaunchKernelGGL(gather_windows_kernel<float>, dim3(gx, R), dim3(256), 0, (hipStream_t)stream, src, table, dst, T, Wmax,
+                           C);
+    }
+    return (int)hipGetLastError();
+}
 __global__ void bias_act_kernel(float* x, const float* bias, int64_t n, int C, int act, float scale) {
     GRID_STRIDE(i, n) {
         float v = x[i] * scale;

@@ -195,11 +195,16 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
 
     def inference_batch(self, speech, text, masked_position, speech_mask, text_mask, speech_segment_pos, text_segment_pos,
                         span_boundary, spembs=None, use_teacher_forcing: bool = True, rows: str = "batch",
-                        max_score_elems: int = 1 << 24):
+                        max_score_elems: int = 1 << 24, span_counts=None):
         """Teacher-forced infill of a whole batch: one forward-only pass, then a3t_splice_spans writes, per row b,
         out[b][t] = after[b][t] for span_boundary[b][0] <= t < span_boundary[b][1], speech[b][t] for the other valid frames
         and 0 behind the row's length speech_mask[b].sum() (the batch's speech_lengths are raw samples, as in the reference).
         Returns (out (B, Tmax, odim) fp32, lengths (B,) int32), both on the device.
+
+        span_boundary: (B, 2), one span per row, as above; or several spans per row -- a list of per-row lists of [s, e]
+        (a row may have none), or a (B, S, 2) tensor with span_counts (B,), how many of a row's S entries count.  Frame t of
+        row b then takes after[b][t] iff it lies in any of the row's spans (a3t_splice_spans_multi); rows="alone" carries
+        the lists through its chunks.
 
         rows="batch" (the default): a row is what the reference's collate function and model give for that row IN that batch.
         That is not the same request run alone, in the reference either: the convolution module and the FFN convolutions do not
@@ -212,15 +217,12 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
         score-sized tensors of the materialised attention); a chunk of one row takes the plain B = 1 pass at the row's exact
         lengths.  The device lengths come from the masks without a host synchronisation; the chunking needs them on the host,
         which is free when the masks arrive as host tensors and is skipped when the padded batch fits the cap as it is."""
-        from . import ops
         if not use_teacher_forcing:
             raise NotImplementedError("only use_teacher_forcing=True is functional in the reference")
         if rows not in ("batch", "alone"):
             raise ValueError(f"rows must be 'batch' or 'alone', got {rows!r}")
         B, Tmax = speech.shape[0], speech.shape[1]
-        sb = span_boundary if torch.is_tensor(span_boundary) else torch.tensor([[int(s), int(e)] for s, e in span_boundary])
-        if sb.shape != (B, 2):
-            raise ValueError(f"span_boundary must be (B, 2) = ({B}, 2), got {tuple(sb.shape)}")
+        sb, nsp = self._span_arguments(span_boundary, span_counts, B)
         if rows == "alone":
             if self.compute != "f32" or self.training:
                 raise ValueError(f"rows='alone' needs a model built with compute='f32' in eval mode (compute={self.compute!r}, "
@@ -231,20 +233,62 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
         batch = self._batch(speech, text, masked_position, speech_mask, text_mask, speech_segment_pos, text_segment_pos, spembs)
         dev = self.store.device
         spans = sb.to(torch.int32).contiguous().to(dev, non_blocking=True)
+        if nsp is not None:
+            nsp = nsp.to(torch.int32).contiguous().to(dev, non_blocking=True)
         if rows == "alone":
-            return self._infill_rows_alone(batch, spans, host, int(max_score_elems))
+            return self._infill_rows_alone(batch, spans, host, int(max_score_elems), nsp)
         out = self._engine().forward(batch, need_grad=False)
         sp = batch["speech"].contiguous()                     # (bf16 mode may have extended the padding)
         res = torch.empty(B, Tmax, sp.shape[2], dtype=torch.float32, device=dev)
         lens = torch.empty(B, dtype=torch.int32, device=dev)
-        ops.splice_spans(out["after"].contiguous(), sp, batch["speech_mask"].contiguous().view(B, -1), spans, res, lens)
+        self._splice(out["after"].contiguous(), sp, batch["speech_mask"].contiguous().view(B, -1), spans, nsp, res, lens)
         return res, lens
+
+    @staticmethod
+    def _span_arguments(span_boundary, span_counts, B):
+        """inference_batch's span_boundary -> (spans, counts): ((B, 2), None) for one span per row, ((B, S, 2), (B,)) for span
+        lists.  A list whose rows are lists of [s, e] pairs (or empty) is a list of span lists."""
+        if torch.is_tensor(span_boundary):
+            sb = span_boundary
+            if sb.dim() == 3:
+                if sb.shape[0] != B or sb.shape[1] < 1 or sb.shape[2] != 2 or span_counts is None:
+                    raise ValueError(f"span_boundary (B, S, 2) = ({B}, S >= 1, 2) comes with span_counts (B,), got "
+                                     f"{tuple(sb.shape)} and span_counts={span_counts!r}")
+                nsp = span_counts if torch.is_tensor(span_counts) else torch.tensor([int(n) for n in span_counts])
+                if nsp.numel() != B:
+                    raise ValueError(f"span_counts must be (B,) = ({B},), got {tuple(nsp.shape)}")
+                return sb, nsp.reshape(B)
+        else:
+            rows_ = list(span_boundary)
+            if any(len(r) == 0 or not isinstance(r[0], (int, float)) and hasattr(r[0], "__len__") for r in rows_):
+                if len(rows_) != B:
+                    raise ValueError(f"span_boundary: {len(rows_)} span lists for {B} rows")
+                S = max(1, max(len(r) for r in rows_))
+                sb = torch.zeros(B, S, 2, dtype=torch.int32)
+                for b, r in enumerate(rows_):
+                    for k, (s, e) in enumerate(r):
+                        sb[b, k, 0], sb[b, k, 1] = int(s), int(e)
+                return sb, torch.tensor([len(r) for r in rows_], dtype=torch.int32)
+            sb = torch.tensor([[int(s), int(e)] for s, e in rows_])
+        if span_counts is not None:
+            raise ValueError("span_counts belongs to a (B, S, 2) span_boundary")
+        if sb.shape != (B, 2):
+            raise ValueError(f"span_boundary must be (B, 2) = ({B}, 2), got {tuple(sb.shape)}")
+        return sb, None
+
+    @staticmethod
+    def _splice(after, speech, mask, spans, nsp, out, lens):
+        from . import ops
+        if nsp is None:
+            ops.splice_spans(after, speech, mask, spans, out, lens)
+        else:
+            ops.splice_spans_multi(after, speech, mask, spans, nsp, out, lens)
 
     _ROW_KEYS = ("speech", "masked_position", "speech_mask", "speech_segment_pos")      # [B][T_mel]..., the rest [B][T_phn]...
 
-    def _infill_rows_alone(self, batch, spans, host, max_score_elems):
-        """inference_batch(rows="alone") behind the argument checks.  host: (frames, phones) per row as host lists, or None."""
-        from . import ops
+    def _infill_rows_alone(self, batch, spans, host, max_score_elems, nsp=None):
+        """inference_batch(rows="alone") behind the argument checks.  host: (frames, phones) per row as host lists, or None;
+        nsp: the rows' span counts when spans is (B, S, 2), None for (B, 2)."""
         from .conformer import score_chunks
         dev, eng = self.store.device, self._engine()
         speech = batch["speech"]
@@ -256,10 +300,10 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
         res = torch.empty(B, Tm, odim, dtype=torch.float32, device=dev)
         lens = torch.empty(B, dtype=torch.int32, device=dev)
 
-        def run(sub, sp, lp, out_rows, out_lens):
+        def run(sub, sp, lp, out_rows, out_lens, cnt=nsp):
             out = eng.forward(sub, need_grad=False, lens=lp)
-            ops.splice_spans(out["after"].contiguous(), sub["speech"].contiguous(), sub["speech_mask"].contiguous(), sp,
-                             out_rows, out_lens)
+            self._splice(out["after"].contiguous(), sub["speech"].contiguous(), sub["speech_mask"].contiguous(), sp, cnt,
+                         out_rows, out_lens)
 
         if B > 1 and host is None and B * self.cfg.heads * (Tm + Tp) ** 2 <= max_score_elems:
             # one chunk as the batch stands: nobody needs the lengths on the host
@@ -280,7 +324,7 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
             ln = torch.empty(len(ch), dtype=torch.int32, device=dev)
             # a chunk of one row: the plain B = 1 pass at the row's exact lengths
             lp = None if len(ch) == 1 else (slens.index_select(0, idx), tlens.index_select(0, idx))
-            run(sub, spans.index_select(0, idx).contiguous(), lp, r, ln)
+            run(sub, spans.index_select(0, idx).contiguous(), lp, r, ln, None if nsp is None else nsp.index_select(0, idx))
             res.index_copy_(0, idx, r)
             lens.index_copy_(0, idx, ln)
         return res, lens

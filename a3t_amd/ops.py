@@ -913,6 +913,45 @@ def splice_spans(after, speech, speech_mask, spans, out, lens):
                                       _ptr(_i32(lens, "lens")), B, Tin, out.shape[1], C, _stream()), "splice_spans")
 
 
+def splice_spans_multi(after, speech, speech_mask, spans, nspans, out, lens):
+    """splice_spans with a list of spans per row: spans [B][S][2] int32, nspans [B] int32 (device); frame t of row b takes
+    after[b][t] iff it lies in one of the row's first nspans[b] spans (a3t_splice_spans_multi)."""
+    B, Tin, C = speech.shape
+    if after.shape != speech.shape or speech_mask.numel() != B * Tin or spans.dim() != 3 or spans.shape[0] != B \
+            or spans.shape[1] < 1 or spans.shape[2] != 2 or nspans.numel() != B or out.dim() != 3 or out.shape[0] != B \
+            or out.shape[2] != C or lens.numel() != B:
+        raise ValueError("splice_spans_multi: shapes do not fit")
+    for t in (after, speech, speech_mask, out):
+        if not t.is_contiguous():
+            raise ValueError("splice_spans_multi: tensors must be contiguous")
+    if after.dtype != torch.float32 or speech.dtype != torch.float32 or out.dtype != torch.float32 \
+            or speech_mask.element_size() != 1:
+        raise TypeError("splice_spans_multi: after / speech / out fp32, speech_mask one byte per frame")
+    L.check(L.load().a3t_splice_spans_multi(_ptr(after), _ptr(speech), _ptr(speech_mask), _ptr(_i32(spans, "spans")),
+                                            _ptr(_i32(nspans, "nspans")), _ptr(out), _ptr(_i32(lens, "lens")), B, Tin,
+                                            out.shape[1], C, spans.shape[1], _stream()), "splice_spans_multi")
+
+
+def gather_windows(src, table, dst):
+    """dst [R][Wmax][C] row r = src[row, first:first + frames] with zeros behind, table [R][3] = {row, first frame, frames}
+    (a3t_gather_windows).  src [B][T][C] fp32 on the device; `table` is a HOST array of integers: it is checked against the
+    shapes here (0 <= row < B, 0 <= first, first + frames <= T, 0 <= frames <= Wmax), then copied to the device."""
+    import numpy as np
+    tab = np.ascontiguousarray(np.asarray(table, dtype=np.int64).reshape(-1, 3))
+    if src.dim() != 3 or dst.dim() != 3 or dst.shape[0] != tab.shape[0] or dst.shape[2] != src.shape[2] or tab.shape[0] < 1:
+        raise ValueError("gather_windows: shapes do not fit")
+    B, T, C = src.shape
+    R, Wmax = dst.shape[0], dst.shape[1]
+    if not src.is_contiguous() or not dst.is_contiguous() or src.dtype != torch.float32 or dst.dtype != torch.float32:
+        raise ValueError("gather_windows: src and dst must be contiguous fp32")
+    row, first, frames = tab[:, 0], tab[:, 1], tab[:, 2]
+    if (row < 0).any() or (row >= B).any() or (first < 0).any() or (frames < 0).any() or (first + frames > T).any() \
+            or (frames > Wmax).any():
+        raise ValueError(f"gather_windows: a window of {tab.tolist()} leaves src {tuple(src.shape)} or dst {tuple(dst.shape)}")
+    dev_tab = torch.from_numpy(tab.astype(np.int32)).to(src.device, non_blocking=True)
+    L.check(L.load().a3t_gather_windows(_ptr(src), _ptr(dev_tab), _ptr(dst), R, T, Wmax, C, _stream()), "gather_windows")
+
+
 def bias_act(x, bias, act, scale_=1.0):
     M, C = x.shape
     L.check(L.load().a3t_bias_act(_ptr(x), _ptr(bias), M, C, act, scale_, _stream()), "bias_act")

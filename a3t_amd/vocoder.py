@@ -45,6 +45,19 @@ def span_window(n0: int, n1: int, T: int, margin: int):
     return max(0, n0 - margin), min(T, max(n1, n0) + margin)
 
 
+def span_windows(spans: Sequence[Sequence[int]], T: int, margin: int):
+    """span_window per span of [[n0, n1], ...] (left to right), windows that touch or overlap merged into one: the frame
+    windows to vocode so that every span's samples come out as in a run over the whole utterance."""
+    wins = []
+    for n0, n1 in spans:
+        w0, w1 = span_window(n0, n1, T, margin)
+        if wins and w0 <= wins[-1][1]:
+            wins[-1] = (min(wins[-1][0], w0), max(wins[-1][1], w1))
+        else:
+            wins.append((w0, w1))
+    return wins
+
+
 def pwg_tile_list(lengths: Sequence[int], hop: int, tile: int = 256) -> np.ndarray:
     """The work list of a3t_pwg_block_ragged: int32 [ntiles][4] = {row b, first sample t0, valid samples W_b = lengths[b] * hop,
     0}, one entry per `tile`-sample tile that holds a valid sample, rows in order."""

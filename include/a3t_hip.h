@@ -430,6 +430,17 @@ int a3t_relpos_softmax_fwd_ragged(const void* ac, const void* bd, int scores_dty
  * [B][Tin][C] fp32, spans [B][2] int32. */
 int a3t_splice_spans(const float* after, const float* speech, const uint8_t* speech_mask, const int32_t* spans, float* out,
                      int32_t* lens, int B, int Tin, int Tout, int C, void* stream);
+/* a3t_splice_spans with several spans per row (an edit of separate places of one utterance): spans [B][S][2] int32, nspans
+ * [B] int32; frame t of row b takes after[b][t] iff it lies in one of the row's first nspans[b] spans [s, e) (nspans is
+ * clamped to [0, S]; entries behind it are not read as spans), every other rule as above.  16 bytes per lane when C % 4 == 0
+ * and the three float pointers are 16-byte aligned, one float per lane otherwise. */
+int a3t_splice_spans_multi(const float* after, const float* speech, const uint8_t* speech_mask, const int32_t* spans,
+                           const int32_t* nspans, float* out, int32_t* lens, int B, int Tin, int Tout, int C, int S,
+                           void* stream);
+/* Window gather: dst [R][Wmax][C] row r = src[row][first .. first + frames) with zeros behind, table [R][3] int32 = {row,
+ * first frame, frames} (frames is clamped to Wmax).  src [B][T][C] fp32; the caller guarantees 0 <= row < B, a frame outside
+ * [0, T) is written as 0 and not read.  Same two paths as a3t_splice_spans_multi. */
+int a3t_gather_windows(const float* src, const int32_t* table, float* dst, int R, int T, int Wmax, int C, void* stream);
 
 /* FastSpeech2 duration head (fastspeech/duration_predictor.py:77-95, inference): per row of z [M][C] -- the last predictor
  * conv after its bias and ReLU -- LayerNorm over C (eps, biased variance), x = LN(z) . w + bias[0] (Linear(C -> 1); bias

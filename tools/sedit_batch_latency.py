@@ -27,8 +27,18 @@ model would cost.
           B's and of C's mel to A's (the request edited alone), relative to the scale max(1, max |mel|), and of the collated
           log-mels.  --compute is not read for these legs.
 
+  --spans: two separate edits in one pass (MultiSpanEditRequest.max_spans), keys `<model>.<compute>.spans.n<N>`.  Every request changes
+          two words with three kept words (>= 40 frames) between them, the new words from a dictionary of the tool's own so that
+          the word diff has exactly these two runs.  A = edit_batch with max_spans=1 (one span over the hull: the kept words are
+          regenerated), B = edit_batch with max_spans=2, C = two sequential passes, one word each (the second pass edits the
+          first one's "orgin_replaced"; its transcript and alignment are prepared ahead, outside the timing: an aligner run on
+          the intermediate audio is not counted).  Order A, B, C, A, full and span-only vocoding, median of --calls, ms per
+          request, and the frames the vocoder was given per request.  `kept_mel_B_to_A`: over the kept middle words B returns
+          the recording's mel and A the model's output -- max and RMS of the difference relative to max(1, max |mel|), frame by
+          frame from the start of the kept run over the shorter of the two runs.
+
     python tools/sedit_batch_latency.py [--models c2] [--compute bf16 f32] [--n 1 4 8] [--calls 50] [--warmup 5] [--kernel]
-                                        [--vocoder-compute f32 f16] [--rows batch alone]
+                                        [--vocoder-compute f32 f16] [--rows batch alone] [--spans]
 """
 import argparse
 import json
@@ -283,6 +293,93 @@ def rows_alone_legs(ed, oc, reqs, calls, warmup):
     return r
 
 
+SPAN_LEX = {"ZEBRA": ["Z", "IY1", "B"], "PLUM": ["P", "L", "AH1"]}      # in no prompt: the word diff is the two swaps
+
+
+def two_edit_requests(frames, oc, seed, duration_fn, token_id_fn):
+    """A `frames`-frame utterance of three-phone words with word i -> ZEBRA and word i + 4 -> PLUM (three kept words between
+    them).  Returns (both edits with max_spans=1, the same with max_spans=2, the first word's edit alone, a function
+    intermediate audio -> the second word's edit)."""
+    from dataclasses import replace
+    from a3t_amd.sedit import EditRequest, MultiSpanEditRequest, plan_batch
+    words = max(9, frames // 17)
+    wav, times2, w2p, old_str, _ = prompt(words, frames, oc.fs, oc.hop_length, seed=seed)
+    old = old_str.split()
+    i = (words - 5) // 2
+
+    def swapped(base, swaps):
+        new = [swaps.get(k, w) for k, w in enumerate(base)]
+        table = [(w.upper(), SPAN_LEX.get(w.upper()) or LEX[w.upper()]) for w in new]
+        return ([ph for _, phs in table for ph in phs], {f"{k}_{w}": list(phs) for k, (w, phs) in enumerate(table)}, " ".join(new))
+
+    phns, nw2p, new_str = swapped(old, {i: "zebra", i + 4: "plum"})
+    hull = MultiSpanEditRequest(wav, times2, w2p, phns, nw2p, old_str, new_str)
+    phns1, nw2p1, mid_str = swapped(old, {i: "zebra"})
+    first = EditRequest(wav, times2, w2p, phns1, nw2p1, old_str, mid_str)
+    # the second pass: the first pass's plan is its aligner output (prepared once; the audio is swapped in per call)
+    plan = plan_batch([first], oc.fs, oc.hop_length, duration_fn, token_id_fn)[0][0]
+    t2 = [[ph, s, e] for ph, s, e in zip(plan.phns, plan.align_start, plan.align_end)]
+    w2p2 = {k: " ".join(v) for k, v in nw2p1.items()}
+    phns2, nw2p2, _ = swapped(mid_str.split(), {i + 4: "plum"})
+    second = EditRequest(plan.wav, t2, w2p2, phns2, nw2p2, mid_str, new_str)
+    return hull, replace(hull, max_spans=2), first, lambda audio: replace(second, wav_org=audio)
+
+
+class _CountingVocoder:
+    """Passes through to the generator and adds up the frames it is given."""
+
+    def __init__(self, voc):
+        self.voc, self.frames = voc, 0
+        self.margin_frames = voc.margin_frames
+
+    def __call__(self, feat):
+        return self.voc(feat)
+
+    def inference(self, c, z=None, normalize_before=False, lengths=None):
+        self.frames += int(sum(lengths)) if lengths is not None else int(c.shape[0] * c.shape[1] if c.dim() == 3 else c.shape[0])
+        return self.voc.inference(c, z, normalize_before, lengths=lengths)
+
+
+def spans_legs(ed, oc, frames_list, calls, warmup):
+    """A, B, C, A of --spans on len(frames_list) requests; ms per request, vocoded frames per request, mel distance."""
+    n = len(frames_list)
+    sets = [two_edit_requests(int(f), oc, 100 + 7 * i, ed.duration_fn, ed.token_id_fn) for i, f in enumerate(frames_list)]
+    hull, multi, first, second = ([s[k] for s in sets] for k in range(4))
+    ed.vocoder = voc = _CountingVocoder(ed.vocoder)
+    r = {}
+
+    def two_passes(outputs):
+        one = ed.edit_batch(first, outputs=outputs)
+        return ed.edit_batch([mk(o["orgin_replaced"]) for mk, o in zip(second, one)], outputs=outputs)
+
+    for name, outputs in (("full", ("prediction", "orgin_replaced")), ("span_only", ("orgin_replaced",))):
+        fns = {"A_hull": lambda: ed.edit_batch(hull, outputs=outputs), "B_max_spans_2": lambda: ed.edit_batch(multi, outputs=outputs),
+               "C_two_passes": lambda: two_passes(outputs)}
+        for key in ("A_hull", "B_max_spans_2", "C_two_passes", "A_hull"):
+            tag = f"{name}.{key}" + ("_again" if f"{name}.{key}_ms" in r else "")
+            r[f"{tag}_ms"] = round(timed(fns[key], calls, warmup) / n, 3)
+            voc.frames = 0
+            fns[key]()
+            r[f"{tag}_vocoded_frames"] = round(voc.frames / n, 1)
+    ed.vocoder = None
+    a, b = ed.edit_batch(hull), ed.edit_batch(multi)
+    ed.vocoder = voc.voc
+    r["frames"] = [int(g["feat"].shape[0]) for g in b]
+    r["spans_B"] = [g["new_spans"] for g in b]
+    r["span_A"] = [g["new_span_boundary"] for g in a]
+    r["kept_frames_between"] = [int(g["old_spans"][-1][0] - g["old_spans"][0][1]) for g in b]
+    dmax, drms = [], []
+    for ga, gb in zip(a, b):
+        k0, k1 = gb["new_spans"][0][1], gb["new_spans"][1][0]
+        m = min(k1, ga["new_span_boundary"][1], ga["feat"].shape[0]) - k0
+        x, y = gb["feat"][k0:k0 + m].double(), ga["feat"][k0:k0 + m].double()
+        scale = max(1.0, float(x.abs().max()))
+        dmax.append(float(f"{float((x - y).abs().max()) / scale:.3e}"))
+        drms.append(float(f"{float((x - y).pow(2).mean().sqrt()) / scale:.3e}"))
+    r["kept_mel_B_to_A"] = dict(max_of_scale=dmax, rms_of_scale=drms)
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", nargs="*", default=["c2"])      # (none given: the --kernel leg alone)
@@ -294,6 +391,7 @@ def main():
     ap.add_argument("--kernel", action="store_true")
     ap.add_argument("--vocoder-compute", nargs="+", default=["f32"], choices=["f32", "f16"])
     ap.add_argument("--rows", nargs="+", default=["batch"], choices=["batch", "alone"])
+    ap.add_argument("--spans", action="store_true")
     a = ap.parse_args()
     prop = torch.cuda.get_device_properties(0)
     out = {"device": f"{prop.name} ({getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs)"}
@@ -304,6 +402,18 @@ def main():
         if "f16" in a.vocoder_compute:
             out["pwg_blocks_f16"] = kernel_bench_f16(1000, sets, a.calls)
             print(json.dumps({"pwg_blocks_f16": out["pwg_blocks_f16"]}), flush=True)
+    if a.spans:
+        for which in a.models:
+            for compute in a.compute:
+                ed, oc = editor(which, compute)
+                for n in a.n:
+                    lo, hi = a.frames_range
+                    frames = np.linspace(hi, lo, n).astype(int) if n > 1 else [(lo + hi) // 2]
+                    key = f"{which}.{compute}.spans.n{n}"
+                    out[key] = spans_legs(ed, oc, frames, a.calls, a.warmup)
+                    print(json.dumps({key: out[key]}), flush=True)
+        print(json.dumps({"sedit_batch_latency": out}))
+        return
     if "alone" in a.rows:
         for which in a.models:
             ed, oc = editor(which, "f32")
