@@ -1239,6 +1239,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_ds_kernel(DsArgs p) {
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             DSTAMP(3);
+            // a one-tile task: nobody has requested the NEXT task's first tile -- the task before this one looks two tiles ahead,
+            // which is this task's second tile and does not exist, and the prologue requests tiles of the first task only.  Its
+            // slot (gt + 1 = gt - 2 mod NRING) was left two barriers ago.  (Without this request a task that follows a one-tile
+            // task multiplied with whatever its first slot held: tests/test_gpu_attn_walk.py, one_tile / cross_5_1_*.)
+            if (more && c_nt == 1) A3T_DS_ISSUE_V(n_, 0, (gt + 1) % NRING);
             // two tiles ahead, into the slot every wave left before this barrier; past the end of the task: the next task's
             issued_prev = true;
             if (k + 2 < c_nt) A3T_DS_ISSUE_V(c_, k + 2, (gt + 2) % NRING);
@@ -1271,11 +1276,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_ds_kernel(DsArgs p) {
             }
             DSTAMP(4);
         }
-        // (a one-tile task leaves the next task's second V tile to be issued here; a barrier first: slot gt+1 may still be read)
-        if (more && c_nt == 1 && n_nt > 1) {
-            __syncthreads();
-            A3T_DS_ISSUE_V(n_, 1, (gt + 1) % NRING);
-        }
+        // (after a one-tile task the next task's second V tile needs no request of its own here: the tile loop above asked for it,
+        //  k + 2 - c_nt = 1, together with the first)
         // ---- the next task's inputs travel while this one's image leaves
         fetch_rows = n_bh != c_bh || n_q0 != c_q0;
         if (more) A3T_DS_FETCH(n_);
