@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("A3T_LIB_PATH") or os.path.join(HERE, "lib", "liba3t_hip.so")   # (override: instrumented builds of tools/)
 
 F32, BF16 = 0, 1
+BF16X3 = 2      # a3t_gemm_desc.compute only: fp32 storage, three bf16 MFMA products per fp32 product
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SWISH = 0, 1, 2, 3
 ACC_STORE, ACC_ADD, ACC_ATOMIC, ACC_SOLE = 0, 1, 2, 3
 

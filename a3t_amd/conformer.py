@@ -4,8 +4,11 @@ BatchNorm helpers, dropout keys -- and EngineOptions, the one record of the A3T_
 the order StepSchedule allows; it must not know what model the blocks sit in (no prologue, head or loss: engine.py, and the
 FastSpeech2 models of duration.py / fs2_tts.py, which run their blocks on a bare stack).
 
-Two numeric modes:
+Three numeric modes:
   compute="f32"  : everything fp32, GEMMs on the exact-fp32 MFMA  (parity path, 1e-4)
+  compute="bf16x3" : the fp32 path -- same storage, same schedule, same fp32-only kernels -- with every GEMM that follows the
+                   mode on three bf16 MFMA products per fp32 product (A3T_BF16X3: operands split into bf16 hi + lo in the
+                   loader, operands carried to 2^-16 where bf16 has 2^-8)
   compute="bf16" : tensors that feed GEMMs are stored in bf16 (LayerNorm outputs, FFN hidden, q/k/v,
                    attention probabilities, ...), weights are cast to a bf16 shadow once per step,
                    GEMMs run on the bf16 MFMA with fp32 accumulation; the residual stream, all
@@ -20,7 +23,7 @@ from dataclasses import dataclass
 import torch
 
 from . import ops
-from ._lib import ACC_ADD, ACC_ATOMIC, ACC_STORE, ACT_RELU, ACT_SWISH, BF16, F32
+from ._lib import ACC_ADD, ACC_ATOMIC, ACC_STORE, ACT_RELU, ACT_SWISH, BF16, BF16X3, F32
 from .config import A3TConfig
 from .params import ParamStore
 from .schedule import StepSchedule
@@ -105,6 +108,9 @@ class EngineOptions:
                    fused_attn_train=0 if ft == "0" else 2 if ft == "2" else 1, **on)
 
 
+COMPUTE_MODES = {"f32": F32, "bf16": BF16, "bf16x3": BF16X3}     # compute= of a stack / engine / model -> a3t_gemm_desc.compute
+
+
 class ConformerStack(StepSchedule):
     def __init__(self, cfg: A3TConfig, store: ParamStore, compute: str = "f32", training: bool = True,
                  dropout: bool = False, options: EngineOptions = None):
@@ -117,9 +123,12 @@ class ConformerStack(StepSchedule):
         self.dropping = bool(dropout and training)
         self.step_seed = 0
         self.store = store
-        self.bf16 = (compute == "bf16")
+        if compute not in COMPUTE_MODES:
+            raise ValueError(f"compute={compute!r}: expected one of {', '.join(map(repr, COMPUTE_MODES))}")
+        self.compute = compute
+        self.bf16 = (compute == "bf16")      # (False for "bf16x3": fp32 storage and the fp32 schedule)
         self.adt = torch.bfloat16 if self.bf16 else torch.float32   # storage of GEMM-operand activations
-        self.cmp = BF16 if self.bf16 else F32
+        self.cmp = COMPUTE_MODES[compute]
         self.training = training
         self.pe = legacy_pe_table(cfg).to(self.dev)
         self.sv = {}
@@ -781,7 +790,7 @@ class ConformerStack(StepSchedule):
     def _check_ragged(self, lens, B):
         if self.bf16 or self.training or self._need_grad:
             raise ValueError("lens: ragged rows need an engine in fp32 compute, eval mode, forward only "
-                             f"(compute={'bf16' if self.bf16 else 'f32'}, training={self.training}, "
+                             f"(compute={self.compute}: 'f32' and 'bf16x3' both count, training={self.training}, "
                              f"need_grad={self._need_grad})")
         if lens.dtype != torch.int32 or lens.numel() != B or lens.device.type != self.dev.type:
             raise ValueError(f"lens must be an int32 tensor of {B} entries on {self.dev}")

@@ -2,9 +2,10 @@
 //
 // Covers torch.nn.Linear, Conv1d-as-implicit-im2col (FFN k=3, postnet k=5, PWG dilated k=3),
 // the attention bmm's and every data / weight gradient of those (NT, NN, TN operand layouts).
-// Two arithmetic modes:
+// Three arithmetic modes:
 //   * A3T_F32  : v_mfma_f32_32x32x2_f32  -- exact fp32 (bitwise an fmaf chain), the parity path
 //   * A3T_BF16 : v_mfma_f32_32x32x16_bf16 -- bf16 operands staged through LDS, fp32 accumulate
+//   * A3T_BF16X3 : fp32 operands split into (hi, lo) bf16 pairs in the loader, three bf16 MFMAs per product
 // Tiling is wave64-native: 256 threads = 4 waves in a 2x2 arrangement, each wave owns a 64x64
 // output sub-tile = 2x2 MFMA 32x32 accumulators (64 AGPR-class registers), block tile 128x128.
 // Operands are register-staged (global -> VGPR -> LDS) so the loader can do the im2col row
@@ -422,6 +423,205 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GP p) {
 }
 
 // =============================================================================================
+// bf16x3 kernel (A3T_BF16X3): fp32 operands, each split on the way to LDS into hi = bf16(x) and lo = bf16(x - hi)
+// (round to nearest even, 16 significand bits kept: |x - hi - lo| <= 2^-16 |x|; the split of split_bf16_kernel), and
+//     a b ~= lo_a hi_b + hi_a lo_b + hi_a hi_b
+// as three v_mfma_f32_32x32x16_bf16 into one fp32 accumulator.  Every product is exact; dropped are lo_a lo_b and the two split
+// residuals, each <= 2^-16 |a||b| (bf16 operands: 2^-8).
+// Addressing, tiling, split K and epilogue are the bf16 kernel's above; LDS holds a hi and a lo image of both operands in two
+// buffers: 2 x 4 x 128 x 40 x 2 B = 80 KiB, dynamic (half a CU's LDS: two workgroups per CU, one barrier per K-tile).
+// =============================================================================================
+constexpr int X3_LDS = 2 * 4 * 128 * 40 * 2;
+
+// (hi, lo) of two fp32 values, packed like io_pack2.  Where hi is not finite lo is 0 (x - hi would be NaN, or the opposite
+// infinity for a finite x that rounds to one).  The outputs such an operand reaches are non-finite as in fp32, but not always
+// the same non-finite value: inf x lo_b is NaN where lo_b is 0 and has lo_b's sign elsewhere.
+__device__ __forceinline__ void x3_split2(float x0, float x1, unsigned int& hi, unsigned int& lo) {
+    hi = io_pack2(x0, x1);
+    lo = io_pack2(x0 - __uint_as_float(hi << 16), x1 - __uint_as_float(hi & 0xffff0000u));
+    if ((hi & 0x00007f80u) == 0x00007f80u) lo &= 0xffff0000u;
+    if ((hi & 0x7f800000u) == 0x7f800000u) lo &= 0x0000ffffu;
+}
+
+template <bool AK, bool BKC>
+__global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GP p) {
+    constexpr int BM = 128, BN = 128, BK = 32, LD = 40;
+    extern __shared__ __attribute__((aligned(16))) unsigned char x3_smem[];
+    // [buffer][A hi | A lo | B hi | B lo][128][LD]
+    unsigned short(*Ts)[4][BM][LD] = (unsigned short(*)[4][BM][LD])x3_smem;
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tn = blockIdx.x % p.tiles_n, tm = blockIdx.x / p.tiles_n;
+    const int ks = blockIdx.y % p.splitk, bz = blockIdx.y / p.splitk;
+    const int z0 = bz / p.batch_inner, z1 = bz % p.batch_inner;
+    const float* A = (const float*)p.A + z0 * p.a_bs0 + z1 * p.a_bs1;
+    const float* B = (const float*)p.B + z0 * p.b_bs0 + z1 * p.b_bs1;
+    const int64_t zoff = z0 * p.c_bs0 + z1 * p.c_bs1;
+
+    const int ktiles = (p.K + BK - 1) / BK;
+    const int per = (ktiles + p.splitk - 1) / p.splitk;
+    const int kt0 = ks * per, kt1 = min(ktiles, kt0 + per);
+    if (kt0 >= kt1) return;
+
+    // staged registers, [0] the hi and [1] the lo image: k-contig: 2 chunks of 8 bf16 (uint4); row-contig: 4x4 micro tile -> 4 x uint2
+    uint4 sa[2][2], sb[2][2];
+    int a_t[2];
+    if (AK) {
+        for (int ps = 0; ps < 2; ++ps) {
+            int m = tm * BM + (tid >> 2) + ps * 64;
+            a_t[ps] = (p.taps > 1) ? (m % p.Tseq) : 0;
+        }
+    }
+    auto load8 = [&](const float* q, uint4& h, uint4& l) {  // 8 consecutive fp32 -> 8 (hi, lo)
+        const float4 v0 = *(const float4*)q, v1 = *(const float4*)(q + 4);
+        x3_split2(v0.x, v0.y, h.x, l.x);
+        x3_split2(v0.z, v0.w, h.y, l.y);
+        x3_split2(v1.x, v1.y, h.z, l.z);
+        x3_split2(v1.z, v1.w, h.w, l.w);
+    };
+    auto load_k = [&](const float* base, bool isA, int row, int kg, int tpos, uint4& h, uint4& l) {
+        h = l = make_uint4(0, 0, 0, 0);
+        if (isA) {
+            if (row < p.M && kg < p.K) {
+                const float* q = a_ptr_k(p, base, row, tpos, kg);
+                if (q) load8(q, h, l);
+            }
+        } else {
+            int64_t koff;
+            if (row < p.N && kg < p.K && b_koff(p, kg, koff)) load8(base + (int64_t)row * p.b_rs + koff, h, l);
+        }
+    };
+    // row-contiguous operand: 4 rows x 4 k micro tile, transposed in registers
+    auto load_r = [&](const float* base, bool isA, int r0, int rmax, int k0, uint4* h, uint4* l) {
+        float v[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            int k = k0 + i;
+            v[i][0] = v[i][1] = v[i][2] = v[i][3] = 0.f;
+            int64_t koff;
+            bool ok = k < p.K;
+            if (isA)
+                koff = (int64_t)k * p.a_cs;
+            else
+                ok = ok && b_koff(p, k, koff);
+            if (ok && r0 < rmax) {
+                const float* q = base + koff + r0;
+                if (r0 + 3 < rmax) {
+                    float4 t = *(const float4*)q;
+                    v[i][0] = t.x, v[i][1] = t.y, v[i][2] = t.z, v[i][3] = t.w;
+                } else {
+                    for (int j = 0; j < 4; ++j)
+                        if (r0 + j < rmax) v[i][j] = q[j];
+                }
+            }
+        }
+        // row j gets (v[0][j], v[1][j], v[2][j], v[3][j]) = 4 consecutive k
+        x3_split2(v[0][0], v[1][0], h[0].x, l[0].x);
+        x3_split2(v[2][0], v[3][0], h[0].y, l[0].y);
+        x3_split2(v[0][1], v[1][1], h[0].z, l[0].z);
+        x3_split2(v[2][1], v[3][1], h[0].w, l[0].w);
+        x3_split2(v[0][2], v[1][2], h[1].x, l[1].x);
+        x3_split2(v[2][2], v[3][2], h[1].y, l[1].y);
+        x3_split2(v[0][3], v[1][3], h[1].z, l[1].z);
+        x3_split2(v[2][3], v[3][3], h[1].w, l[1].w);
+    };
+
+    auto load_tiles = [&](int k0) {
+        if (AK) {
+            const int r = tid >> 2, kq = tid & 3;
+#pragma unroll
+            for (int ps = 0; ps < 2; ++ps) load_k(A, true, tm * BM + r + ps * 64, k0 + kq * 8, a_t[ps], sa[0][ps], sa[1][ps]);
+        } else {
+            load_r(A, true, tm * BM + (tid & 31) * 4, p.M, k0 + (tid >> 5) * 4, sa[0], sa[1]);
+        }
+        if (BKC) {
+            const int r = tid >> 2, kq = tid & 3;
+#pragma unroll
+            for (int ps = 0; ps < 2; ++ps) load_k(B, false, tn * BN + r + ps * 64, k0 + kq * 8, 0, sb[0][ps], sb[1][ps]);
+        } else {
+            load_r(B, false, tn * BN + (tid & 31) * 4, p.N, k0 + (tid >> 5) * 4, sb[0], sb[1]);
+        }
+    };
+    // one operand's staged registers -> its hi (img) and lo (img + 1) images
+    auto store_op = [&](int buf, int img, bool kcontig, const uint4 (*s)[2]) {
+#pragma unroll
+        for (int hl = 0; hl < 2; ++hl) {
+            unsigned short(*T)[LD] = Ts[buf][img + hl];
+            if (kcontig) {
+                const int r = tid >> 2, kq = tid & 3;
+#pragma unroll
+                for (int ps = 0; ps < 2; ++ps) *(uint4*)&T[r + ps * 64][kq * 8] = s[hl][ps];
+            } else {
+                const int r0 = (tid & 31) * 4, kq = tid >> 5;
+                *(uint2*)&T[r0 + 0][kq * 4] = make_uint2(s[hl][0].x, s[hl][0].y);
+                *(uint2*)&T[r0 + 1][kq * 4] = make_uint2(s[hl][0].z, s[hl][0].w);
+                *(uint2*)&T[r0 + 2][kq * 4] = make_uint2(s[hl][1].x, s[hl][1].y);
+                *(uint2*)&T[r0 + 3][kq * 4] = make_uint2(s[hl][1].z, s[hl][1].w);
+            }
+        }
+    };
+    auto store_tiles = [&](int buf) {
+        store_op(buf, 0, AK, sa);
+        store_op(buf, 2, BKC, sb);
+    };
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    const int wm = (w >> 1) * 64, wn = (w & 1) * 64, lr = lane & 31, lk = lane >> 5;
+    load_tiles(kt0 * BK);
+    store_tiles(0);
+    __syncthreads();
+    int buf = 0;
+    for (int kt = kt0; kt < kt1; ++kt) {
+        const bool more = (kt + 1 < kt1);
+        if (more) load_tiles((kt + 1) * BK);
+#pragma unroll
+        for (int kk = 0; kk < BK / 16; ++kk) {
+            bf16x8 ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                ah[i] = *(const bf16x8*)&Ts[buf][0][wm + i * 32 + lr][kk * 16 + lk * 8];
+                al[i] = *(const bf16x8*)&Ts[buf][1][wm + i * 32 + lr][kk * 16 + lk * 8];
+                bh[i] = *(const bf16x8*)&Ts[buf][2][wn + i * 32 + lr][kk * 16 + lk * 8];
+                bl[i] = *(const bf16x8*)&Ts[buf][3][wn + i * 32 + lr][kk * 16 + lk * 8];
+            }
+            // the two cross terms first, hi x hi last: the small terms are not added to an already large sum
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+        }
+        if (more) store_tiles(buf ^ 1);
+        __syncthreads();
+        buf ^= 1;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                int row = tm * BM + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                int col = tn * BN + wn + j * 32 + lr;
+                epilogue_store(p, zoff, row, col, acc[i][j][r], ks);
+            }
+}
+
+// =============================================================================================
 // host: what the GEMM files share (switches), the plan (route table) and the launch
 // =============================================================================================
 // Kernel-selection switches, read from the environment on first use.  8P / PN / TT / 8P_TN / 8P_TN3: 0 never, 1 whenever legal,
@@ -509,8 +709,23 @@ static bool glds_routes(GP& p, int batch, bool AK, bool BKC, GemmPlan* pl) {
     return true;
 }
 
-// Validates the descriptor, fills the kernel argument and walks the routes: fused conv weight gradient, fp32, the direct-to-LDS
-// bf16 kernels, the legacy bf16 kernel.  Returns 0 or A3T_EINVAL; launches nothing.
+// The register-staged kernels (legacy bf16, bf16x3): k-contiguous operands are read in chunks of 8 elements, row-contiguous in
+// chunks of 4
+static bool staged_aligned(const GP& p, bool AK, bool BKC) {
+    bool ok = al(p.A, 16) && al(p.B, 16);
+    if (AK)
+        ok = ok && m4(p.a_rs, 8) && m4(p.K, 8) && m4(p.Kc, 8) && m4(p.a_bs0, 8) && m4(p.a_bs1, 8);
+    else
+        ok = ok && m4(p.a_cs, 4) && m4(p.a_bs0, 4) && m4(p.a_bs1, 4);
+    if (BKC)
+        ok = ok && m4(p.b_rs, 8) && m4(p.K, 8) && m4(p.Kc, 8) && m4(p.b_ts, 8) && m4(p.b_bs0, 8) && m4(p.b_bs1, 8);
+    else
+        ok = ok && m4(p.b_cs, 4) && m4(p.b_ts, 4) && m4(p.b_bs0, 4) && m4(p.b_bs1, 4);
+    return ok;
+}
+
+// Validates the descriptor, fills the kernel argument and walks the routes: fused conv weight gradient, fp32 (and bf16x3 on fp32
+// operands), the direct-to-LDS bf16 kernels, the legacy bf16 kernel.  Returns 0 or A3T_EINVAL; launches nothing.
 static int gemm_plan(const a3t_gemm_desc* d, GP* gp, GemmPlan* pl) {
     if (!d || !d->A || !d->B || !d->C || d->M <= 0 || d->N <= 0 || d->K <= 0) return A3T_EINVAL;
     GP& p = *gp;
@@ -571,8 +786,15 @@ static int gemm_plan(const a3t_gemm_desc* d, GP* gp, GemmPlan* pl) {
     const int tiles_m = (p.M + 127) / 128;
     const dim3 grid((unsigned)(p.tiles_n * tiles_m), (unsigned)(batch * p.splitk));
 
-    if (d->compute == A3T_F32) {
+    if (d->compute == A3T_F32 || d->compute == A3T_BF16X3) {
         if (d->a_dtype != A3T_F32 || d->b_dtype != A3T_F32 || d->colsum || p.a_signmask || p.A2) return A3T_EINVAL;
+        // bf16x3 takes exactly what fp32 takes: the three-product kernel inside the register-staged loaders' alignment
+        // contract, the (more exact) fp32 kernel everywhere else
+        if (d->compute == A3T_BF16X3 && staged_aligned(p, AK, BKC)) {
+            pl->route = GR_BF16X3, pl->ak = AK, pl->bkc = BKC, pl->grid = grid;
+            snprintf(pl->name, sizeof(pl->name), "gemm_bf16x3_kernel<%s, %s>", tf(AK), tf(BKC));
+            return 0;
+        }
         bool vec = al(p.A, 16) && al(p.B, 16) && m4(p.a_bs0, 4) && m4(p.a_bs1, 4) && m4(p.b_bs0, 4) && m4(p.b_bs1, 4);
         if (AK)
             vec = vec && m4(p.a_rs, 4) && m4(p.K, 4) && m4(p.Kc, 4);
@@ -590,17 +812,7 @@ static int gemm_plan(const a3t_gemm_desc* d, GP* gp, GemmPlan* pl) {
     if (d->a_dtype == A3T_BF16 && d->b_dtype == A3T_BF16 && glds_routes(p, batch, AK, BKC, pl)) return 0;
     if (keep || p.a_signmask || p.A2 || p.a_unaligned) return A3T_EINVAL;        // keep-bit images only exist in the 8-phase kernel, sign masks in the direct-to-LDS TN kernels
     if (d->colsum) return A3T_EINVAL;   // fused column sums live in the direct-to-LDS kernel's epilogue
-    // the legacy register-staged kernel: k-contiguous operands are read in chunks of 8 elements, row-contiguous in chunks of 4
-    bool ok = al(p.A, 16) && al(p.B, 16);
-    if (AK)
-        ok = ok && m4(p.a_rs, 8) && m4(p.K, 8) && m4(p.Kc, 8) && m4(p.a_bs0, 8) && m4(p.a_bs1, 8);
-    else
-        ok = ok && m4(p.a_cs, 4) && m4(p.a_bs0, 4) && m4(p.a_bs1, 4);
-    if (BKC)
-        ok = ok && m4(p.b_rs, 8) && m4(p.K, 8) && m4(p.Kc, 8) && m4(p.b_ts, 8) && m4(p.b_bs0, 8) && m4(p.b_bs1, 8);
-    else
-        ok = ok && m4(p.b_cs, 4) && m4(p.b_ts, 4) && m4(p.b_bs0, 4) && m4(p.b_bs1, 4);
-    if (!ok) return A3T_EINVAL;
+    if (!staged_aligned(p, AK, BKC)) return A3T_EINVAL;
     pl->route = GR_BF16_LEGACY, pl->ak = AK, pl->bkc = BKC, pl->grid = grid;
     pl->a_f32 = d->a_dtype == A3T_F32, pl->b_f32 = d->b_dtype == A3T_F32;
     snprintf(pl->name, sizeof(pl->name), "gemm_bf16_kernel<%s, %s, %s, %s>", pl->a_f32 ? "float" : "unsigned short",
@@ -648,6 +860,26 @@ static int legacy_launch(const GP& p, const GemmPlan& pl, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
+// The 80 KiB are granted per kernel and per device, so at every launch, like the direct-to-LDS kernels' (gemm_bf16.hip): a
+// process that drives a second GPU must not launch there without the raised limit.
+static int x3_launch(const GP& p, const GemmPlan& pl, hipStream_t stream) {
+#define LAUNCH_X3(ak, bk)                                                                                                   \
+    do {                                                                                                                    \
+        const hipError_t opt_in =                                                                                           \
+            hipFuncSetAttribute((const void*)gemm_bf16x3_kernel<ak, bk>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS); \
+        if (opt_in != hipSuccess) return (int)opt_in;                                                                       \
+        hipLaunchKernelGGL((gemm_bf16x3_kernel<ak, bk>), pl.grid, dim3(256), X3_LDS, stream, p);                            \
+    } while (0)
+    if (pl.ak && pl.bkc)
+        LAUNCH_X3(true, true);
+    else if (pl.ak)
+        LAUNCH_X3(true, false);
+    else
+        LAUNCH_X3(false, false);
+#undef LAUNCH_X3
+    return (int)hipGetLastError();
+}
+
 extern "C" int a3t_gemm(const a3t_gemm_desc* d, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     GP p;
@@ -658,6 +890,7 @@ extern "C" int a3t_gemm(const a3t_gemm_desc* d, void* stream_) {
     switch (pl.route) {
         case GR_F32: r = f32_launch(p, pl, stream); break;
         case GR_BF16_LEGACY: r = legacy_launch(p, pl, stream); break;
+        case GR_BF16X3: r = x3_launch(p, pl, stream); break;
         case GR_GLDS_128: r = glds_launch(p, pl, stream); break;
         case GR_PN: r = pn_launch(p, pl, stream); break;
         case GR_TT: r = tt_launch(p, pl, stream); break;

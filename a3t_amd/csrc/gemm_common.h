@@ -223,10 +223,10 @@ __device__ __forceinline__ void colsum_flush(const GP& p, float4 cs, int lane, b
 // host: kernel selection.  gemm_plan (gemm.hip) validates a descriptor and walks the routes in order; each kernel file owns one
 // X_plan (predicate, cost model, geometry: pure host code, false = not this kernel) and one X_launch.
 // =============================================================================================
-enum GemmRoute { GR_F32, GR_BF16_LEGACY, GR_GLDS_128, GR_PN, GR_G8, GR_G8_TN, GR_G8_TN3, GR_TT };
+enum GemmRoute { GR_F32, GR_BF16_LEGACY, GR_GLDS_128, GR_PN, GR_G8, GR_G8_TN, GR_G8_TN3, GR_TT, GR_BF16X3 };
 struct GemmPlan {
     GemmRoute route;
-    bool ak, bkc, vec;          // F32 / BF16_LEGACY: A / B k-contiguous; F32: 16-byte loads
+    bool ak, bkc, vec;          // F32 / BF16_LEGACY / BF16X3: A / B k-contiguous; F32: 16-byte loads
     bool a_f32, b_f32;          // BF16_LEGACY: fp32 operand storage
     int ly, stages, wn, conv;   // GLDS_128: layout, LDS stages, 64-column groups per tile, conv mode (ly also for TT)
     bool cv;                    // PN / G8: implicit-im2col conv; G8_TN / G8_TN3: fused conv weight gradient

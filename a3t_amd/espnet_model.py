@@ -16,6 +16,7 @@ from typing import Dict, List, Tuple, Union
 import torch
 
 from .config import A3TConfig
+from .conformer import COMPUTE_MODES
 from .params import ParamStore
 
 
@@ -55,6 +56,8 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
         self.feats_extract = feats_extract
         self.normalize = normalize            # stored, never applied (sedit_model.py:79)
         self.cfg = config
+        if compute not in COMPUTE_MODES:      # (a typo must not reach the engine, nor the checks on self.compute, as another mode)
+            raise ValueError(f"compute={compute!r}: expected one of {', '.join(map(repr, COMPUTE_MODES))}")
         self.compute = compute
         # torch.nn.Dropout semantics: the recipe's dropout sites are active in train() mode, off in eval() mode
         # (dropout=False builds a deterministic training engine: parity tests, finite-difference checks)
@@ -212,7 +215,8 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
         positional table depend on the padded lengths.  The model is trained on exactly such batches.
 
         rows="alone": row b is computed as the reference's B = 1 driver computes it, from the row's own speech_mask / text_mask
-        lengths (prefix masks; MLMEngine._forward_rows_alone), to fp32 rounding -- not bit for bit.  fp32 compute, eval mode.
+        lengths (prefix masks; MLMEngine._forward_rows_alone), to fp32 rounding -- not bit for bit.  fp32 or bf16x3 compute (fp32
+        storage both), eval mode.
         The rows are sorted by tokens n_b and cut into chunks with B * heads * n_max^2 <= max_score_elems (each of the three
         score-sized tensors of the materialised attention); a chunk of one row takes the plain B = 1 pass at the row's exact
         lengths.  The device lengths come from the masks without a host synchronisation; the chunking needs them on the host,
@@ -224,9 +228,10 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
         B, Tmax = speech.shape[0], speech.shape[1]
         sb, nsp = self._span_arguments(span_boundary, span_counts, B)
         if rows == "alone":
-            if self.compute != "f32" or self.training:
-                raise ValueError(f"rows='alone' needs a model built with compute='f32' in eval mode (compute={self.compute!r}, "
-                                 f"training={self.training}): the fused bf16 attention forward has no per-row rel_shift")
+            if self.compute not in ("f32", "bf16x3") or self.training:
+                raise ValueError("rows='alone' needs a model built with compute='f32' or 'bf16x3' in eval mode "
+                                 f"(compute={self.compute!r}, training={self.training}): the fused bf16 attention forward has "
+                                 "no per-row rel_shift")
             host = None
             if not speech_mask.is_cuda and not text_mask.is_cuda:
                 host = (speech_mask.reshape(B, -1).sum(-1).tolist(), text_mask.reshape(B, -1).sum(-1).tolist())

@@ -30,6 +30,7 @@ extern "C" {
 
 #define A3T_F32 0
 #define A3T_BF16 1
+#define A3T_BF16X3 2 /* a3t_gemm_desc::compute only: never a storage type */
 
 #define A3T_EINVAL (-22)
 
@@ -85,7 +86,12 @@ typedef struct a3t_gemm_desc {
     int32_t splitk;
     int32_t a_dtype, b_dtype, c_dtype; /* A3T_F32 | A3T_BF16 (storage) */
     int32_t compute;                   /* A3T_F32: v_mfma_f32_32x32x2_f32 (exact f32);
-                                          A3T_BF16: v_mfma_f32_32x32x16_bf16, fp32 accumulate */
+                                          A3T_BF16: v_mfma_f32_32x32x16_bf16, fp32 accumulate;
+                                          A3T_BF16X3: fp32 A and B, each split into hi = bf16(x), lo = bf16(x - hi) on the
+                                          way to LDS, a b ~= lo_a hi_b + hi_a lo_b + hi_a hi_b as three bf16 MFMAs into one
+                                          fp32 accumulator (operands to 2^-16, bf16: 2^-8).  Accepts and refuses exactly what A3T_F32
+                                          does; descriptors outside the 8-element (k-contiguous) / 4-element (row-contiguous)
+                                          alignment of its loaders run on the A3T_F32 kernel */
     int32_t s_dtype;                   /* storage type of S (A3T_F32 | A3T_BF16) */
     int32_t colsum_slots;              /* 0/1: one accumulator row; S > 1: output tiles spread their atomics over S
                                           copies colsum + slot*colsum_ss (slot = (row tile + batch) % S) which the

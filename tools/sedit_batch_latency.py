@@ -37,8 +37,15 @@ model would cost.
           the recording's mel and A the model's output -- max and RMS of the difference relative to max(1, max |mel|), frame by
           frame from the start of the kept run over the shorter of the two runs.
 
-    python tools/sedit_batch_latency.py [--models c2] [--compute bf16 f32] [--n 1 4 8] [--calls 50] [--warmup 5] [--kernel]
-                                        [--vocoder-compute f32 f16] [--rows batch alone] [--spans]
+  --ab R: the compute modes of --compute against each other on one set of requests, keys `<model>.ab.n<N>`: one editor per mode,
+          and R times over, mode after mode (f32, bf16x3, bf16, f32, ...): the loop of `edit`, edit_batch(requests) and -- with
+          --rows alone, on the modes that have it (f32, bf16x3) -- edit_batch(requests, rows="alone"), each the median of --calls
+          calls.  Per mode and leg ms per request as median [min, max] over the R rounds, for every other mode whether its range
+          lies clear of f32's, and the distance of its edit_batch mel from the f32 editor's (RMS and worst element over all
+          requests, relative to max(1, max |mel|)).
+
+    python tools/sedit_batch_latency.py [--models c2] [--compute bf16 f32 bf16x3] [--n 1 4 8] [--calls 50] [--warmup 5] [--kernel]
+                                        [--vocoder-compute f32 f16] [--rows batch alone] [--spans] [--ab 3]
 """
 import argparse
 import json
@@ -293,6 +300,45 @@ def rows_alone_legs(ed, oc, reqs, calls, warmup):
     return r
 
 
+def ab_legs(eds, reqs, alone, calls, warmup, rounds):
+    """--ab (module docstring): eds = {compute: editor}, f32 among them."""
+    n = len(reqs)
+    args = [(r.wav_org, r.times2, r.word2phns, r.new_phns, r.new_word2phns, r.old_str, r.new_str) for r in reqs]
+    ts = {c: {} for c in eds}
+    for _ in range(rounds):
+        for c, ed in eds.items():
+            def loop():
+                for x in args:
+                    ed.edit(*x)
+
+            legs_ = {"loop_of_edit": loop, "edit_batch": lambda: ed.edit_batch(reqs)}
+            if alone and c != "bf16":
+                legs_["edit_batch_rows_alone"] = lambda: ed.edit_batch(reqs, rows="alone")
+            for k, fn in legs_.items():
+                ts[c].setdefault(k, []).append(timed(fn, calls, warmup) / n)
+    out = {}
+    for c, legs_ in ts.items():
+        out[c] = {k: dict(ms=round(float(np.median(v)), 3), min_max_ms=[round(min(v), 3), round(max(v), 3)]) for k, v in legs_.items()}
+        if c != "f32":
+            for k, v in legs_.items():
+                ref = ts["f32"][k]
+                out[c][k]["f32_over_this"] = round(float(np.median(ref)) / float(np.median(v)), 3)
+                out[c][k]["range_clear_of_f32"] = bool(max(v) < min(ref) or max(ref) < min(v))
+    mel = {}
+    for c, ed in eds.items():
+        ed.vocoder, voc = None, ed.vocoder
+        mel[c] = [g["feat"].double() for g in ed.edit_batch(reqs)]
+        ed.vocoder = voc
+    for c in eds:
+        if c != "f32":
+            d = torch.cat([(x - y).reshape(-1) for x, y in zip(mel[c], mel["f32"])])
+            scale = max(1.0, max(float(y.abs().max()) for y in mel["f32"]))
+            out[c]["edit_batch_mel_to_f32_of_scale"] = dict(rms=float(f"{float(d.pow(2).mean().sqrt()) / scale:.3e}"),
+                                                            worst=float(f"{float(d.abs().max()) / scale:.3e}"))
+    out["frames"] = [int(f.shape[0]) for f in mel["f32"]]
+    return out
+
+
 SPAN_LEX = {"ZEBRA": ["Z", "IY1", "B"], "PLUM": ["P", "L", "AH1"]}      # in no prompt: the word diff is the two swaps
 
 
@@ -392,6 +438,7 @@ def main():
     ap.add_argument("--vocoder-compute", nargs="+", default=["f32"], choices=["f32", "f16"])
     ap.add_argument("--rows", nargs="+", default=["batch"], choices=["batch", "alone"])
     ap.add_argument("--spans", action="store_true")
+    ap.add_argument("--ab", type=int, default=0, metavar="ROUNDS")
     a = ap.parse_args()
     prop = torch.cuda.get_device_properties(0)
     out = {"device": f"{prop.name} ({getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs)"}
@@ -412,6 +459,23 @@ def main():
                     key = f"{which}.{compute}.spans.n{n}"
                     out[key] = spans_legs(ed, oc, frames, a.calls, a.warmup)
                     print(json.dumps({key: out[key]}), flush=True)
+        print(json.dumps({"sedit_batch_latency": out}))
+        return
+    if a.ab:
+        if "f32" not in a.compute:
+            ap.error("--ab compares against f32: name it in --compute")
+        for which in a.models:
+            eds = {c: editor(which, c) for c in a.compute}
+            oc = eds["f32"][1]
+            for n in a.n:
+                rs = np.random.RandomState(n)
+                lo, hi = a.frames_range
+                reqs = [request(int(f), int(k), oc, seed=10 * n + i)
+                        for i, (f, k) in enumerate(zip(np.linspace(hi, lo, n).astype(int) if n > 1 else [(lo + hi) // 2],
+                                                       rs.randint(3, 11, n)))]
+                key = f"{which}.ab.n{n}"
+                out[key] = ab_legs({c: e[0] for c, e in eds.items()}, reqs, "alone" in a.rows, a.calls, a.warmup, a.ab)
+                print(json.dumps({key: out[key]}), flush=True)
         print(json.dumps({"sedit_batch_latency": out}))
         return
     if "alone" in a.rows:
