@@ -76,6 +76,20 @@ _SIGS = {
     "a3t_embed_finish_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                              ctypes.c_uint32, _P],
     "a3t_scale": [_P, _P, c_int64, c_float, _P],
+    "a3t_attn_fwd_plain": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_float, c_float,
+                           ctypes.c_uint32, _P],
+    "a3t_attn_fwd_train_plain": [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_float,
+                                 c_float, ctypes.c_uint32, _P],
+    "a3t_embed_finish_abs_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float,
+                                 ctypes.c_uint32, _P, _P],
+    "a3t_embed_finish_abs_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int,
+                                 c_float, c_float, ctypes.c_uint32, _P],
+    "a3t_embed_finish_abs_partials": [c_int, c_int, c_int, c_int],
+    "a3t_scale_add_pos": [_P, _P, _P, c_int, c_int, c_int, c_float, c_float, ctypes.c_uint32, _P],
+    "a3t_softmax_plain_fwd": [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_float, _P, c_float,
+                              ctypes.c_uint32, _P],
+    "a3t_softmax_plain_bwd": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_float, _P,
+                              c_float, ctypes.c_uint32, _P, _P],
     "a3t_axpy": [_P, _P, c_int64, c_float, _P],
     "a3t_attn_bias_fold": [_P, c_int32, c_int32, _P, _P, _P, _P],
     "a3t_scale_dev": [_P, _P, c_int64, _P, _P],

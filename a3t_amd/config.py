@@ -36,6 +36,10 @@ class A3TConfig:
     segment_emb: bool = True     # input_layer 'sega_mlm'; False = 'mlm': no segment table, segment ids are not read
     pre_blocks: int = 0          # pre_speech_layer: conformer blocks over the speech tokens alone, before the text joins
     has_decoder: bool = True     # False = decoder 'no_decoder': the head reads encoder.after_norm (no sqrt(d) scale, no decoder.after_norm)
+    # encoder / decoder 'transformer' (transformer/encoder.py:370-777): pre-LN blocks of plain MultiHeadedAttention + position-wise
+    # FFN, absolute positions added in the prologue and at the decoder entry.  ff_kernel = 1 is positionwise_layer_type 'linear'.
+    block: str = "conformer"     # "conformer" | "transformer"
+    scaled_pos: bool = False     # use_scaled_pos_enc: x + alpha * pe with two trained scalars (speech, text); transformer only
     # feature extraction
     fs: int = 24000
     n_fft: int = 2048
@@ -55,9 +59,9 @@ class A3TConfig:
     @staticmethod
     def from_espnet(encoder_conf: Dict[str, Any], decoder_conf: Dict[str, Any], model_conf: Dict[str, Any],
                     input_size: int, odim: int, vocab: int, feats_conf: Dict[str, Any] = None,
-                    has_decoder: bool = True) -> "A3TConfig":
+                    has_decoder: bool = True, block: str = "conformer", scaled_pos: bool = False) -> "A3TConfig":
         """Translate the recipe's encoder_conf/decoder_conf/model_conf dictionaries.  has_decoder=False (decoder: no_decoder):
-        decoder_conf is not read."""
+        decoder_conf is not read.  block="transformer" (encoder: transformer): _from_espnet_transformer."""
         e, m = encoder_conf, model_conf
         d = decoder_conf if has_decoder else {}          # (left alone without a decoder, tasks/mlm.py:393-395)
         input_layer = e.get("input_layer", "sega_mlm")
@@ -66,6 +70,15 @@ class A3TConfig:
         pre_blocks = int(e.get("pre_speech_layer", 0) or 0)
         if pre_blocks < 0:
             raise ValueError(f"pre_speech_layer={pre_blocks}: expected 0 or more")
+        if block == "transformer":
+            c = A3TConfig._from_espnet_transformer(e, d, m, input_size, odim, vocab, has_decoder, scaled_pos,
+                                                   input_layer == "sega_mlm", pre_blocks)
+            return A3TConfig._with_feats(c, feats_conf)
+        if block != "conformer":
+            raise NotImplementedError(f"block={block!r}: expected 'conformer' or 'transformer'")
+        if scaled_pos:
+            raise NotImplementedError("use_scaled_pos_enc=True: the conformer encoder never builds pos_enc_class "
+                                      "(ScaledPositionalEncoding is reachable with encoder: transformer only)")
         for conf, who in ((e, "encoder_conf"), (d, "decoder_conf")):
             if conf.get("positionwise_layer_type", "conv1d") != "conv1d":
                 raise NotImplementedError(f"{who}.positionwise_layer_type={conf['positionwise_layer_type']!r}: only 'conv1d' "
@@ -85,11 +98,65 @@ class A3TConfig:
             positional_dropout_rate=e.get("positional_dropout_rate", 0.1),
             attention_dropout_rate=e.get("attention_dropout_rate", 0.0), mlm_prob=m.get("mlm_prob", 0.25),
             mean_phn_span=m.get("mean_phn_span", 3))
+        return A3TConfig._with_feats(c, feats_conf)
+
+    @staticmethod
+    def _with_feats(c, feats_conf):
         if feats_conf:
             for k in ("fs", "n_fft", "win_length", "hop_length", "n_mels", "fmin", "fmax"):
                 if k in feats_conf and feats_conf[k] is not None:
                     setattr(c, k, feats_conf[k])
         return c
+
+    @staticmethod
+    def _from_espnet_transformer(e, d, m, input_size, odim, vocab, has_decoder, scaled_pos, segment_emb, pre_blocks):
+        """encoder: transformer with decoder: transformer | no_decoder (MLMEncoder / MLMDecoder, transformer/encoder.py:370-777;
+        the defaults are that constructor's).  Everything the engine does not run is refused by its field name."""
+        if pre_blocks > 0:
+            raise NotImplementedError(f"encoder_conf.pre_speech_layer={pre_blocks}: pre-speech blocks are implemented for the "
+                                      "conformer encoder only")
+        for conf, who in ((e, "encoder_conf"), (d, "decoder_conf")) if has_decoder else ((e, "encoder_conf"),):
+            sa = conf.get("selfattention_layer_type", "selfattn")
+            if sa != "selfattn":      # (lightconv*, dynamicconv*, longformer; rel_selfattn builds the same class but is not the name)
+                raise NotImplementedError(f"{who}.selfattention_layer_type={sa!r}: only 'selfattn' is implemented for a "
+                                          "transformer model")
+            pw = conf.get("positionwise_layer_type", "linear")
+            if pw not in ("linear", "conv1d"):
+                raise NotImplementedError(f"{who}.positionwise_layer_type={pw!r}: only 'linear' and 'conv1d' are implemented")
+            k = int(conf.get("positionwise_conv_kernel_size", 1)) if pw == "conv1d" else 1
+            if k < 1 or k % 2 == 0:
+                raise NotImplementedError(f"{who}.positionwise_conv_kernel_size={k}: expected an odd kernel size")
+            if not conf.get("normalize_before", True):
+                raise NotImplementedError(f"{who}.normalize_before=False: only pre-LN blocks are implemented")
+            if conf.get("concat_after", False):
+                raise NotImplementedError(f"{who}.concat_after=True is not implemented")
+            if float(conf.get("stochastic_depth_rate", 0.0) or 0.0) > 0.0:
+                raise NotImplementedError(f"{who}.stochastic_depth_rate={conf['stochastic_depth_rate']}: layer skipping is not "
+                                          "implemented")
+            if conf.get("intermediate_layers") is not None:
+                raise NotImplementedError(f"{who}.intermediate_layers is not implemented")
+
+        def ffn(conf):
+            pw = conf.get("positionwise_layer_type", "linear")
+            return int(conf.get("positionwise_conv_kernel_size", 1)) if pw == "conv1d" else 1
+        if has_decoder:
+            for k, dflt in (("attention_dim", 256), ("attention_heads", 4), ("linear_units", 2048)):
+                if d.get(k, dflt) != e.get(k, dflt):
+                    raise NotImplementedError(f"decoder_conf.{k}={d.get(k, dflt)} differs from encoder_conf.{k}="
+                                              f"{e.get(k, dflt)}: one block size per model")
+            if ffn(d) != ffn(e):
+                raise NotImplementedError("decoder_conf.positionwise_layer_type / positionwise_conv_kernel_size differ from "
+                                          "encoder_conf's: one FFN kernel size per model")
+        return A3TConfig(
+            idim=input_size, odim=odim, vocab=vocab, adim=e.get("attention_dim", 256), heads=e.get("attention_heads", 4),
+            ff=e.get("linear_units", 2048), ff_kernel=ffn(e), enc_blocks=e.get("num_blocks", 6),
+            dec_blocks=d.get("num_blocks", 6) if has_decoder else 0, segment_emb=segment_emb, pre_blocks=0,
+            has_decoder=bool(has_decoder), block="transformer", scaled_pos=bool(scaled_pos),
+            postnet_layers=m.get("postnet_layers", 0), postnet_chans=m.get("postnet_chans", 0),
+            postnet_filts=m.get("postnet_filts", 0), lsm_weight=m.get("lsm_weight", 0.0), dropout_rate=e.get("dropout_rate", 0.1),
+            positional_dropout_rate=e.get("positional_dropout_rate", 0.1),
+            attention_dropout_rate=e.get("attention_dropout_rate", 0.0), mlm_prob=m.get("mlm_prob", 0.25),
+            mean_phn_span=m.get("mean_phn_span", 3))
 
 
 def config_c4(**kw) -> A3TConfig:

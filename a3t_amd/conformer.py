@@ -3,6 +3,8 @@ hand-derived backward, with what a block needs around it -- positional table, bf
 BatchNorm helpers, dropout keys -- and EngineOptions, the one record of the A3T_* switches.  ConformerStack launches kernels in
 the order StepSchedule allows; it must not know what model the blocks sit in (no prologue, head or loss: engine.py, and the
 FastSpeech2 models of duration.py / fs2_tts.py, which run their blocks on a bare stack).
+A stack built from a config with block = "transformer" runs the transformer EncoderLayer instead (tblock_fwd / tblock_bwd: plain
+MultiHeadedAttention, one position-wise FFN with residual scale 1.0, no LayerNorm behind the block).
 
 Three numeric modes:
   compute="f32"  : everything fp32, GEMMs on the exact-fp32 MFMA  (parity path, 1e-4)
@@ -131,12 +133,18 @@ class ConformerStack(StepSchedule):
         self.cmp = COMPUTE_MODES[compute]
         self.training = training
         self.pe = legacy_pe_table(cfg).to(self.dev)
+        # a transformer model's blocks (tblock_fwd / tblock_bwd): FFN residual scale 1.0 where the macaron pair has 0.5 each, and
+        # absolute positions -- PositionalEncoding.pe is the same table in forward order (row t = PE(t); the legacy rel-pos class
+        # inherits extend_pe and only reverses it)
+        self.transformer = cfg.block == "transformer"
+        self._ffs = 1.0 if self.transformer else 0.5
+        self.pe_abs = self.pe.flip(0).contiguous() if self.transformer else None
         self.sv = {}
         self.scratch64 = torch.zeros(4 * max(cfg.ff, 3 * cfg.adim, cfg.postnet_chans, 64), dtype=torch.float64,
                                      device=self.dev)
         self.bn_momentum = 0.1
         # Linear weight gradients collected for one grouped launch (_lin_wgrad): 4 = one Conformer block's; needs the deep scratch ring
-        self._wg_group = 4 if (self.bf16 and self.side is not None and self._depth >= 8 and opt.wgrad_group) else 1
+        self._wg_group = (2 if self.transformer else 4) if (self.bf16 and self.side is not None and self._depth >= 8 and opt.wgrad_group) else 1
         self._wg_pending, self._wg_slots = [], set()
         self._gm_ready = None
         self.colsum_slots = 16          # spread of the attention bias-gradient atomics (1 and 64 measured: slower / equal)
@@ -409,7 +417,7 @@ class ConformerStack(StepSchedule):
         if lens is not None:      # the second conv's taps read zeros behind every row's length, not relu(b1 + ...)
             ops.zero_tail(h, lens, 1, M // T, T)
         xo = self.ws.get(tag + ".xo", (M, c.adim))
-        ops.conv_fwd(h, self.W(pre + ".w2"), xo, T, pad, bias=p[pre + ".b2"], R=x, alpha=0.5, compute=self.cmp,
+        ops.conv_fwd(h, self.W(pre + ".w2"), xo, T, pad, bias=p[pre + ".b2"], R=x, alpha=self._ffs, compute=self.cmp,
                      drop=self._drop(c.dropout_rate, tag + ".o"))
         self.sv[tag] = (y, h, keep, lay)
         return xo
@@ -423,13 +431,14 @@ class ConformerStack(StepSchedule):
         pad = (c.ff_kernel - 1) // 2
         self._sub_begin()
         g16 = self._g16(g)
-        ga = self._gm(g, tag + ".o", c.dropout_rate, gr[pre + ".b2"], 0.5)
-        self._side(lambda: ops.conv_bwd_weight(ga, h, gr[pre + ".w2"], T, pad, alpha=0.5, compute=self.cmp))
+        ffs = self._ffs
+        ga = self._gm(g, tag + ".o", c.dropout_rate, gr[pre + ".b2"], ffs)
+        self._side(lambda: ops.conv_bwd_weight(ga, h, gr[pre + ".w2"], T, pad, alpha=ffs, compute=self.cmp))
         dh = self._act(self._t("tmp.dh"), (M, c.ff))
         # (without dropout b2's gradient = 0.5*colsum(g) was accumulated by the LayerNorm backward that
         #  produced g; the dropout on h folds into the relu mask S=h>0 and the 1/(1-p) factor)
         hd = self._drop(c.dropout_rate, tag + ".h")
-        a_dh = 0.5 / (1.0 - hd[0]) if hd else 0.5
+        a_dh = ffs / (1.0 - hd[0]) if hd else ffs
         if keep is not None:     # k-contiguous conv of ga with the transposed weights, masked by the forward's keep bits
             ops.conv_fwd(ga, self._wt["w2"][2][pre + ".w2"], dh, T, c.ff_kernel - 1 - pad, alpha=a_dh, compute=self.cmp,
                          keep_in=keep, keep_layout=lay, colsum=gr[pre + ".b1"])
@@ -818,6 +827,131 @@ class ConformerStack(StepSchedule):
         self._conv_bwd(pre + ".cnv", pre + ".cnv", g, T, (gr[pre + ".mha.bo"], 1.0), pre + ".mha.o")
         self._mha_bwd(pre + ".mha", pre + ".mha", g, B, T, (gr[pre + ".ffm.b2"], 0.5), pre + ".ffm.o")
         self._ffn_bwd(pre + ".ffm", pre + ".ffm", g, T, None)
+        return g
+
+    # ------------------------------------------------------------------ one transformer block (plain attention, absolute positions)
+    def _tmha_fwd(self, tag, pre, x, keymask, B, T):
+        """MultiHeadedAttention (attention.py:64-122) behind its LayerNorm: scores q k^T * scale, no positional term -- no (q + u),
+        (q + v), linear_pos or band.  The three routes of _mha_fwd, chosen the same way (_attn_choice, attn_fused_supported): "fwd" /
+        "train" = the band-free instantiations of the fused kernels (a3t_attn_fwd_plain / a3t_attn_fwd_train_plain), "mat" =
+        a3t_softmax_plain_fwd between the two batched GEMMs; q is read in place from the fused projection."""
+        p, c = self.store.p, self.c
+        d, dk, H, cmp = c.adim, c.dk, c.heads, self.cmp
+        M = B * T
+        y = self._ln_fwd(tag + ".ln", x, pre + ".ln")
+        qkv = self._act(tag + ".qkv", (M, 3 * d))
+        ops.linear_fwd(y, self.W(pre + ".wqkv"), qkv, bias=p[pre + ".bqkv"], compute=cmp)
+        fused = (self._fused_now or self._fused_train_now) and ops.attn_fused_supported(dk, T)
+        route = "fwd" if (self._fused_now and fused) else "train" if (self._fused_train_now and fused) else "mat"
+        self.attn_path[tag[:-4]] = route
+        self.block_dims[tag[:-4]] = (B, T)
+        for k in (".rs", ".signed"):      # the markers of an earlier pass under this tag
+            self.sv.pop(tag + k, None)
+        scale = 1.0 / math.sqrt(dk)
+        adr = self._drop(c.attention_dropout_rate, tag + ".att")
+        ctx = self._act(tag + ".ctx", (M, d))
+        probs = pdrop = None
+        if route == "fwd":           # keeps nothing for a backward
+            lse = self.ws.get(tag + ".lse", (B, H, T))
+            ops.attn_fwd_plain(qkv, keymask, ctx, lse, B, H, T, scale, drop=adr or (0.0, 0))
+        elif route == "train":       # un-normalised probabilities, 1 / row sum in rs, the dropout mask on their sign bits (_attn_fwd_train)
+            probs = self._act(tag + ".probs", (B, H, T, T))
+            signed = bool(adr) and self.opt.attn_bwd_ds and self.opt.attn_signed and T <= 2048
+            pdrop = self._act(tag + ".pdrop", (B, H, T, T)) if adr and not signed else None
+            lse = self.ws.get(tag + ".lse", (B, H, T))
+            rs = self.ws.get(tag + ".rs", (B, H, T))
+            ops.attn_fwd_train_plain(qkv, keymask, ctx, lse, probs, pdrop, rs, B, H, T, scale, drop=adr or (0.0, 0))
+            self.sv[tag + ".signed"] = signed
+            self.sv[tag + ".rs"] = rs
+        else:
+            sdt = torch.bfloat16 if self.bf16 else torch.float32
+            ac = self.ws.get("tmp.ac", (B, H, T, T), sdt)
+            kk = qkv.view(-1)[d:]
+            vv = qkv.view(-1)[2 * d:]
+            zb, qb = (H * T * T, T * T), (T * 3 * d, dk)
+            ops.gemm(qkv, kk, ac, T, T, dk, 3 * d, 1, 3 * d, 1, T, batch=B * H, batch_inner=H, a_bs=qb, b_bs=qb, c_bs=zb, compute=cmp)
+            probs = self._act(tag + ".probs", (B, H, T, T))
+            pdrop = self._act(tag + ".pdrop", (B, H, T, T)) if adr else None
+            ops.softmax_plain_fwd(ac, keymask, probs, B, H, T, scale, probs_drop=pdrop, drop=adr or (0.0, 0))
+            ops.gemm(pdrop if adr else probs, vv, ctx, T, dk, T, T, 1, 1, 3 * d, d, batch=B * H, batch_inner=H, a_bs=zb, b_bs=qb,
+                     c_bs=(T * d, dk), compute=cmp)
+        xo = self.ws.get(tag + ".xo", (M, d))
+        ops.linear_fwd(ctx, self.W(pre + ".wo"), xo, bias=p[pre + ".bo"], R=x, compute=cmp,
+                       drop=self._drop(c.dropout_rate, tag + ".o"))
+        self.sv[tag] = None if route == "fwd" else (y, qkv, probs, ctx, pdrop)
+        return xo
+
+    def _tmha_bwd(self, tag, pre, g, B, T, nb=None, nxt=None):
+        """dS, then the three products around it: dq = dS K (one launch, no second operand pair), dK = dS^T q, dV = P^T dctx, all into
+        the thirds of dqkv.  Behind the fused training forward dS comes from the saved un-normalised probabilities in one launch
+        (a3t_attn_bwd_ds with dbd = NULL; dV reads the dropout mask off their sign bits), otherwise from the dprobs GEMM and
+        a3t_softmax_plain_bwd.  No positional-bias column sums and no linear_pos gradient; the bias of the fused projection is the
+        column sum of dqkv."""
+        gr, c = self.store.g, self.c
+        d, H, dk, cmp = c.adim, c.heads, c.dk, self.cmp
+        M = B * T
+        y, qkv, probs, ctx, pdrop = self.sv[tag]
+        self._sub_begin()
+        g16 = self._g16(g)
+        ga = self._gm(g, tag + ".o", c.dropout_rate, gr[pre + ".bo"], 1.0)
+        self._lin_wgrad(ga, ctx, gr[pre + ".wo"])
+        dctx = self._act("tmp.dctx", (M, d))
+        self._lin_dgrad(ga, pre + ".wo", dctx)
+        kk = qkv.view(-1)[d:]
+        vv = qkv.view(-1)[2 * d:]
+        dqkv = self._act(self._t("tmp.dqkv"), (M, 3 * d))
+        dkk = dqkv.view(-1)[d:]
+        dvv = dqkv.view(-1)[2 * d:]
+        sdt = torch.bfloat16 if self.bf16 else torch.float32
+        zb, qb = (H * T * T, T * T), (T * 3 * d, dk)
+        scale = 1.0 / math.sqrt(dk)
+        rs = self.sv.get(tag + ".rs")      # fused training forward: probs / pdrop are exp(s - m_ref), rs = 1 / row sum
+        signed = bool(self.sv.get(tag + ".signed"))      # ONE saved tensor: |probs| = the probability, sign = dropped
+        adr = self._drop(c.attention_dropout_rate, tag + ".att") if (pdrop is not None or signed) else None
+        regen = self.bf16 and adr is not None and T % 8 == 0 and T <= 2048      # the mask back from the counter RNG (_mha_bwd)
+        ds_fused = rs is not None and self.opt.attn_bwd_ds and (adr is None or regen) and ops.attn_fused_supported(dk, T)
+        assert ds_fused or not signed
+        dctx_v = dctx
+        if rs is not None:                 # dV = pdrop^T (rs * dctx): the row normalisation folded into the small operand
+            dctx_v = self._act("tmp.dctxs", (M, d))
+            ops.attn_scale_rows(dctx, rs, dctx_v, B, H, T)
+        ops.gemm(pdrop if pdrop is not None else probs, dctx_v, dvv, T, dk, T, 1, T, 1, d, 3 * d, batch=B * H, batch_inner=H,
+                 a_bs=zb, b_bs=(T * d, dk), c_bs=qb, compute=cmp, a_signmask=signed, alpha=1.0 / (1.0 - adr[0]) if signed else 1.0)
+        ds = self.ws.get("tmp.ds16", (B, H, T, T), torch.bfloat16) if self.bf16 else None
+        if ds_fused:
+            ops.attn_bwd_ds(dctx, ctx, qkv, probs, rs, ds, None, B, H, T, scale, drop=adr or (0.0, 0), signed_probs=signed)
+        else:
+            dpr = self.ws.get("tmp.ac", (B, H, T, T), sdt)      # (the score buffer of the forward)
+            ops.gemm(dctx, vv, dpr, T, T, dk, d, 1, 3 * d, 1, T, batch=B * H, batch_inner=H, a_bs=(T * d, dk), b_bs=qb, c_bs=zb,
+                     compute=cmp)
+            if ds is None:
+                ds = dpr                                        # (fp32: in place)
+            ops.softmax_plain_bwd(probs, dpr, ds, B, H, T, scale, probs_drop=None if regen else pdrop,
+                                  drop_p=adr[0] if adr else 0.0, drop_key=adr[1] if regen else 0, rowscale=rs)
+        ops.gemm(ds, kk, dqkv, T, dk, T, T, 1, 1, 3 * d, 3 * d, batch=B * H, batch_inner=H, a_bs=zb, b_bs=qb, c_bs=qb, compute=cmp)
+        ops.gemm(ds, qkv, dkk, T, dk, T, 1, T, 1, 3 * d, 3 * d, batch=B * H, batch_inner=H, a_bs=zb, b_bs=qb, c_bs=qb, compute=cmp)
+        self._bias_grad(dqkv, gr[pre + ".bqkv"])
+        self._lin_wgrad(dqkv, y, gr[pre + ".wqkv"])
+        dy = self._act("tmp.dy", (M, d))
+        self._lin_dgrad(dqkv, pre + ".wqkv", dy)
+        self._pre_ln(ga, g, g16)
+        self._ln_bwd(tag + ".ln", dy, pre + ".ln", g, g, g16, nb, nxt)
+        self._sub_end()
+        return g
+
+    def tblock_fwd(self, pre, x, keymask, B, T):
+        """x += drop(out(attn(ln1 x))); x += drop(ffn(ln2 x))  (transformer/encoder_layer.py:62-121, normalize_before, no
+        concat_after); no LayerNorm closes the block."""
+        x = self._tmha_fwd(pre + ".mha", pre + ".mha", x, keymask, B, T)
+        return self._ffn_fwd(pre + ".ff", pre + ".ff", x, T)
+
+    def tblock_bwd(self, pre, g, B, T, prev=None):
+        """prev: the block in front of this one in the same stack (None for the first) -- its FFN wrote the residual stream this
+        block's first LayerNorm read, so that LayerNorm's backward delivers prev.ff.b2's gradient (block_bwd)."""
+        gr = self.store.g
+        self._ffn_bwd(pre + ".ff", pre + ".ff", g, T, (gr[pre + ".mha.bo"], 1.0), pre + ".mha.o")
+        self._tmha_bwd(pre + ".mha", pre + ".mha", g, B, T, (gr[prev + ".ff.b2"], 1.0) if prev else None,
+                       prev + ".ff.o" if prev else None)
         return g
 
     def _attn_choice(self, B, T, need_grad):

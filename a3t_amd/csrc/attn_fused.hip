@@ -261,7 +261,9 @@ struct DT16 {   // 32-row x DK tile, DMA-filled by 8 waves, swizzled for 16-row 
     }
 };
 
-template <int NDB>
+// PLAIN (MultiHeadedAttention, attention.py:64-122: a transformer model's blocks): scores = q k^T * scale and nothing else -- no
+// (q+v) fragments, no Pext ring or its DMA, no band MFMAs, no band scratch.  qu holds q; qv, pos, bu, bv are not read.
+template <int NDB, bool PLAIN = false>
 __global__ __launch_bounds__(512, 2) void attn_fwd16_kernel(AttnArgs p) {
     using D = DT16<NDB>;
     constexpr int DK = D::DK, KS = NDB, NDT = 2 * NDB, TB = D::BYTES;
@@ -284,10 +286,10 @@ __global__ __launch_bounds__(512, 2) void attn_fwd16_kernel(AttnArgs p) {
     const int Q0 = qb * 128, q0 = Q0 + 16 * w, i = q0 + lq;
     const int XB = T - Q0 - 128;                         // band block n (16 rows) covers x in [XB + 16 n, +16); ring tile u = blocks 2u, 2u+1
     const u16* quB = p.qu + (int64_t)b * T * p.ldq + h * DK;
-    const u16* qvB = p.qv + (int64_t)b * T * p.ldq + h * DK;
+    const u16* qvB = PLAIN ? nullptr : p.qv + (int64_t)b * T * p.ldq + h * DK;
     const u16* kB = p.k + (int64_t)b * T * p.ldkv + h * DK;
     const u16* vB = p.v + (int64_t)b * T * p.ldkv + h * DK;
-    const u16* pB = p.pos + h * DK;
+    const u16* pB = PLAIN ? nullptr : p.pos + h * DK;
     const uint8_t* mkB = p.keymask + (int64_t)b * T;
     float* scw = sc + w * 16 * SC16_LD;
 
@@ -299,9 +301,11 @@ __global__ __launch_bounds__(512, 2) void attn_fwd16_kernel(AttnArgs p) {
 
     D::issue(Kb, kB, p.ldkv, w, lane, [&](int r) { return krow(0, r); });
     D::issue(Vb, vB, p.ldkv, w, lane, [&](int r) { return krow(0, r); });
+    if constexpr (!PLAIN) {
 #pragma unroll
-    for (int u = 0; u < 5; ++u) D::issue(Pr + u * TB, pB, p.ldp, w, lane, [&](int r) { return prow(u, r); });
-    const bool biased = p.bu != nullptr;
+        for (int u = 0; u < 5; ++u) D::issue(Pr + u * TB, pB, p.ldp, w, lane, [&](int r) { return prow(u, r); });
+    }
+    const bool biased = !PLAIN && p.bu != nullptr;
     if (biased) {
         if (tid < DK) pbl[tid] = p.bu[h * DK + tid], pbl[DK + tid] = p.bv[h * DK + tid];
         __syncthreads();
@@ -313,7 +317,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd16_kernel(AttnArgs p) {
     for (int kk = 0; kk < KS; ++kk) {
         const int off = 32 * kk + 8 * PI;
         fqu[kk] = ld_frag_qb(quB + (int64_t)i * p.ldq + off, i < T, pbu + off, biased);
-        fqv[kk] = ld_frag_qb(qvB + (int64_t)i * p.ldq + off, i < T, pbv + off, biased);
+        if constexpr (!PLAIN) fqv[kk] = ld_frag_qb(qvB + (int64_t)i * p.ldq + off, i < T, pbv + off, biased);
     }
     for (int sb = w; sb < NS; sb += 8) {
         const int jl = 32 * sb + (lane & 31);
@@ -343,7 +347,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd16_kernel(AttnArgs p) {
     auto band_store = [&](int n, const f32x4& acc) {
         *(float4*)(scw + lq * SC16_LD + 16 * (n & 3) + 4 * lg) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     };
-    {
+    if constexpr (!PLAIN) {
         const int n = 7 - w;
         band_switch(n);
         band_store(n, band_block(n));
@@ -360,7 +364,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd16_kernel(AttnArgs p) {
         const unsigned char* Kt = Kb + (s & 1) * TB;
         const unsigned char* Vt = Vb + (s & 1) * TB;
         const int n0 = 7 - w + 2 * s;                    // tile uses band blocks n0, n0+1, n0+2 (n0 from the previous step)
-        band_switch(n0 + 1);                             // (a 16-block never straddles x = T; both new blocks share a side
+        if constexpr (!PLAIN) band_switch(n0 + 1);       // (a 16-block never straddles x = T; both new blocks share a side
         PHASE_FENCE();                                   //  unless n0+2 is the first upper one, handled below)
         // ---- S^T (two 16-key halves) and the two new band blocks ---------------------------------------------------------
         f32x4 sa0 = zero4(), sa1 = zero4();
@@ -369,11 +373,13 @@ __global__ __launch_bounds__(512, 2) void attn_fwd16_kernel(AttnArgs p) {
             sa0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(D::rows(Kt, lq, 4 * kk + PI), fqu[kk], sa0, 0, 0, 0);
             sa1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(D::rows(Kt, 16 + lq, 4 * kk + PI), fqu[kk], sa1, 0, 0, 0);
         }
-        const f32x4 b1 = band_block(n0 + 1);
-        band_store(n0 + 1, b1);
-        band_switch(n0 + 2);
-        const f32x4 b2 = band_block(n0 + 2);
-        band_store(n0 + 2, b2);
+        if constexpr (!PLAIN) {
+            const f32x4 b1 = band_block(n0 + 1);
+            band_store(n0 + 1, b1);
+            band_switch(n0 + 2);
+            const f32x4 b2 = band_block(n0 + 2);
+            band_store(n0 + 2, b2);
+        }
         PHASE_FENCE();
         // ---- skewed band read: (query ii, key kk) <- band column 15 - ii + kk of blocks n0 .. n0+2 ------------------------
         const unsigned int vm = kmw[s];
@@ -381,18 +387,18 @@ __global__ __launch_bounds__(512, 2) void attn_fwd16_kernel(AttnArgs p) {
         const float* srow = scw + lq * SC16_LD;
         float sv[8];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) sv[r] = srow[(c0 + (r & 3) + 16 * (r >> 2)) & 63];
+        for (int r = 0; r < 8; ++r) sv[r] = PLAIN ? 0.f : srow[(c0 + (r & 3) + 16 * (r >> 2)) & 63];
         asm volatile("" ::: "memory");
         if (s + 1 < NS) {   // next tiles by DMA (after this step's last LDS write, see the 32-query kernel)
             D::issue(Kb + ((s + 1) & 1) * TB, kB, p.ldkv, w, lane, [&](int r) { return krow(s + 1, r); });
             D::issue(Vb + ((s + 1) & 1) * TB, vB, p.ldkv, w, lane, [&](int r) { return krow(s + 1, r); });
-            D::issue(Pr + ((s + 5) % 6) * TB, pB, p.ldp, w, lane, [&](int r) { return prow(s + 5, r); });
+            if constexpr (!PLAIN) D::issue(Pr + ((s + 5) % 6) * TB, pB, p.ldp, w, lane, [&](int r) { return prow(s + 5, r); });
         }
         float mloc = NEG_INF;
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const int kk = (r & 3) + 16 * (r >> 2) + 4 * lg;
-            const float x = ((r < 4 ? sa0[r & 3] : sa1[r & 3]) + sv[r]) * p.scale;
+            const float x = PLAIN ? (r < 4 ? sa0[r & 3] : sa1[r & 3]) * p.scale : ((r < 4 ? sa0[r & 3] : sa1[r & 3]) + sv[r]) * p.scale;
             sv[r] = ((vm >> kk) & 1u) ? x : NEG_INF;
             mloc = fmaxf(mloc, sv[r]);
         }
@@ -497,7 +503,9 @@ __device__ __forceinline__ f32x16 mfma32(const bf16x8& a, const bf16x8& b, const
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
-template <int NDB, bool DROP, bool SAVE, bool TWOPASS = false, bool SPLIT = false, bool SGN = false>
+// PLAIN: the band-free instantiation (see attn_fwd16_kernel) -- one MFMA chain per product stage instead of two, no ring DMA, the
+// scratch and ring areas of the LDS layout stay where they are and are not touched.  Everything around the scores is the same code.
+template <int NDB, bool DROP, bool SAVE, bool TWOPASS = false, bool SPLIT = false, bool SGN = false, bool PLAIN = false>
 __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
     // SGN (training with dropout, probs_drop == NULL): ONE saved tensor -- probs = exp(s - m_ref) with the sign bit set where the
     // dropout mask dropped the element.  Its readers take |x| as the probability and the sign as the mask (a3t_attn_bwd_ds,
@@ -556,16 +564,16 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
     const int Q0 = qb * 128, q0 = Q0 + 32 * w, i = q0 + lr;
     const int X0 = T - 32 - Q0;                          // band block u covers x in [X0 + 32 (u - 3), +32)
     const u16* quB = p.qu + (int64_t)b * T * p.ldq + h * DK;
-    const u16* qvB = p.qv + (int64_t)b * T * p.ldq + h * DK;
+    const u16* qvB = PLAIN ? nullptr : p.qv + (int64_t)b * T * p.ldq + h * DK;
     const u16* kB = p.k + (int64_t)b * T * p.ldkv + h * DK;
     const u16* vB = p.v + (int64_t)b * T * p.ldkv + h * DK;
-    const u16* pB = p.pos + h * DK;
+    const u16* pB = PLAIN ? kB : p.pos + h * DK;          // (PLAIN: a descriptor nobody issues a load through)
     const uint8_t* mkB = p.keymask + (int64_t)b * T;
     float* scw = sc + w * 32 * SC_LD;
 
     // this head's pos_bias_u | pos_bias_v (when the kernel adds them) in the staging area of the probability stores, which is
     // idle until the key loop; the barrier below publishes them
-    const bool biased = p.bu != nullptr;
+    const bool biased = !PLAIN && p.bu != nullptr;
     float* pbl = (float*)stg;
     if (biased && tid < DK) pbl[tid] = p.bu[h * DK + tid], pbl[DK + tid] = p.bv[h * DK + tid];
     // ---- key-mask words; the first tile with a valid key (the same for every query: the mask is per key) ----------------
@@ -636,6 +644,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
             dma16(r, smem0 + (unsigned)(tile - smem) + (q * 4 + w) * 1024, voffK[q] + (unsigned)(32 * s) * ldkv2);
     };
     auto issue_p1 = [&](int u, const int q) __attribute__((always_inline)) {
+        if constexpr (PLAIN) return;
         if (q < NPW || (q * 4 + w) * 1024 < TB) {
             const int x = X0 + 32 * (u - 3) + drow[q];
             const int xr = x < T ? x : x - T - 1;
@@ -663,8 +672,10 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
         const int off = 16 * kk + 8 * lh;
         const lds_cfp bu8 = (lds_cfp)LDS_AS(pbl + off), bv8 = (lds_cfp)LDS_AS(pbl + DK + off);
         fqu[kk] = ld_frag_qb(quB + (int64_t)i * p.ldq + off, i < T, bu8, biased);
-        fqvL[kk] = ld_frag_qb(qvB + (int64_t)i * p.ldq + off, i < T, bv8, biased);
-        fqvU[kk] = ld_frag_qb(qvB + (int64_t)(i + 1) * p.ldq + off, i + 1 < T, bv8, biased);
+        if constexpr (!PLAIN) {
+            fqvL[kk] = ld_frag_qb(qvB + (int64_t)i * p.ldq + off, i < T, bv8, biased);
+            fqvU[kk] = ld_frag_qb(qvB + (int64_t)(i + 1) * p.ldq + off, i + 1 < T, bv8, biased);
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the DMA (invisible to the compiler) and the fragment loads
     __syncthreads();
@@ -734,8 +745,8 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
     // ---- prologue: S(s0), both band blocks of step s0, the reference maximum ---------------------------------------------
     const float sl2 = p.scale * 1.4426950408889634f;     // exponentials in base 2: p = exp2(s sl2 - m2)
     f32x16 Sc = s_mm(Kb + (s0 & 1) * TB);
-    float bd[16];
-    {
+    float bd[16];                                         // (PLAIN: there is no band, bd is never read)
+    if constexpr (!PLAIN) {
         const int u = s0 - w + 3;
         band_store(u, band_mm(u));
         band_store(u + 1, band_mm(u + 1));
@@ -748,7 +759,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int kk = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if ((vm >> kk) & 1u) mx = fmaxf(mx, (S_[r] + bd_[r]) * sl2);
+            if ((vm >> kk) & 1u) mx = fmaxf(mx, (PLAIN ? S_[r] : S_[r] + bd_[r]) * sl2);
         }
         return fmaxf(mx, __shfl_xor(mx, 32, 64));
     };
@@ -766,10 +777,12 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
             __syncthreads();
             const f32x16 S2 = s_mm(Kb + (s & 1) * TB);
             float bd2[16];
-            const int u = s - w + 3;
-            band_store(u, band_mm(u));
-            band_store(u + 1, band_mm(u + 1));
-            band_read(u, bd2);
+            if constexpr (!PLAIN) {
+                const int u = s - w + 3;
+                band_store(u, band_mm(u));
+                band_store(u + 1, band_mm(u + 1));
+                band_read(u, bd2);
+            }
             m2 = fmaxf(m2, tile_max(s, S2, bd2));
         }
     }
@@ -790,10 +803,12 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         Sc = s_mm(Kb + (sa & 1) * TB);
-        const int u = sa - w + 3;
-        band_store(u, band_mm(u));
-        band_store(u + 1, band_mm(u + 1));
-        band_read(u, bd);
+        if constexpr (!PLAIN) {
+            const int u = sa - w + 3;
+            band_store(u, band_mm(u));
+            band_store(u + 1, band_mm(u + 1));
+            band_read(u, bd);
+        }
     }
     __syncthreads();                                      // every wave is through with ring tile sa
     issue_p(sa + 5);
@@ -827,7 +842,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
     auto rd = [&](const int t, const unsigned char* Kt, const unsigned char* slot, const int Vt) __attribute__((always_inline)) {
         if (t < KS) {
             st[t % 3][0] = frag_rows(Kt, t);
-            st[t % 3][1] = frag_rows(slot, t);
+            if constexpr (!PLAIN) st[t % 3][1] = frag_rows(slot, t);
         } else if (t < NSTG) {
             st[t % 3][0] = frag_cols(Vt, 0, t - KS);
             st[t % 3][1] = frag_cols(Vt, 1, t - KS);
@@ -847,7 +862,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
         unsigned int sw[8];       // SG: the tile's sixteen tagged probabilities as packed bf16 pairs (quad g -> sw[2 g], sw[2 g + 1])
         float psum = 0.f;
         auto expo = [&](const int r) __attribute__((always_inline)) {
-            const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(Sc[r] + bd[r], sl2, -m2));
+            const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(PLAIN ? Sc[r] : Sc[r] + bd[r], sl2, -m2));
             pv[r] = (!msk || ((vm >> ((r & 3) + 8 * (r >> 2))) & 1u)) ? e : 0.f;
             psum += pv[r];
         };
@@ -933,7 +948,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
             TSTAMP(5 + t);
             rd(t + 2, Kt, slot, Vt);
             Sn = mfma32(st[t % 3][0], fqu[t], Sn);
-            Bn = mfma32(st[t % 3][1], up ? fqvU[t] : fqvL[t], Bn);
+            if constexpr (!PLAIN) Bn = mfma32(st[t % 3][1], up ? fqvU[t] : fqvL[t], Bn);
             // this iteration's tile DMA, one 1-KiB piece per stage (an LDS-DMA instruction holds the issue port for 50-150
             // cycles: under the MFMAs here, not in front of them): K(s+2), V(s+1), ring tile s+6 -- all three targets were
             // last read in iteration s-1
@@ -973,9 +988,9 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
             const int d = t - KS;
             O[d] = mfma32(st[t % 3][0], pf0, O[d]);
             O[d] = mfma32(st[t % 3][1], pf1, O[d]);
-            if (d == 0) band_store(un, Bn);
+            if (!PLAIN && d == 0) band_store(un, Bn);
             if (SAVE && DROP && d == (NDB > 2 ? 2 : NDB - 1)) flush_d(s);
-            if (d == 1 || NDB == 1) band_read(un - 1, bd);
+            if (!PLAIN && (d == 1 || NDB == 1)) band_read(un - 1, bd);
             PHASE_FENCE();
         }
         TSTAMP(3);
@@ -990,7 +1005,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd32_kernel(AttnArgs p) {
         TSTAMP(0);
         TSTAMP(1);
         const bool full = __builtin_amdgcn_readfirstlane(kmw[s]) == 0xffffffffu;
-        if (use_upper(s + 1 - w + 4)) {
+        if (!PLAIN && use_upper(s + 1 - w + 4)) {
             if (full) products(TrueT(), FalseT(), s);
             else products(TrueT(), TrueT(), s);
         } else {
@@ -1452,7 +1467,7 @@ extern "C" int a3t_attn_split_mode(int mode) {
     return old;
 }
 
-template <int NDB>
+template <int NDB, bool PLAIN = false>
 static int launch_fwd16(const AttnArgs& a, hipStream_t s) {
     constexpr int TB = DT16<NDB>::BYTES;
     constexpr int lds = 10 * TB + 8 * 16 * SC16_LD * 4 + 4 * 128 + 2 * 32 * NDB * 4;
@@ -1485,14 +1500,14 @@ static int launch_fwd16(const AttnArgs& a, hipStream_t s) {
         const bool split = at.part_ws != nullptr;
 #define A3T_L32(DR, SV, SG)                                                                                                             \
     do {                                                                                                                             \
-        (void)hipFuncSetAttribute((const void*)attn_fwd32_kernel<NDB, DR, SV, false, false, SG>, hipFuncAttributeMaxDynamicSharedMemorySize, lds32);   \
+        (void)hipFuncSetAttribute((const void*)attn_fwd32_kernel<NDB, DR, SV, false, false, SG, PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds32);   \
         if (split) {                                                                                                                 \
-            (void)hipFuncSetAttribute((const void*)attn_fwd32_kernel<NDB, DR, SV, false, true, SG>,                                      \
+            (void)hipFuncSetAttribute((const void*)attn_fwd32_kernel<NDB, DR, SV, false, true, SG, PLAIN>,                               \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds32);                                            \
-            hipLaunchKernelGGL((attn_fwd32_kernel<NDB, DR, SV, false, true, SG>), dim3(nfull + ntail * nparts), dim3(256), lds32, s, at); \
+            hipLaunchKernelGGL((attn_fwd32_kernel<NDB, DR, SV, false, true, SG, PLAIN>), dim3(nfull + ntail * nparts), dim3(256), lds32, s, at); \
             hipLaunchKernelGGL(attn_split_finish_kernel, dim3(ntail * 32), dim3(256), 0, s, at, (int)ntail, DT32<NDB>::DK);            \
         } else {                                                                                                                     \
-            hipLaunchKernelGGL((attn_fwd32_kernel<NDB, DR, SV, false, false, SG>), dim3(grid), dim3(256), lds32, s, a);                                 \
+            hipLaunchKernelGGL((attn_fwd32_kernel<NDB, DR, SV, false, false, SG, PLAIN>), dim3(grid), dim3(256), lds32, s, a);                          \
         }                                                                                                                            \
     } while (0)
         if (a.probs) {
@@ -1500,16 +1515,16 @@ static int launch_fwd16(const AttnArgs& a, hipStream_t s) {
             // a first sweep for the true row maximum (every block but the flagged ones exits at once)
             if (a.drop_thr && !a.pdrop) {       // one saved tensor: the dropout mask rides on the sign bits of probs
                 A3T_L32(true, true, true);
-                (void)hipFuncSetAttribute((const void*)attn_fwd32_kernel<NDB, true, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds32);
-                hipLaunchKernelGGL((attn_fwd32_kernel<NDB, true, true, true, false, true>), dim3(grid), dim3(256), lds32, s, a);
+                (void)hipFuncSetAttribute((const void*)attn_fwd32_kernel<NDB, true, true, true, false, true, PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds32);
+                hipLaunchKernelGGL((attn_fwd32_kernel<NDB, true, true, true, false, true, PLAIN>), dim3(grid), dim3(256), lds32, s, a);
             } else if (a.drop_thr) {
                 A3T_L32(true, true, false);
-                (void)hipFuncSetAttribute((const void*)attn_fwd32_kernel<NDB, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds32);
-                hipLaunchKernelGGL((attn_fwd32_kernel<NDB, true, true, true>), dim3(grid), dim3(256), lds32, s, a);
+                (void)hipFuncSetAttribute((const void*)attn_fwd32_kernel<NDB, true, true, true, false, false, PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds32);
+                hipLaunchKernelGGL((attn_fwd32_kernel<NDB, true, true, true, false, false, PLAIN>), dim3(grid), dim3(256), lds32, s, a);
             } else {
                 A3T_L32(false, true, false);
-                (void)hipFuncSetAttribute((const void*)attn_fwd32_kernel<NDB, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds32);
-                hipLaunchKernelGGL((attn_fwd32_kernel<NDB, false, true, true>), dim3(grid), dim3(256), lds32, s, a);
+                (void)hipFuncSetAttribute((const void*)attn_fwd32_kernel<NDB, false, true, true, false, false, PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds32);
+                hipLaunchKernelGGL((attn_fwd32_kernel<NDB, false, true, true, false, false, PLAIN>), dim3(grid), dim3(256), lds32, s, a);
             }
             return (int)hipGetLastError();
         } else {
@@ -1519,8 +1534,8 @@ static int launch_fwd16(const AttnArgs& a, hipStream_t s) {
 #undef A3T_L32
         a16.use_redo = 1;        // the same grid again: a block exits at once unless its row sums overflowed
     }
-    (void)hipFuncSetAttribute((const void*)attn_fwd16_kernel<NDB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL(attn_fwd16_kernel<NDB>, dim3(grid), dim3(512), lds, s, a16);
+    (void)hipFuncSetAttribute((const void*)attn_fwd16_kernel<NDB, PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL((attn_fwd16_kernel<NDB, PLAIN>), dim3(grid), dim3(512), lds, s, a16);
     return (int)hipGetLastError();
 }
 
@@ -1609,6 +1624,7 @@ extern "C" int a3t_attn_scale_rows(const void* x, const float* rowscale, void* y
     return (int)hipGetLastError();
 }
 
+template <bool PLAIN = false>
 static int attn_fwd_impl(const void* qu, const void* qv, const void* k, const void* v, const void* pos,
                          const uint8_t* keymask, void* ctx, float* lse, void* probs, void* probs_drop, float* rowscale, int B,
                          int H, int T, int dk, int64_t ldq, int64_t ldkv, int64_t ldp, int64_t ldo, float scale, float drop_p,
@@ -1616,6 +1632,7 @@ static int attn_fwd_impl(const void* qu, const void* qv, const void* k, const vo
     if (!attn_shape_ok(dk, T)) return A3T_EINVAL;
     if ((bias_u == nullptr) != (bias_v == nullptr) || !al16(bias_u) || !al16(bias_v)) return A3T_EINVAL;
     if (!(al16(qu) && al16(qv) && al16(k) && al16(v) && al16(pos) && al16(ctx))) return A3T_EINVAL;
+    if (PLAIN && (!qu || !k || !v || !keymask || !ctx || !lse)) return A3T_EINVAL;
     if ((ldq % 8) || (ldkv % 8) || (ldp % 8) || (ldo % 4)) return A3T_EINVAL;
     if (drop_p < 0.f || drop_p >= 1.f) return A3T_EINVAL;
     AttnArgs a = {};
@@ -1630,11 +1647,11 @@ static int attn_fwd_impl(const void* qu, const void* qv, const void* k, const vo
     a.drop_key = drop_key, a.drop_inv = 1.f / (1.f - drop_p);
     hipStream_t s = (hipStream_t)stream;
     switch (dk / 32) {
-        case 1: return launch_fwd16<1>(a, s);
-        case 2: return launch_fwd16<2>(a, s);
-        case 3: return launch_fwd16<3>(a, s);
-        case 4: return launch_fwd16<4>(a, s);
-        case 6: return launch_fwd16<6>(a, s);
+        case 1: return launch_fwd16<1, PLAIN>(a, s);
+        case 2: return launch_fwd16<2, PLAIN>(a, s);
+        case 3: return launch_fwd16<3, PLAIN>(a, s);
+        case 4: return launch_fwd16<4, PLAIN>(a, s);
+        case 6: return launch_fwd16<6, PLAIN>(a, s);
     }
     return A3T_EINVAL;
 }
@@ -1643,7 +1660,7 @@ extern "C" int a3t_attn_fwd(const void* qu, const void* qv, const void* k, const
                             const uint8_t* keymask, void* ctx, float* lse, int B, int H, int T, int dk, int64_t ldq,
                             int64_t ldkv, int64_t ldp, int64_t ldo, float scale, float drop_p, uint32_t drop_key,
                             const float* bias_u, const float* bias_v, void* stream) {
-    return attn_fwd_impl(qu, qv, k, v, pos, keymask, ctx, lse, nullptr, nullptr, nullptr, B, H, T, dk, ldq, ldkv, ldp, ldo, scale,
+    return attn_fwd_impl<false>(qu, qv, k, v, pos, keymask, ctx, lse, nullptr, nullptr, nullptr, B, H, T, dk, ldq, ldkv, ldp, ldo, scale,
                          drop_p, drop_key, bias_u, bias_v, stream);
 }
 
@@ -1654,6 +1671,24 @@ extern "C" int a3t_attn_fwd_train(const void* qu, const void* qv, const void* k,
                                   const float* bias_v, void* stream) {
     if (!probs || !rowscale || (T % 8)) return A3T_EINVAL;      // (drop_p > 0 without probs_drop: the sign-tagged single tensor)
     if (((uintptr_t)probs & 7) || ((uintptr_t)probs_drop & 7)) return A3T_EINVAL;
-    return attn_fwd_impl(qu, qv, k, v, pos, keymask, ctx, lse, probs, drop_p > 0.f ? probs_drop : nullptr, rowscale, B, H, T, dk, ldq,
+    return attn_fwd_impl<false>(qu, qv, k, v, pos, keymask, ctx, lse, probs, drop_p > 0.f ? probs_drop : nullptr, rowscale, B, H, T, dk, ldq,
                          ldkv, ldp, ldo, scale, drop_p, drop_key, bias_u, bias_v, stream);
+}
+
+/* The band-free instantiations (a transformer model's MultiHeadedAttention): scores = q k^T * scale.  q [B*T][ldq]; there is no
+ * (q + v), no positional table and no bias -- the kernels are compiled without everything that feeds the band. */
+extern "C" int a3t_attn_fwd_plain(const void* q, const void* k, const void* v, const uint8_t* keymask, void* ctx, float* lse, int B,
+                                  int H, int T, int dk, int64_t ldq, int64_t ldkv, int64_t ldo, float scale, float drop_p,
+                                  uint32_t drop_key, void* stream) {
+    return attn_fwd_impl<true>(q, q, k, v, nullptr, keymask, ctx, lse, nullptr, nullptr, nullptr, B, H, T, dk, ldq, ldkv, 8, ldo, scale,
+                               drop_p, drop_key, nullptr, nullptr, stream);
+}
+
+extern "C" int a3t_attn_fwd_train_plain(const void* q, const void* k, const void* v, const uint8_t* keymask, void* ctx, float* lse,
+                                        void* probs, void* probs_drop, float* rowscale, int B, int H, int T, int dk, int64_t ldq,
+                                        int64_t ldkv, int64_t ldo, float scale, float drop_p, uint32_t drop_key, void* stream) {
+    if (!probs || !rowscale || (T % 8)) return A3T_EINVAL;
+    if (((uintptr_t)probs & 7) || ((uintptr_t)probs_drop & 7)) return A3T_EINVAL;
+    return attn_fwd_impl<true>(q, q, k, v, nullptr, keymask, ctx, lse, probs, drop_p > 0.f ? probs_drop : nullptr, rowscale, B, H, T,
+                               dk, ldq, ldkv, 8, ldo, scale, drop_p, drop_key, nullptr, nullptr, stream);
 }

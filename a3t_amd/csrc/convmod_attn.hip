@@ -458,7 +458,8 @@ __device__ __forceinline__ float bd_shift(const void* __restrict__ BDz, int dt, 
 // RAGGED (fp32, no dropout): row b of the padded batch has n = lens[b] frames and is computed as if it had been passed alone:
 // the keys are j < n (keymask is not read), the shift is taken at n, and the query rows i >= n are stored as 0 (probs @ V
 // must read zeros there).
-template <int NV, bool RAGGED>
+// PLAIN (MultiHeadedAttention, attention.py:64-122): no positional term -- bd is not read, the scores are ac * scale.
+template <int NV, bool RAGGED, bool PLAIN = false>
 __global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(const void* __restrict__ ac,
                                                                  const void* __restrict__ bd, int s_dt,
                                                                  const uint8_t* __restrict__ keymask,
@@ -493,6 +494,7 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(const void* __r
     };
     const int64_t po = zz * p_bs + (int64_t)i * T;
     const float NEG = -3.4028235e38f;
+#define SM_SCORE(j) ((PLAIN ? ldx(ac, s_dt, ao + (j)) : ldx(ac, s_dt, ao + (j)) + bd_shift(bz, s_dt, T, n, i, (j))) * scale)
     if (NV > 0) {
         float v[NV > 0 ? NV : 1];
         float mx = NEG;
@@ -500,7 +502,7 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(const void* __r
         for (int q = 0; q < NV; ++q) {
             int j = lane + q * 64;
             v[q] = NEG;
-            if (j < T && valid(j)) v[q] = (ldx(ac, s_dt, ao + j) + bd_shift(bz, s_dt, T, n, i, j)) * scale;
+            if (j < T && valid(j)) v[q] = SM_SCORE(j);
             mx = fmaxf(mx, v[q]);
         }
         mx = wmax(mx);
@@ -527,7 +529,7 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(const void* __r
     int any = 0;
     for (int j = lane; j < T; j += 64)
         if (valid(j)) {
-            mx = fmaxf(mx, (ldx(ac, s_dt, ao + j) + bd_shift(bz, s_dt, T, n, i, j)) * scale);
+            mx = fmaxf(mx, SM_SCORE(j));
             any = 1;
         }
     mx = wmax(mx);
@@ -541,14 +543,15 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(const void* __r
     }
     float s = 0.f;
     for (int j = lane; j < T; j += 64)
-        if (valid(j)) s += expf((ldx(ac, s_dt, ao + j) + bd_shift(bz, s_dt, T, n, i, j)) * scale - mx);
+        if (valid(j)) s += expf(SM_SCORE(j) - mx);
     s = wsum(s);
     const float inv_s = 1.f / s;
     for (int j = lane; j < T; j += 64) {
-        const float pj = valid(j) ? expf((ldx(ac, s_dt, ao + j) + bd_shift(bz, s_dt, T, n, i, j)) * scale - mx) * inv_s : 0.f;
+        const float pj = valid(j) ? expf(SM_SCORE(j) - mx) * inv_s : 0.f;
         stx(probs, p_dt, po + j, pj);
         if (pdrop) stx(pdrop, p_dt, po + j, rng_keep(key, (unsigned int)(po + j), thr) ? pj * inv : 0.f);
     }
+#undef SM_SCORE
 }
 
 // ---- all-bf16 fast path (bf16 compute mode): T % 8 == 0, every lane owns NC chunks of 8 consecutive keys, so the
@@ -565,7 +568,7 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
     return u;
 }
 
-template <int NC>
+template <int NC, bool PLAIN = false>
 __global__ __launch_bounds__(256) void relpos_softmax_fwd_bf16_kernel(
     const unsigned short* __restrict__ ac, const unsigned short* __restrict__ bd, const uint8_t* __restrict__ keymask,
     unsigned short* __restrict__ probs, int H, int T, int64_t ac_bs, int64_t bd_bs, int64_t p_bs, float scale,
@@ -595,7 +598,10 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_bf16_kernel(
             unpack8(*(const uint4*)(ar + j0), a);
             const uint2 m2 = *(const uint2*)(mk + j0);
             float bv[8];
-            if (j0 + 7 <= i) {
+            if constexpr (PLAIN) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) bv[e] = 0.f;
+            } else if (j0 + 7 <= i) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) bv[e] = bf2f_(b0[j0 + e]);
             } else if (j0 >= i + 2) {
@@ -611,7 +617,7 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_bf16_kernel(
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const unsigned int mb = ((e < 4 ? m2.x : m2.y) >> (8 * (e & 3))) & 0xff;
-                if (mb) v[q][e] = (a[e] + bv[e]) * scale;
+                if (mb) v[q][e] = PLAIN ? a[e] * scale : (a[e] + bv[e]) * scale;
                 mx = fmaxf(mx, v[q][e]);
             }
         }
@@ -668,13 +674,13 @@ __global__ __launch_bounds__(256) void relpos_softmax_fwd_bf16_kernel(
 static inline bool sm_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // one launcher for the plain entry point (lens == nullptr) and the ragged one (keymask == nullptr, no dropout)
-template <bool RAGGED>
+template <bool RAGGED, bool PLAIN = false>
 static int relpos_softmax_fwd_launch(const void* ac, const void* bd, int scores_dtype, const uint8_t* keymask, void* probs,
                                      int probs_dtype, int H, int T, int64_t ac_bs, int64_t bd_bs, int64_t p_bs, float scale,
                                      int64_t nrows, void* probs_drop, unsigned int thr, float dinv, uint32_t drop_key,
                                      const int32_t* lens, hipStream_t stream) {
 #define CALL(NV)                                                                                                       \
-    hipLaunchKernelGGL((relpos_softmax_fwd_kernel<NV, RAGGED>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, stream, ac, \
+    hipLaunchKernelGGL((relpos_softmax_fwd_kernel<NV, RAGGED, PLAIN>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, stream, ac, \
                        bd, scores_dtype, keymask, probs, probs_dtype, H, T, ac_bs, bd_bs, p_bs, scale, nrows, probs_drop,  \
                        thr, dinv, drop_key, lens)
     SM_DISPATCH(T, CALL);
@@ -682,10 +688,11 @@ static int relpos_softmax_fwd_launch(const void* ac, const void* bd, int scores_
     return (int)hipGetLastError();
 }
 
-extern "C" int a3t_relpos_softmax_fwd(const void* ac, const void* bd, int scores_dtype, const uint8_t* keymask,
-                                      void* probs, int probs_dtype, int B, int H, int T, int64_t ac_bs, int64_t bd_bs,
-                                      int64_t p_bs, float scale, void* probs_drop, float drop_p, uint32_t drop_key,
-                                      void* stream) {
+template <bool PLAIN>
+static int softmax_fwd_entry(const void* ac, const void* bd, int scores_dtype, const uint8_t* keymask,
+                             void* probs, int probs_dtype, int B, int H, int T, int64_t ac_bs, int64_t bd_bs,
+                             int64_t p_bs, float scale, void* probs_drop, float drop_p, uint32_t drop_key,
+                             void* stream) {
     int64_t nrows = (int64_t)B * H * T;
     if (drop_p < 0.f || drop_p >= 1.f) return A3T_EINVAL;
     if (drop_p == 0.f) probs_drop = nullptr;
@@ -694,7 +701,7 @@ extern "C" int a3t_relpos_softmax_fwd(const void* ac, const void* bd, int scores
     if (scores_dtype == A3T_BF16 && probs_dtype == A3T_BF16 && T % 8 == 0 && T <= 2048 && ac_bs % 8 == 0 &&
         p_bs % 8 == 0 && sm_al16(ac) && sm_al16(probs) && sm_al16(keymask) && (!probs_drop || sm_al16(probs_drop))) {
 #define CALLV(NC)                                                                                                     \
-    hipLaunchKernelGGL(relpos_softmax_fwd_bf16_kernel<NC>, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0,           \
+    hipLaunchKernelGGL((relpos_softmax_fwd_bf16_kernel<NC, PLAIN>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0,           \
                        (hipStream_t)stream, (const unsigned short*)ac, (const unsigned short*)bd, keymask,            \
                        (unsigned short*)probs, H, T, ac_bs, bd_bs, p_bs, scale, nrows, (unsigned short*)probs_drop, \
                        thr, dinv, drop_key)
@@ -702,8 +709,25 @@ extern "C" int a3t_relpos_softmax_fwd(const void* ac, const void* bd, int scores
 #undef CALLV
         return (int)hipGetLastError();
     }
-    return relpos_softmax_fwd_launch<false>(ac, bd, scores_dtype, keymask, probs, probs_dtype, H, T, ac_bs, bd_bs, p_bs, scale,
-                                            nrows, probs_drop, thr, dinv, drop_key, nullptr, (hipStream_t)stream);
+    return relpos_softmax_fwd_launch<false, PLAIN>(ac, bd, scores_dtype, keymask, probs, probs_dtype, H, T, ac_bs, bd_bs, p_bs,
+                                                   scale, nrows, probs_drop, thr, dinv, drop_key, nullptr, (hipStream_t)stream);
+}
+extern "C" int a3t_relpos_softmax_fwd(const void* ac, const void* bd, int scores_dtype, const uint8_t* keymask,
+                                      void* probs, int probs_dtype, int B, int H, int T, int64_t ac_bs, int64_t bd_bs,
+                                      int64_t p_bs, float scale, void* probs_drop, float drop_p, uint32_t drop_key,
+                                      void* stream) {
+    return softmax_fwd_entry<false>(ac, bd, scores_dtype, keymask, probs, probs_dtype, B, H, T, ac_bs, bd_bs, p_bs, scale,
+                                    probs_drop, drop_p, drop_key, stream);
+}
+// softmax_j(ac * scale) with the key mask: the same kernels without the positional term (no bd operand at all)
+extern "C" int a3t_softmax_plain_fwd(const void* ac, int scores_dtype, const uint8_t* keymask, void* probs, int probs_dtype,
+                                     int B, int H, int T, int64_t ac_bs, int64_t p_bs, float scale, void* probs_drop,
+                                     float drop_p, uint32_t drop_key, void* stream) {
+    if (!ac || !keymask || !probs || B <= 0 || H <= 0 || T <= 0) return A3T_EINVAL;
+    const int64_t tt = (int64_t)T * T;
+    if (ac_bs < tt || p_bs < tt || ((int64_t)B * H * T + 3) / 4 > 0x7fffffff) return A3T_EINVAL;
+    return softmax_fwd_entry<true>(ac, nullptr, scores_dtype, keymask, probs, probs_dtype, B, H, T, ac_bs, 0, p_bs, scale,
+                                   probs_drop, drop_p, drop_key, stream);
 }
 
 extern "C" int a3t_relpos_softmax_fwd_ragged(const void* ac, const void* bd, int scores_dtype, const int32_t* lens,
@@ -720,7 +744,8 @@ extern "C" int a3t_relpos_softmax_fwd_ragged(const void* ac, const void* bd, int
 
 // ds = probs*(dprobs - sum_j dprobs*probs)*scale: written to ds (same dtype as dbd; may alias dprobs
 // when fp32) and scattered un-shifted into the compact dBD (every dBD element written exactly once).
-template <int NV>
+// PLAIN: ds only (dbd is not touched)
+template <int NV, bool PLAIN = false>
 __global__ __launch_bounds__(256) void relpos_softmax_bwd_kernel(const void* __restrict__ probs, int p_dt,
                                                                  const void* dprobs, int dp_dt, void* ds,
                                                                  void* __restrict__ dbd,
@@ -760,6 +785,7 @@ __global__ __launch_bounds__(256) void relpos_softmax_bwd_kernel(const void* __r
     s = wsum(s);
     auto emit = [&](int j, float v) {
         stx(ds, o_dt, oz + (int64_t)i * T + j, v);
+        if constexpr (PLAIN) return;
         if (j <= i)
             stx(dbd, o_dt, dz + (int64_t)i * T + (T - 1 - i + j), v);
         else if (j > i + 1)
@@ -775,11 +801,11 @@ __global__ __launch_bounds__(256) void relpos_softmax_bwd_kernel(const void* __r
         for (int j = lane; j < T; j += 64)
             emit(j, ldx(probs, p_dt, po + j) * (dpv(po + j, ldx(dprobs, dp_dt, dro + j)) - s) * scale);
     }
-    if (i == 0)  // BD[0][0..T-2] never reaches the scores
+    if (!PLAIN && i == 0)  // BD[0][0..T-2] never reaches the scores
         for (int j = lane; j < T - 1; j += 64) stx(dbd, o_dt, dz + j, 0.f);
 }
 
-template <int NC>
+template <int NC, bool PLAIN = false>
 __global__ __launch_bounds__(256) void relpos_softmax_bwd_bf16_kernel(
     const unsigned short* __restrict__ probs, const unsigned short* __restrict__ dprobs, unsigned short* __restrict__ ds,
     unsigned short* __restrict__ dbd, int T, int64_t p_bs, int64_t dp_bs, int64_t o_bs, float scale, int64_t nrows,
@@ -844,7 +870,9 @@ __global__ __launch_bounds__(256) void relpos_softmax_bwd_bf16_kernel(
             const uint4 u = pack8(o);
             *(uint4*)(so + j0) = u;
             const unsigned int uw[4] = {u.x, u.y, u.z, u.w};
-            if (j0 + 7 <= i) {
+            if constexpr (PLAIN) {
+                (void)uw;
+            } else if (j0 + 7 <= i) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) d0[j0 + e] = (unsigned short)(uw[e >> 1] >> (16 * (e & 1)));
             } else if (j0 >= i + 2) {
@@ -863,14 +891,15 @@ __global__ __launch_bounds__(256) void relpos_softmax_bwd_bf16_kernel(
             }
         }
     }
-    if (i == 0)  // BD[0][0..T-2] never reaches the scores
+    if (!PLAIN && i == 0)  // BD[0][0..T-2] never reaches the scores
         for (int j = lane; j < T - 1; j += 64) dbd[dz + j] = 0;
 }
 
-extern "C" int a3t_relpos_softmax_bwd(const void* probs, int probs_dtype, const void* dprobs, int dprobs_dtype, void* ds,
-                                      void* dbd, int out_dtype, int B, int H, int T, int64_t p_bs, int64_t dp_bs,
-                                      int64_t o_bs, float scale, const void* probs_drop, float drop_p, int64_t dbd_bsb,
-                                      int64_t dbd_bsh, uint32_t drop_key, const float* rowscale, void* stream) {
+template <bool PLAIN>
+static int softmax_bwd_entry(const void* probs, int probs_dtype, const void* dprobs, int dprobs_dtype, void* ds,
+                             void* dbd, int out_dtype, int B, int H, int T, int64_t p_bs, int64_t dp_bs,
+                             int64_t o_bs, float scale, const void* probs_drop, float drop_p, int64_t dbd_bsb,
+                             int64_t dbd_bsh, uint32_t drop_key, const float* rowscale, void* stream) {
     if (dbd_bsb == 0 && dbd_bsh == 0) dbd_bsb = (int64_t)H * o_bs, dbd_bsh = o_bs;     // default: [B][H][T][T] like ds
     if (drop_p < 0.f || drop_p >= 1.f) return A3T_EINVAL;
     const float dinv = 1.f / (1.f - drop_p);
@@ -883,7 +912,7 @@ extern "C" int a3t_relpos_softmax_bwd(const void* probs, int probs_dtype, const 
         p_bs % 8 == 0 && dp_bs % 8 == 0 && o_bs % 8 == 0 && dbd_bsb % 8 == 0 && dbd_bsh % 8 == 0 && sm_al16(probs) && sm_al16(dprobs) && sm_al16(ds) &&
         (!probs_drop || sm_al16(probs_drop)) && ds != dprobs) {
 #define CALLV(NC)                                                                                                  \
-    hipLaunchKernelGGL(relpos_softmax_bwd_bf16_kernel<NC>, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0,        \
+    hipLaunchKernelGGL((relpos_softmax_bwd_bf16_kernel<NC, PLAIN>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0,        \
                        (hipStream_t)stream, (const unsigned short*)probs, (const unsigned short*)dprobs,          \
                        (unsigned short*)ds, (unsigned short*)dbd, T, p_bs, dp_bs, o_bs, scale, nrows,             \
                        (const unsigned short*)probs_drop, dinv, H, dbd_bsb, dbd_bsh, rthr, drop_key, rowscale)
@@ -893,10 +922,28 @@ extern "C" int a3t_relpos_softmax_bwd(const void* probs, int probs_dtype, const 
     }
     if (rthr || rowscale) return A3T_EINVAL;    // (the generic kernel reads the mask off probs_drop and takes normalised probabilities)
 #define CALL(NV)                                                                                                 \
-    hipLaunchKernelGGL(relpos_softmax_bwd_kernel<NV>, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0,           \
+    hipLaunchKernelGGL((relpos_softmax_bwd_kernel<NV, PLAIN>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0,           \
                        (hipStream_t)stream, probs, probs_dtype, dprobs, dprobs_dtype, ds, dbd, out_dtype, T, p_bs, dp_bs, \
                        o_bs, scale, nrows, probs_drop, dinv, H, dbd_bsb, dbd_bsh)
     SM_DISPATCH(T, CALL);
 #undef CALL
     return (int)hipGetLastError();
+}
+extern "C" int a3t_relpos_softmax_bwd(const void* probs, int probs_dtype, const void* dprobs, int dprobs_dtype, void* ds,
+                                      void* dbd, int out_dtype, int B, int H, int T, int64_t p_bs, int64_t dp_bs,
+                                      int64_t o_bs, float scale, const void* probs_drop, float drop_p, int64_t dbd_bsb,
+                                      int64_t dbd_bsh, uint32_t drop_key, const float* rowscale, void* stream) {
+    return softmax_bwd_entry<false>(probs, probs_dtype, dprobs, dprobs_dtype, ds, dbd, out_dtype, B, H, T, p_bs, dp_bs, o_bs, scale,
+                                    probs_drop, drop_p, dbd_bsb, dbd_bsh, drop_key, rowscale, stream);
+}
+// ds = probs * (dprobs - sum_j dprobs * probs) * scale, nothing else: the backward of a3t_softmax_plain_fwd
+extern "C" int a3t_softmax_plain_bwd(const void* probs, int probs_dtype, const void* dprobs, int dprobs_dtype, void* ds,
+                                     int out_dtype, int B, int H, int T, int64_t p_bs, int64_t dp_bs, int64_t o_bs, float scale,
+                                     const void* probs_drop, float drop_p, uint32_t drop_key, const float* rowscale,
+                                     void* stream) {
+    if (!probs || !dprobs || !ds || B <= 0 || H <= 0 || T <= 0) return A3T_EINVAL;
+    const int64_t tt = (int64_t)T * T;
+    if (p_bs < tt || dp_bs < tt || o_bs < tt || ((int64_t)B * H * T + 3) / 4 > 0x7fffffff) return A3T_EINVAL;
+    return softmax_bwd_entry<true>(probs, probs_dtype, dprobs, dprobs_dtype, ds, nullptr, out_dtype, B, H, T, p_bs, dp_bs, o_bs,
+                                   scale, probs_drop, drop_p, 0, 0, drop_key, rowscale, stream);
 }

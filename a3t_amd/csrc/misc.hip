@@ -110,6 +110,153 @@ extern "C" int a3t_embed_finish_bwd(const float* dxs, const float* e, const int6
     return (int)hipGetLastError();
 }
 
+// ---- absolute positions (transformer/embedding.py: PositionalEncoding :82-85 x * sqrt(d) + pe[t], ScaledPositionalEncoding
+// :143-147 x + alpha * pe[t]), fused into the embed-finish pass.  pe [>= max(Tm, Tp)][D] in forward order (row t = PE(t)); t restarts
+// at 0 for the text part of a joined row: speech_embed and text_embed each end in a positional encoding of their own.  The dropout
+// is the encoding's own (over the sum), then the segment embedding and the speaker vector as in embed_finish_fwd_kernel.
+__global__ void embed_finish_abs_fwd_kernel(const float* __restrict__ e, const float* __restrict__ emb,
+                                            const float* __restrict__ seg, const int64_t* __restrict__ text,
+                                            const int64_t* __restrict__ spos, const int64_t* __restrict__ tpos,
+                                            const float* __restrict__ pe, const float* __restrict__ alpha_s,
+                                            const float* __restrict__ alpha_t, float* __restrict__ xs, int B, int Tm, int Tp,
+                                            int D, float xscale, unsigned int thr, float inv, unsigned int key,
+                                            const float* __restrict__ spk) {
+    const int T = Tm + Tp;
+    const int64_t n = (int64_t)B * T * D;
+    const float as = alpha_s ? alpha_s[0] : 1.f, at = alpha_s ? alpha_t[0] : 1.f;
+    const float xsc = alpha_s ? 1.f : xscale;
+    GRID_STRIDE(i, n) {
+        int64_t row = i / D;
+        int c = (int)(i - row * D);
+        int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
+        float v, sg;
+        if (t < Tm) {
+            int64_t r = (int64_t)b * Tm + t;
+            v = fmaxf(e[r * D + c], 0.f) * xsc + as * pe[(int64_t)t * D + c];
+            sg = seg ? seg[spos[r] * D + c] : 0.f;
+        } else {
+            int64_t r = (int64_t)b * Tp + (t - Tm);
+            v = emb[text[r] * D + c] * xsc + at * pe[(int64_t)(t - Tm) * D + c];
+            sg = seg ? seg[tpos[r] * D + c] : 0.f;
+        }
+        if (inv > 0.f) v = rng_keep(key, (unsigned int)i, thr) ? v * inv : 0.f;
+        if (spk) sg += spk[(int64_t)b * D + c];
+        xs[i] = v + sg;
+    }
+}
+extern "C" int a3t_embed_finish_abs_fwd(const float* e, const float* emb, const float* seg, const int64_t* text,
+                                        const int64_t* spos, const int64_t* tpos, const float* pe, const float* alpha_s,
+                                        const float* alpha_t, float* xs, int B, int Tm, int Tp, int D, float xscale,
+                                        float drop_p, uint32_t drop_key, const float* spk, void* stream) {
+    if (!pe || !xs || B <= 0 || Tm < 0 || Tp < 0 || Tm + Tp <= 0 || D <= 0 || (alpha_s == nullptr) != (alpha_t == nullptr) ||
+        (Tm > 0 && !e) || (Tp > 0 && (!emb || !text)) || drop_p < 0.f || drop_p >= 1.f)
+        return A3T_EINVAL;
+    int64_t n = (int64_t)B * (Tm + Tp) * D;
+    hipLaunchKernelGGL(embed_finish_abs_fwd_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, e, emb, seg, text,
+                       spos, tpos, pe, alpha_s, alpha_t, xs, B, Tm, Tp, D, xscale,
+                       (unsigned int)((double)drop_p * 4294967296.0), drop_p > 0.f ? 1.f / (1.f - drop_p) : 0.f, drop_key, spk);
+    return (int)hipGetLastError();
+}
+
+// Backward of the above.  de / demb / dseg as embed_finish_bwd_kernel (the factor on the embedding side is 1 with alpha).
+// partial (alpha given): [gridDim.x][2] = this workgroup's sums of dx * pe over the kept speech / text elements, reduced in a fixed
+// order (grid-stride per thread, xor-shuffle per wave, waves 0..3 in turn): no floating-point atomics, the same bits every run.
+__global__ __launch_bounds__(256) void embed_finish_abs_bwd_kernel(
+    const float* __restrict__ dxs, const float* __restrict__ e, const int64_t* __restrict__ text,
+    const int64_t* __restrict__ spos, const int64_t* __restrict__ tpos, const float* __restrict__ pe, float* __restrict__ de,
+    float* demb, float* dseg, float* __restrict__ partial, int B, int Tm, int Tp, int D, int V, int nseg, float xscale,
+    unsigned int thr, float inv, unsigned int key) {
+    const int T = Tm + Tp;
+    const int64_t n = (int64_t)B * T * D;
+    float ps = 0.f, pt = 0.f;
+    GRID_STRIDE(i, n) {
+        int64_t row = i / D;
+        int c = (int)(i - row * D);
+        int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
+        float g = dxs[i];
+        float gd = g;
+        if (inv > 0.f) gd = rng_keep(key, (unsigned int)i, thr) ? g * inv : 0.f;
+        if (t < Tm) {
+            int64_t r = (int64_t)b * Tm + t;
+            de[r * D + c] = (e[r * D + c] > 0.f) ? gd * xscale : 0.f;
+            ps += gd * pe[(int64_t)t * D + c];
+            if (dseg) {
+                int64_t s = spos[r];
+                if (s != nseg - 1) atomicAdd(&dseg[s * D + c], g);
+            }
+        } else {
+            int64_t r = (int64_t)b * Tp + (t - Tm);
+            int64_t tok = text[r];
+            if (tok != V - 1) atomicAdd(&demb[tok * D + c], gd * xscale);
+            pt += gd * pe[(int64_t)(t - Tm) * D + c];
+            if (dseg) {
+                int64_t s = tpos[r];
+                if (s != nseg - 1) atomicAdd(&dseg[s * D + c], g);
+            }
+        }
+    }
+    if (!partial) return;
+    __shared__ float sh[2][4];
+    for (int o = 32; o > 0; o >>= 1) ps += __shfl_xor(ps, o, 64), pt += __shfl_xor(pt, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[0][threadIdx.x >> 6] = ps, sh[1][threadIdx.x >> 6] = pt;
+    __syncthreads();
+    if (threadIdx.x < 2)
+        partial[(int64_t)blockIdx.x * 2 + threadIdx.x] =
+            ((sh[threadIdx.x][0] + sh[threadIdx.x][1]) + sh[threadIdx.x][2]) + sh[threadIdx.x][3];
+}
+// dalpha_s += sum_w partial[w][0], dalpha_t += sum_w partial[w][1]: one workgroup, thread k adds partials k, k + 256, ... in order,
+// then a fixed tree over the 256 threads.
+__global__ __launch_bounds__(256) void alpha_fold_kernel(const float* __restrict__ partial, int nw, float* dalpha_s,
+                                                         float* dalpha_t) {
+    __shared__ float sh[2][256];
+    float a = 0.f, b = 0.f;
+    for (int w = threadIdx.x; w < nw; w += 256) a += partial[2 * w], b += partial[2 * w + 1];
+    sh[0][threadIdx.x] = a, sh[1][threadIdx.x] = b;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[0][threadIdx.x] += sh[0][threadIdx.x + o], sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) dalpha_s[0] += sh[0][0], dalpha_t[0] += sh[1][0];
+}
+extern "C" int a3t_embed_finish_abs_partials(int B, int Tm, int Tp, int D) {
+    return 2 * nblocks((int64_t)B * (Tm + Tp) * D);
+}
+extern "C" int a3t_embed_finish_abs_bwd(const float* dxs, const float* e, const int64_t* text, const int64_t* spos,
+                                        const int64_t* tpos, const float* pe, float* de, float* demb, float* dseg,
+                                        float* dalpha_s, float* dalpha_t, float* partial, int B, int Tm, int Tp, int D, int V,
+                                        int nseg, float xscale, float drop_p, uint32_t drop_key, void* stream) {
+    if (!dxs || !pe || B <= 0 || Tm < 0 || Tp < 0 || Tm + Tp <= 0 || D <= 0 || (dalpha_s == nullptr) != (dalpha_t == nullptr) ||
+        (dalpha_s && !partial) || (Tm > 0 && (!e || !de)) || (Tp > 0 && (!demb || !text)) || drop_p < 0.f || drop_p >= 1.f)
+        return A3T_EINVAL;
+    int64_t n = (int64_t)B * (Tm + Tp) * D;
+    const int nb = nblocks(n);
+    hipLaunchKernelGGL(embed_finish_abs_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, dxs, e, text, spos, tpos, pe,
+                       de, demb, dseg, dalpha_s ? partial : nullptr, B, Tm, Tp, D, V, nseg, dalpha_s ? 1.f : xscale,
+                       (unsigned int)((double)drop_p * 4294967296.0), drop_p > 0.f ? 1.f / (1.f - drop_p) : 0.f, drop_key);
+    if (dalpha_s)
+        hipLaunchKernelGGL(alpha_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, nb, dalpha_s, dalpha_t);
+    return (int)hipGetLastError();
+}
+
+// Decoder entry of a transformer model (MLMDecoder.embed = PositionalEncoding, input_layer None): y[b][t] = drop(x[b][t] * s + pe[t])
+__global__ void scale_add_pos_kernel(const float* __restrict__ x, const float* __restrict__ pe, float* __restrict__ y,
+                                     int64_t n, int64_t TD, float s, unsigned int thr, float inv, unsigned int key) {
+    GRID_STRIDE(i, n) {
+        float v = x[i] * s + pe[i % TD];
+        if (inv > 0.f) v = rng_keep(key, (unsigned int)i, thr) ? v * inv : 0.f;
+        y[i] = v;
+    }
+}
+extern "C" int a3t_scale_add_pos(const float* x, const float* pe, float* y, int B, int T, int D, float s, float drop_p,
+                                 uint32_t drop_key, void* stream) {
+    if (!x || !pe || !y || B <= 0 || T <= 0 || D <= 0 || drop_p < 0.f || drop_p >= 1.f) return A3T_EINVAL;
+    int64_t n = (int64_t)B * T * D;
+    hipLaunchKernelGGL(scale_add_pos_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, x, pe, y, n, (int64_t)T * D, s,
+                       (unsigned int)((double)drop_p * 4294967296.0), drop_p > 0.f ? 1.f / (1.f - drop_p) : 0.f, drop_key);
+    return (int)hipGetLastError();
+}
+
 __global__ void scale_kernel(const float* x, float* y, int64_t n, float s) {
     GRID_STRIDE(i, n) y[i] = x[i] * s;
 }

@@ -63,7 +63,11 @@ class MLMEngine(ConformerStack):
             self.sv["spk"] = se
         self.sv["embed"] = (xm, e, text, spos, tpos, masked, speech2)
         xs = xsp = xst = None
-        if split:
+        if self.transformer:     # absolute positions ride on the same pass (a3t_embed_finish_abs_fwd); never split
+            xs = ws.get("emb.xs", (B * T, d))
+            ops.embed_finish_abs_fwd(e, p["temb"], seg, text, spos, tpos, self.pe_abs, self._alphas(p), xs, B, Tm, Tp, d, xscale,
+                                     drop=self._drop(pp, "emb.x") or (0.0, 0), spk=spk)
+        elif split:
             xsp, xst = ws.get("emb.xsp", (B * Tm, d)), ws.get("emb.xst", (B * Tp, d))
             ops.embed_finish_fwd(e, p["temb"], seg, text, spos, tpos, xsp, B, Tm, 0, d, xscale,
                                  drop=self._drop(pp, "emb.x") or (0.0, 0), spk=spk)
@@ -74,6 +78,11 @@ class MLMEngine(ConformerStack):
             ops.embed_finish_fwd(e, p["temb"], seg, text, spos, tpos, xs, B, Tm, Tp, d, xscale,
                                  drop=self._drop(pp, "emb.x") or (0.0, 0), spk=spk)
         return xs, xsp, xst
+
+    def _alphas(self, views):
+        """(alpha_s, alpha_t) of ScaledPositionalEncoding as views of the parameter store (store.p) or of its gradients (store.g);
+        None with the plain encoding."""
+        return (views["emb.alpha_s"], views["emb.alpha_t"]) if self.c.scaled_pos else None
 
     def _head(self, x, slens=None):
         """Slice the speech frames, sfc, postnet (sedit_model.py:363-372): (hs, before, after), after = None without a postnet
@@ -148,6 +157,9 @@ class MLMEngine(ConformerStack):
         # pre-speech blocks (conformer/encoder.py:547-551): speech and text tokens are finished into buffers of their own, the
         # speech side goes through the pre.{i} blocks at T = T_mel, then the two are joined along time
         xs, xsp, xst = self._prologue(batch, speech2, text, masked, split=c.pre_blocks > 0)
+        if self.transformer:     # no relative-position tables, nothing to project ahead
+            x = self._encode(xs, B, T, (None, keymask), (None, keymask), self._drop(pp, "dec.x"))
+            return self._finish(x, speech2, masked, need_grad, gscale)
         pos_e = self._act("pos.enc", (T, d))
         pos_d = self._act("pos.dec", (T, d))
         pos_on_side = None
@@ -202,6 +214,12 @@ class MLMEngine(ConformerStack):
             xs = ws.get("emb.xs", (B * T, d))
             ops.concat_rows(x, xst, xs, B, Tm, Tp, d)
         x = self._encode(xs, B, T, (pos_e, keymask), (pos_d, keymask), self._drop(pp, "dec.x"))
+        return self._finish(x, speech2, masked, need_grad, gscale)
+
+    def _finish(self, x, speech2, masked, need_grad, gscale):
+        """Head and loss behind the last block's LayerNorm: what forward() returns."""
+        c, ws = self.c, self.ws
+        B, Tm, _, _ = self.dims
         hs, before, after = self._head(x)
         loss = ws.get("head.loss", (1,))
         scratch = ws.get("head.lscratch", (ops.loss_scratch_floats(B * Tm),))
@@ -218,18 +236,21 @@ class MLMEngine(ConformerStack):
         ragged: lens / pos_rows of the encoder's blocks, lens of the decoder's."""
         c = self.c
         for i in range(c.enc_blocks):
-            x = self.block_fwd(f"enc.{i}", x, *enc, B, T, **ragged)
+            x = self.tblock_fwd(f"enc.{i}", x, enc[1], B, T) if self.transformer else self.block_fwd(f"enc.{i}", x, *enc, B, T, **ragged)
         x = self._ln_fwd("enc.after", x, "enc.after", out_dtype=torch.float32)
         if c.has_decoder:
             xd = self.ws.get("dec.in", (B * T, c.adim))
-            if dec_drop:
+            if self.transformer:      # MLMDecoder.embed: PositionalEncoding over the joined row, t = 0 .. T - 1
+                ops.scale_add_pos(x, self.pe_abs, xd, B, T, c.adim, math.sqrt(c.adim), drop=dec_drop or (0.0, 0))
+            elif dec_drop:
                 ops.dropout(x, xd, dec_drop[0], dec_drop[1], scale=math.sqrt(c.adim))
             else:
                 ops.scale(x, xd, math.sqrt(c.adim))
             x = xd
             self._wait_cast("_cast_ev")       # decoder / head shadows cast on the side stream (refresh_weights)
             for i in range(c.dec_blocks):
-                x = self.block_fwd(f"dec.{i}", x, *dec, B, T, lens=ragged.get("lens"))
+                x = self.tblock_fwd(f"dec.{i}", x, dec[1], B, T) if self.transformer else \
+                    self.block_fwd(f"dec.{i}", x, *dec, B, T, lens=ragged.get("lens"))
             x = self._ln_fwd("dec.after", x, "dec.after", out_dtype=torch.float32)
         return x
 
@@ -243,6 +264,9 @@ class MLMEngine(ConformerStack):
         row hold its speech frames for the head (_head(slens)).  Rows of before / after behind sl_b are unspecified (finite).
         No loss."""
         c, ws, (slens, tlens) = self.c, self.ws, lens
+        if self.transformer:
+            raise NotImplementedError("lens= (rows='alone'): ragged rows are implemented for the conformer blocks only, not for a "
+                                      "transformer model")
         self._need_grad = bool(need_grad)
         self._check_ragged(slens, batch["speech"].shape[0])
         self._check_ragged(tlens, batch["speech"].shape[0])
@@ -317,20 +341,29 @@ class MLMEngine(ConformerStack):
         g = ws.get("grad.x", (B * T, d), zero=True)
         g16 = self._g16(g)
         ops.slice_rows(g, dhs, B, T, Tm, d, reverse_add=True)
+        tr = self.transformer
+
+        def closing(stack, n):      # a transformer stack ends in an FFN, not in a block LayerNorm: its bias gradient comes from after_norm's backward
+            return ((gr[f"{stack}.{n - 1}.ff.b2"], 1.0), f"{stack}.{n - 1}.ff.o") if tr else (None, None)
+
+        def stack_bwd(stack, n):
+            for i in reversed(range(n)):
+                if tr:
+                    self.tblock_bwd(f"{stack}.{i}", g, B, T, f"{stack}.{i - 1}" if i > 0 else None)
+                    done(f"{stack}.{i}.mha.ln.g")
+                else:
+                    self.block_bwd(f"{stack}.{i}", g, B, T)
+                    done(f"{stack}.{i}.ffm.ln.g")
         if c.has_decoder:
-            self._ln_bwd("dec.after", g, "dec.after", None, g, g16)
-            for i in reversed(range(c.dec_blocks)):
-                self.block_bwd(f"dec.{i}", g, B, T)
-                done(f"dec.{i}.ffm.ln.g")
+            self._ln_bwd("dec.after", g, "dec.after", None, g, g16, *closing("dec", c.dec_blocks))
+            stack_bwd("dec", c.dec_blocks)
             dd = self._drop(c.positional_dropout_rate, "dec.x")
             if dd:
                 ops.dropout(g, g, dd[0], dd[1], scale=math.sqrt(d))
             else:
                 ops.scale(g, g, math.sqrt(d))
-        self._ln_bwd("enc.after", g, "enc.after", None, g, g16)
-        for i in reversed(range(c.enc_blocks)):
-            self.block_bwd(f"enc.{i}", g, B, T)
-            done(f"enc.{i}.ffm.ln.g")
+        self._ln_bwd("enc.after", g, "enc.after", None, g, g16, *closing("enc", c.enc_blocks))
+        stack_bwd("enc", c.enc_blocks)
         gs = gt = None
         if c.pre_blocks > 0:     # the gradient of the concatenation: the speech part goes back through the pre-speech blocks
             gs, gt = ws.get("grad.xsp", (B * Tm, d)), ws.get("grad.xst", (B * Tp, d))
@@ -354,7 +387,12 @@ class MLMEngine(ConformerStack):
         de = ws.get("tmp.de", (B * Tm, d))
         dseg = gr["seg"] if c.segment_emb else None
         pdrop = c.positional_dropout_rate
-        if gs is None:
+        if tr:
+            dal = self._alphas(gr)
+            part = ws.get("tmp.dalpha", (ops.embed_finish_abs_partials(B, Tm, Tp, d),)) if dal is not None else None
+            ops.embed_finish_abs_bwd(g, e, text, spos, tpos, self.pe_abs, de, gr["temb"], dseg, dal, part, B, Tm, Tp, d, c.vocab,
+                                     c.seg_table, math.sqrt(d), drop=self._drop(pdrop, "emb.x") or (0.0, 0))
+        elif gs is None:
             ops.embed_finish_bwd(g, e, text, spos, tpos, de, gr["temb"], dseg, B, Tm, Tp, d, c.vocab, c.seg_table,
                                  math.sqrt(d), drop=self._drop(pdrop, "emb.x") or (0.0, 0))
         else:

@@ -228,6 +228,9 @@ class ESPnetMLMEncAsDecoderModel(torch.nn.Module):
         B, Tmax = speech.shape[0], speech.shape[1]
         sb, nsp = self._span_arguments(span_boundary, span_counts, B)
         if rows == "alone":
+            if self.cfg.block == "transformer":
+                raise NotImplementedError("rows='alone' (lens= on the engine): ragged rows are implemented for the conformer blocks "
+                                          "only, not for a transformer model")
             if self.compute not in ("f32", "bf16x3") or self.training:
                 raise ValueError("rows='alone' needs a model built with compute='f32' or 'bf16x3' in eval mode "
                                  f"(compute={self.compute!r}, training={self.training}): the fused bf16 attention forward has "

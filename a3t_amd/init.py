@@ -41,6 +41,8 @@ def xavier_init_(store: ParamStore, seed: int = 0, bn_gamma: float = 0.0):
             new[key] = w
         elif len(shp) > 1:
             new[key] = _xavier(shp, gen)
+        elif len(shp) == 0:       # ScaledPositionalEncoding.alpha: neither loop of initialize() touches a 0-d parameter
+            new[key] = torch.ones(shp)
         elif ("norm" in key and "conv_module.norm" not in key) or key.startswith("encoder.speech_embed.2"):
             new[key] = torch.ones(shp) if key.endswith("weight") else torch.zeros(shp)   # LayerNorm reset
         elif key.endswith(("conv_module.norm.weight", ".1.weight")):

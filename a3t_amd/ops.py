@@ -405,6 +405,32 @@ def attn_fwd_train(qu, qv, qkv, P, keymask, ctx, lse, probs, probs_drop, rowscal
                         (T, T, dk, B * H, 1, 1)))
 
 
+def attn_fwd_plain(qkv, keymask, ctx, lse, B, H, T, scale, drop=(0.0, 0)):
+    """attn_fwd without the positional term: ctx[b, :, h, :] = dropout(softmax(q k^T * scale)) v, q | k | v the thirds of qkv
+    [B*T][3d] (bf16); the band-free instantiation of the fused kernels."""
+    d = qkv.shape[1] // 3
+    if qkv.dtype != torch.bfloat16 or ctx.dtype != torch.bfloat16 or qkv.shape[0] < B * T or ctx.numel() < B * T * d or \
+            lse.numel() < B * H * T or keymask.numel() < B * T or d % H:
+        raise ValueError("attn_fwd_plain: shapes do not fit")
+    L.check(L.load().a3t_attn_fwd_plain(_ptr(qkv), _ptr(qkv.view(-1)[d:]), _ptr(qkv.view(-1)[2 * d:]), _ptr(keymask), _ptr(ctx),
+                                        _ptr(lse), B, H, T, d // H, 3 * d, 3 * d, d, scale, drop[0], drop[1], _stream()),
+            "attn_fwd_plain")
+
+
+def attn_fwd_train_plain(qkv, keymask, ctx, lse, probs, probs_drop, rowscale, B, H, T, scale, drop=(0.0, 0)):
+    """attn_fwd_train without the positional term; probs / probs_drop / rowscale as there (probs_drop=None with dropout on: the
+    mask in the sign bits of probs)."""
+    d = qkv.shape[1] // 3
+    n = B * H * T * T
+    if qkv.dtype != torch.bfloat16 or ctx.dtype != torch.bfloat16 or probs.dtype != torch.bfloat16 or qkv.shape[0] < B * T or \
+            ctx.numel() < B * T * d or lse.numel() < B * H * T or rowscale.numel() < B * H * T or keymask.numel() < B * T or \
+            probs.numel() < n or (probs_drop is not None and (probs_drop.numel() < n or probs_drop.dtype != torch.bfloat16)) or d % H:
+        raise ValueError("attn_fwd_train_plain: shapes do not fit")
+    L.check(L.load().a3t_attn_fwd_train_plain(_ptr(qkv), _ptr(qkv.view(-1)[d:]), _ptr(qkv.view(-1)[2 * d:]), _ptr(keymask),
+                                              _ptr(ctx), _ptr(lse), _ptr(probs), _ptr(probs_drop), _ptr(rowscale), B, H, T, d // H,
+                                              3 * d, 3 * d, d, scale, drop[0], drop[1], _stream()), "attn_fwd_train_plain")
+
+
 def attn_scale_rows(x, rowscale, y, B, H, T):
     d = x.shape[1]
     L.check(L.load().a3t_attn_scale_rows(_ptr(x), _ptr(rowscale), _ptr(y), B, H, T, d // H, _stream()), "attn_scale_rows")
@@ -439,6 +465,83 @@ def embed_finish_bwd(dxs, e, text, spos, tpos, de, demb, dseg, B, Tm, Tp, D, V, 
     L.check(L.load().a3t_embed_finish_bwd(_ptr(dxs), _ptr(e), _ptr(text), _ptr(spos), _ptr(tpos), _ptr(de),
                                           _ptr(demb), _ptr(dseg), B, Tm, Tp, D, V, nseg, xscale, drop[0], drop[1],
                                           _stream()), "embed_bwd")
+
+
+def _f32c(t, n, what):
+    """t is a contiguous fp32 tensor of at least n elements (what the absolute-position kernels index without a stride)."""
+    if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+        raise ValueError(f"{what}: expected a contiguous float32 tensor of >= {n} elements")
+    return t
+
+
+def embed_finish_abs_fwd(e, emb, seg, text, spos, tpos, pe, alpha, xs, B, Tm, Tp, D, xscale, drop=(0.0, 0), spk=None):
+    """embed_finish_fwd with absolute positions: relu(e) * xscale + pe[t] | emb[text] * xscale + pe[t - Tm], or with
+    alpha = (alpha_s, alpha_t) (device scalars) relu(e) + alpha_s * pe[t] | emb[text] + alpha_t * pe[t - Tm]; then dropout, + seg,
+    + spk.  pe: [>= max(Tm, Tp)][D] fp32, row t = PE(t)."""
+    _f32c(pe, max(Tm, Tp) * D, "pe")
+    _f32c(xs, B * (Tm + Tp) * D, "xs")
+    if Tm:
+        _f32c(e, B * Tm * D, "e")
+    if Tp and (text.dtype != torch.int64 or text.numel() < B * Tp):
+        raise ValueError("text: expected int64 [B][Tp]")
+    if seg is not None and (spos.numel() < B * Tm or tpos.numel() < B * Tp or spos.dtype != torch.int64 or tpos.dtype != torch.int64):
+        raise ValueError("spos / tpos: expected int64 [B][Tm] / [B][Tp]")
+    a_s, a_t = alpha if alpha is not None else (None, None)
+    L.check(L.load().a3t_embed_finish_abs_fwd(_ptr(e), _ptr(emb), _ptr(seg), _ptr(text), _ptr(spos), _ptr(tpos), _ptr(pe),
+                                              _ptr(a_s), _ptr(a_t), _ptr(xs), B, Tm, Tp, D, xscale, drop[0], drop[1], _ptr(spk),
+                                              _stream()), "embed_abs_fwd")
+
+
+def embed_finish_abs_partials(B, Tm, Tp, D):
+    """Floats of scratch embed_finish_abs_bwd needs for the per-workgroup partial sums of the alpha gradients."""
+    return int(L.load().a3t_embed_finish_abs_partials(B, Tm, Tp, D))
+
+
+def embed_finish_abs_bwd(dxs, e, text, spos, tpos, pe, de, demb, dseg, dalpha, partial, B, Tm, Tp, D, V, nseg, xscale,
+                         drop=(0.0, 0)):
+    """Backward of embed_finish_abs_fwd.  dalpha = (dalpha_s, dalpha_t) (accumulated into; partial = fp32 scratch of
+    embed_finish_abs_partials floats) or None for the plain encoding."""
+    _f32c(pe, max(Tm, Tp) * D, "pe")
+    _f32c(dxs, B * (Tm + Tp) * D, "dxs")
+    if Tm:
+        _f32c(e, B * Tm * D, "e")
+        _f32c(de, B * Tm * D, "de")
+    if Tp:
+        _f32c(demb, V * D, "demb")
+    d_s, d_t = dalpha if dalpha is not None else (None, None)
+    if dalpha is not None:
+        _f32c(partial, embed_finish_abs_partials(B, Tm, Tp, D), "partial")
+    L.check(L.load().a3t_embed_finish_abs_bwd(_ptr(dxs), _ptr(e), _ptr(text), _ptr(spos), _ptr(tpos), _ptr(pe), _ptr(de),
+                                              _ptr(demb), _ptr(dseg), _ptr(d_s), _ptr(d_t), _ptr(partial), B, Tm, Tp, D, V, nseg,
+                                              xscale, drop[0], drop[1], _stream()), "embed_abs_bwd")
+
+
+def scale_add_pos(x, pe, y, B, T, D, s, drop=(0.0, 0)):
+    """y[b][t] = dropout(x[b][t] * s + pe[t]): the decoder entry of a transformer model."""
+    _f32c(x, B * T * D, "x")
+    _f32c(y, B * T * D, "y")
+    _f32c(pe, T * D, "pe")
+    L.check(L.load().a3t_scale_add_pos(_ptr(x), _ptr(pe), _ptr(y), B, T, D, s, drop[0], drop[1], _stream()), "scale_add_pos")
+
+
+def softmax_plain_fwd(ac, keymask, probs, B, H, T, scale, probs_drop=None, drop=(0.0, 0)):
+    """relpos_softmax_fwd without the positional term: probs = softmax_j(ac * scale) under the key mask."""
+    n = B * H * T * T
+    if ac.numel() < n or probs.numel() < n or keymask.numel() < B * T or (probs_drop is not None and probs_drop.numel() < n):
+        raise ValueError("softmax_plain_fwd: shapes do not fit")
+    L.check(L.load().a3t_softmax_plain_fwd(_ptr(ac), _dt(ac), _ptr(keymask), _ptr(probs), _dt(probs), B, H, T, T * T, T * T, scale,
+                                           _ptr(probs_drop), drop[0], drop[1], _stream()), "softmax_plain_fwd")
+
+
+def softmax_plain_bwd(probs, dprobs, ds, B, H, T, scale, probs_drop=None, drop_p=0.0, drop_key=0, rowscale=None):
+    """relpos_softmax_bwd without dbd: ds = probs * (dprobs - sum_j dprobs * probs) * scale (ds may be dprobs itself in fp32)."""
+    n = B * H * T * T
+    if probs.numel() < n or dprobs.numel() < n or ds.numel() < n or (probs_drop is not None and probs_drop.numel() < n) or \
+            (rowscale is not None and rowscale.numel() < B * H * T):
+        raise ValueError("softmax_plain_bwd: shapes do not fit")
+    L.check(L.load().a3t_softmax_plain_bwd(_ptr(probs), _dt(probs), _ptr(dprobs), _dt(dprobs), _ptr(ds), _dt(ds), B, H, T, T * T,
+                                           T * T, T * T, scale, _ptr(probs_drop), drop_p, drop_key, _ptr(rowscale), _stream()),
+            "softmax_plain_bwd")
 
 
 def scale(x, y, s):

@@ -33,8 +33,19 @@ def _block_layout(c: A3TConfig, K: int) -> List[Tuple[str, tuple]]:
     return out
 
 
+def _tblock_layout(c: A3TConfig, K: int = 0) -> List[Tuple[str, tuple]]:
+    """One transformer EncoderLayer (transformer/encoder_layer.py), in forward order: attention, then the FFN.  The names are the
+    conformer block's, so that the sub-layers run on the same code; `linear` FFN weights are the k = 1 case of the conv layout."""
+    d, ff, kf = c.adim, c.ff, c.ff_kernel
+    return [("mha.ln.g", (d,)), ("mha.ln.b", (d,)), ("mha.wqkv", (3 * d, d)), ("mha.bqkv", (3 * d,)), ("mha.wo", (d, d)),
+            ("mha.bo", (d,)), ("ff.ln.g", (d,)), ("ff.ln.b", (d,)), ("ff.w1", (ff, kf, d)), ("ff.b1", (ff,)),
+            ("ff.w2", (d, kf, ff)), ("ff.b2", (d,))]
+
+
 def param_layout(c: A3TConfig) -> "OrderedDict[str, tuple]":
     d = c.adim
+    transformer = c.block == "transformer"
+    _block_layout = globals()["_tblock_layout" if transformer else "_block_layout"]
     lay = OrderedDict()
     if c.segment_emb:
         lay["seg"] = (c.seg_table, d)
@@ -44,6 +55,9 @@ def param_layout(c: A3TConfig) -> "OrderedDict[str, tuple]":
     lay["emb.ln.g"] = (d,)
     lay["emb.ln.b"] = (d,)
     lay["temb"] = (c.vocab, d)
+    if transformer and c.scaled_pos:      # ScaledPositionalEncoding.alpha of speech_embed.4 / text_embed.1
+        lay["emb.alpha_s"] = (1,)
+        lay["emb.alpha_t"] = (1,)
     if c.spk_embed_dim > 0:
         lay["spk.w"] = (d, c.spk_embed_dim)
         lay["spk.b"] = (d,)
@@ -76,7 +90,7 @@ def buffer_layout(c: A3TConfig) -> "OrderedDict[str, tuple]":
     """BatchNorm running statistics (not trained, part of the checkpoint)."""
     lay = OrderedDict()
     for st, n in (("pre", c.pre_blocks), ("enc", c.enc_blocks), ("dec", c.dec_blocks if c.has_decoder else 0)):
-        for i in range(n):
+        for i in range(n if c.block != "transformer" else 0):       # (a transformer block has no BatchNorm)
             lay[f"{st}.{i}.cnv.bn.rm"] = (c.adim,)
             lay[f"{st}.{i}.cnv.bn.rv"] = (c.adim,)
     for l in range(c.postnet_layers):
@@ -122,7 +136,28 @@ def _ref_block_map(ref: str, mine: str, c: A3TConfig):
     return m
 
 
+def _ref_tblock_map(ref: str, mine: str, c: A3TConfig):
+    """_ref_block_map for one transformer EncoderLayer.  feed_forward.w_1.weight is [ff][d] for `linear` ("lin1": the k = 1 conv
+    layout [ff][1][d] holds the same numbers in the same order) and [ff][d][k] for conv1d."""
+    d = c.adim
+    m = []
+    a = ref + "self_attn."
+    for j, n in enumerate(("q", "k", "v")):
+        m += [(a + f"linear_{n}.weight", mine + "mha.wqkv", (j * d, (j + 1) * d), "rows"),
+              (a + f"linear_{n}.bias", mine + "mha.bqkv", (j * d, (j + 1) * d), "rows")]
+    m += [(a + "linear_out.weight", mine + "mha.wo", None, "reshape"),
+          (a + "linear_out.bias", mine + "mha.bo", None, "reshape")]
+    wk = "lin1" if c.ff_kernel == 1 else "conv"
+    m += [(ref + "feed_forward.w_1.weight", mine + "ff.w1", None, wk), (ref + "feed_forward.w_1.bias", mine + "ff.b1", None, "reshape"),
+          (ref + "feed_forward.w_2.weight", mine + "ff.w2", None, wk), (ref + "feed_forward.w_2.bias", mine + "ff.b2", None, "reshape")]
+    for rn, mn in (("norm1", "mha.ln"), ("norm2", "ff.ln")):
+        m += [(ref + rn + ".weight", mine + mn + ".g", None, "reshape"), (ref + rn + ".bias", mine + mn + ".b", None, "reshape")]
+    return m
+
+
 def reference_key_map(c: A3TConfig):
+    transformer = c.block == "transformer"
+    _ref_block_map = globals()["_ref_tblock_map" if transformer else "_ref_block_map"]
     m = [("encoder.segment_emb.weight", "seg", None, "reshape")] if c.segment_emb else []
     m += [("encoder.speech_embed.0.mask_feature", "mask_feature", None, "reshape"),
          ("encoder.speech_embed.1.weight", "emb.w", None, "reshape"),
@@ -130,6 +165,9 @@ def reference_key_map(c: A3TConfig):
          ("encoder.speech_embed.2.weight", "emb.ln.g", None, "reshape"),
          ("encoder.speech_embed.2.bias", "emb.ln.b", None, "reshape"),
          ("encoder.text_embed.0.weight", "temb", None, "reshape")]
+    if transformer and c.scaled_pos:
+        m += [("encoder.speech_embed.4.alpha", "emb.alpha_s", None, "scalar"),
+              ("encoder.text_embed.1.alpha", "emb.alpha_t", None, "scalar")]
     if c.spk_embed_dim > 0:    # extension keys (no reference counterpart): optional when loading a reference checkpoint
         m += [("spk_proj.weight", "spk.w", None, "optional"), ("spk_proj.bias", "spk.b", None, "optional")]
     for i in range(c.pre_blocks):
@@ -158,6 +196,10 @@ def reference_shape(kind: str, store_shape: tuple, key: str) -> tuple:
     if kind == "conv":
         o, t, i = store_shape
         return (o, i, t)
+    if kind == "lin1":
+        return (store_shape[0], store_shape[2])
+    if kind == "scalar":
+        return ()
     return store_shape
 
 
@@ -211,6 +253,10 @@ class ParamStore:
             t = self._view(name, rows, kind, grads).detach()
             if kind == "conv":
                 t = t.permute(0, 2, 1)
+            elif kind == "lin1":
+                t = t.reshape(t.shape[0], t.shape[2])
+            elif kind == "scalar":
+                t = t.reshape(())
             elif key.endswith("mask_feature"):
                 t = t.view(1, 1, -1)
             elif "pos_bias" in key:

@@ -104,14 +104,17 @@ class MLMTask:
             args.feats_extract = args.feats_extract_conf = None
         if getattr(args, "normalize", None) is not None:
             logging.warning("normalize is built but never applied by the reference model (SURVEY §0); ignored")
-        if args.encoder != "conformer":
-            raise NotImplementedError(f"encoder={args.encoder!r}: only encoder=conformer is implemented")
-        if args.decoder not in ("conformer", "no_decoder"):
-            raise NotImplementedError(f"decoder={args.decoder!r}: only decoder=conformer and decoder=no_decoder are implemented")
+        if args.encoder not in ("conformer", "transformer"):
+            raise NotImplementedError(f"encoder={args.encoder!r}: only encoder=conformer and encoder=transformer are implemented")
+        if args.decoder not in (args.encoder, "no_decoder"):
+            raise NotImplementedError(f"decoder={args.decoder!r} with encoder={args.encoder!r}: only decoder={args.encoder} (the "
+                                      "encoder's block type) and decoder=no_decoder are implemented")
         has_decoder = args.decoder != "no_decoder"
+        block = args.encoder
+        scaled = bool(getattr(args, "use_scaled_pos_enc", False))
         # the reference force-selects the legacy rel-pos implementation and writes it back into args (decoder_conf only when
-        # there is a conformer decoder, tasks/mlm.py:393-395)
-        for conf in (args.encoder_conf, args.decoder_conf) if has_decoder else (args.encoder_conf,):
+        # there is a conformer decoder, tasks/mlm.py:393-395); a transformer model's confs are left as they are
+        for conf in () if block != "conformer" else (args.encoder_conf, args.decoder_conf) if has_decoder else (args.encoder_conf,):
             if conf.get("pos_enc_layer_type", "rel_pos") == "rel_pos":
                 conf["pos_enc_layer_type"] = "legacy_rel_pos"
             if conf.get("selfattention_layer_type", "rel_selfattn") == "rel_selfattn":
@@ -121,7 +124,8 @@ class MLMTask:
         if args.model_conf.get("duration_predictor_layers", 0) > 0:
             raise NotImplementedError("ESPnetMLMTTSModel (duration predictor variant) is listed as 'next' (SURVEY §8f)")
         cfg = A3TConfig.from_espnet(args.encoder_conf, args.decoder_conf, args.model_conf, args.input_size, odim,
-                                    vocab_size, getattr(args, "feats_extract_conf", None), has_decoder=has_decoder)
+                                    vocab_size, getattr(args, "feats_extract_conf", None), has_decoder=has_decoder,
+                                    block=block, scaled_pos=scaled)
         model = ESPnetMLMEncAsDecoderModel(token_list=token_list, odim=odim, feats_extract=feats_extract,
                                            normalize=None, config=cfg, device=device, compute=compute,
                                            **args.model_conf)
@@ -136,7 +140,7 @@ class MLMTask:
             # build_model_from_file path) or from `init: xavier_uniform` (the recipe).
             n = 0
             for k, v in model.store.p.items():
-                if k.endswith(".g"):
+                if k.endswith(".g") or k.startswith("emb.alpha_"):
                     v.fill_(1.0)
                     n += 1
             logging.warning("MLMTask.build_model(init=None): weights are zero until load_state_dict(); %d norm scales set to 1 "

@@ -175,9 +175,10 @@ class A3TTrainer:
             dist.broadcast(store.flat, 0)                      # C5
             for b in store.buf.values():                       # C2 (once: BN statistics then stay rank-local)
                 dist.broadcast(b, 0)
-            bounds = [store.offsets[f"pre.{i}.ffm.ln.g"][0] for i in range(cfg.pre_blocks)]
-            bounds += [store.offsets[f"enc.{i}.ffm.ln.g"][0] for i in range(cfg.enc_blocks)]
-            bounds += [store.offsets[f"dec.{i}.ffm.ln.g"][0] for i in range(cfg.dec_blocks if cfg.has_decoder else 0)]
+            first = "mha.ln.g" if cfg.block == "transformer" else "ffm.ln.g"      # a block's first parameter (engine.backward's hook)
+            bounds = [store.offsets[f"pre.{i}.{first}"][0] for i in range(cfg.pre_blocks)]
+            bounds += [store.offsets[f"enc.{i}.{first}"][0] for i in range(cfg.enc_blocks)]
+            bounds += [store.offsets[f"dec.{i}.{first}"][0] for i in range(cfg.dec_blocks if cfg.has_decoder else 0)]
             bounds += [store.offsets["sfc.w"][0]]
             self.ranges = bucket_ranges(store.total, bounds, bucket_min_elems)   # default: >= 64 MB fp32 per collective
             if overlap:

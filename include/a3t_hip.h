@@ -237,6 +237,15 @@ int a3t_relpos_softmax_bwd(const void* probs, int probs_dtype, const void* dprob
                            void* dbd, int out_dtype, int B, int H, int T, int64_t p_bs, int64_t dp_bs, int64_t o_bs,
                            float scale, const void* probs_drop, float drop_p, int64_t dbd_bs_b, int64_t dbd_bs_h,
                            uint32_t drop_key, const float* rowscale, void* stream);
+/* The pair without a positional term (MultiHeadedAttention, attention.py:64-122, a transformer model's blocks): probs =
+ * softmax_j(ac * scale) under the same key mask, dropout and dtypes; ds alone in the backward.  The same kernels instantiated
+ * without bd / dbd: neither tensor exists.  probs_drop / drop_* / rowscale as above. */
+int a3t_softmax_plain_fwd(const void* ac, int scores_dtype, const uint8_t* keymask, void* probs, int probs_dtype, int B, int H,
+                          int T, int64_t ac_bs, int64_t p_bs, float scale, void* probs_drop, float drop_p, uint32_t drop_key,
+                          void* stream);
+int a3t_softmax_plain_bwd(const void* probs, int probs_dtype, const void* dprobs, int dprobs_dtype, void* ds, int out_dtype,
+                          int B, int H, int T, int64_t p_bs, int64_t dp_bs, int64_t o_bs, float scale, const void* probs_drop,
+                          float drop_p, uint32_t drop_key, const float* rowscale, void* stream);
 /* rowscale (optional, bf16 vector path): [B*H*T] fp32; probs then hold UN-normalised probabilities exp(s - m_ref) as
  * written by a3t_attn_fwd_train and row r of probs is multiplied by rowscale[r] (= 1 / its row sum) on load. */
 /* drop_p > 0 with probs_drop == NULL (bf16 vector path): the dropout mask is regenerated from the counter RNG with drop_key
@@ -280,6 +289,18 @@ int a3t_attn_fwd_train(const void* qu, const void* qv, const void* k, const void
                        const uint8_t* keymask, void* ctx, float* lse, void* probs, void* probs_drop, float* rowscale,
                        int B, int H, int T, int dk, int64_t ldq, int64_t ldkv, int64_t ldp, int64_t ldo, float scale,
                        float drop_p, uint32_t drop_key, const float* bias_u, const float* bias_v, void* stream);
+/* The two forwards above WITHOUT the positional term (MultiHeadedAttention, attention.py:64-122: the blocks of a transformer
+ * model): scores = q k^T * scale.  Instantiations of the same kernels compiled without the (q + v) fragments, the Pext ring and its
+ * DMA, the band MFMAs and the band scratch; key mask, first-valid-tile skip, fixed reference maximum with the overflow redo,
+ * key-split tail, dropout, the saved un-normalised probabilities (sign-tagged with probs_drop == NULL), rowscale and lse are the
+ * same code, and every output equals, bit for bit, what a3t_attn_fwd / a3t_attn_fwd_train give for qu = qv = q and an all-zero pos.
+ * q [B*T][ldq] (e.g. the first d columns of the fused projection, ldq = 3d).  Shapes and the stream contract as above. */
+int a3t_attn_fwd_plain(const void* q, const void* k, const void* v, const uint8_t* keymask, void* ctx, float* lse, int B, int H,
+                       int T, int dk, int64_t ldq, int64_t ldkv, int64_t ldo, float scale, float drop_p, uint32_t drop_key,
+                       void* stream);
+int a3t_attn_fwd_train_plain(const void* q, const void* k, const void* v, const uint8_t* keymask, void* ctx, float* lse, void* probs,
+                             void* probs_drop, float* rowscale, int B, int H, int T, int dk, int64_t ldq, int64_t ldkv,
+                             int64_t ldo, float scale, float drop_p, uint32_t drop_key, void* stream);
 /* y[r][h*dk + c] = x[r][h*dk + c] * rowscale[(b*H + h)*T + i], r = b*T + i: folds the row normalisation of
  * a3t_attn_fwd_train's probabilities into the dctx operand of dV = probs_drop^T dctx (attention.py:96 backward). */
 int a3t_attn_scale_rows(const void* x, const float* rowscale, void* y, int B, int H, int T, int dk, void* stream);
@@ -315,6 +336,27 @@ int a3t_embed_finish_fwd(const float* e, const float* emb, const float* seg, con
 int a3t_embed_finish_bwd(const float* dxs, const float* e, const int64_t* text, const int64_t* spos,
                          const int64_t* tpos, float* de, float* demb, float* dseg, int B, int Tm, int Tp,
                          int D, int V, int nseg, float xscale, float drop_p, uint32_t drop_key, void* stream);
+/* The same pass with ABSOLUTE positions for a transformer model (transformer/encoder.py:478-501: speech_embed and text_embed each end
+ * in pos_enc_class): alpha_s == alpha_t == NULL, PositionalEncoding, v = relu(e) * xscale + pe[t] / emb[text] * xscale + pe[t'];
+ * both given (device scalars), ScaledPositionalEncoding, v = relu(e) + alpha_s * pe[t] / emb[text] + alpha_t * pe[t'] (xscale unused).
+ * pe [>= max(Tm, Tp)][D] fp32 in forward order, t' = t - Tm restarts at 0 for the text part.  Then the encoding's dropout over the
+ * sum (element index as a3t_embed_finish_fwd), + seg, + spk. */
+int a3t_embed_finish_abs_fwd(const float* e, const float* emb, const float* seg, const int64_t* text, const int64_t* spos,
+                             const int64_t* tpos, const float* pe, const float* alpha_s, const float* alpha_t, float* xs, int B,
+                             int Tm, int Tp, int D, float xscale, float drop_p, uint32_t drop_key, const float* spk,
+                             void* stream);
+/* Its backward: de, demb, dseg as a3t_embed_finish_bwd; dalpha_s / dalpha_t (both or neither) += sum of dx * pe over the kept
+ * speech / text elements, reduced without floating-point atomics -- per-workgroup partial sums into `partial`
+ * (a3t_embed_finish_abs_partials(B, Tm, Tp, D) floats of scratch) and a fixed-order fold: the same bits on every run. */
+int a3t_embed_finish_abs_bwd(const float* dxs, const float* e, const int64_t* text, const int64_t* spos, const int64_t* tpos,
+                             const float* pe, float* de, float* demb, float* dseg, float* dalpha_s, float* dalpha_t,
+                             float* partial, int B, int Tm, int Tp, int D, int V, int nseg, float xscale, float drop_p,
+                             uint32_t drop_key, void* stream);
+int a3t_embed_finish_abs_partials(int B, int Tm, int Tp, int D);      /* floats of `partial` (not an error code) */
+/* Decoder entry of a transformer model (MLMDecoder.embed = PositionalEncoding): y[b][t] = dropout(x[b][t] * s + pe[t]), element
+ * index of the dropout as a3t_dropout's (whose scaled form is its backward) */
+int a3t_scale_add_pos(const float* x, const float* pe, float* y, int B, int T, int D, float s, float drop_p, uint32_t drop_key,
+                      void* stream);
 /* y = x * s (decoder entry xscale, conformer/encoder.py:585-588) */
 int a3t_scale(const float* x, float* y, int64_t n, float s, void* stream);
 int a3t_axpy(const float* x, float* y, int64_t n, float a, void* stream); /* y += a*x */
