@@ -67,6 +67,9 @@ _SIGS = {
     "a3t_attn_scale_rows": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "a3t_attn_bwd_ds": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_float,
                         c_float, ctypes.c_uint32, c_int, c_int64, _P],
+    "a3t_attn_bwd_dpos": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, _P],
+    "a3t_attn_bwd_dpos_ws": [c_int, c_int, c_int, c_int],
+    "a3t_attn_bwd_dpos_plan": [c_int, c_int, c_int, c_int, POINTER(c_int)],
     "a3t_attn_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64,
                      c_float, c_float, ctypes.c_uint32, _P, _P, _P],
     "a3t_pwg_block": [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P],

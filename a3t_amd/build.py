@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "liba3t_hip.so")
-SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_bf16_8p.hip", "gemm_bf16_tn.hip", "gemm_bf16_pn.hip", "gemm_bf16_tt.hip", "attn_fused.hip", "norm_reduce.hip", "convmod_attn.hip", "dwconv_vec.hip", "misc.hip", "pwg_fused.hip", "pwg_fused_f16.hip", "features.hip", "duration.hip", "fs2_tts.hip", "gst.hip", "hifigan.hip", "hifigan_f16.hip", "melgan.hip", "stylemelgan.hip"]
+SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_bf16_8p.hip", "gemm_bf16_tn.hip", "gemm_bf16_pn.hip", "gemm_bf16_tt.hip", "attn_fused.hip", "attn_dpos.hip", "norm_reduce.hip", "convmod_attn.hip", "dwconv_vec.hip", "misc.hip", "pwg_fused.hip", "pwg_fused_f16.hip", "features.hip", "duration.hip", "fs2_tts.hip", "gst.hip", "hifigan.hip", "hifigan_f16.hip", "melgan.hip", "stylemelgan.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"] + os.environ.get("A3T_EXTRA_FLAGS", "").split()
 
 
@@ -18,7 +18,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # The waveform kernels share their loops through headers (wave_conv.h, wave_tiles.h), where one edit moves the registers of
 # several kernels at once: test_wave_kernel_register_budget holds each to no scratch and to its occupancy.
 WAVE_SOURCES = ("pwg_fused.hip", "pwg_fused_f16.hip", "hifigan.hip", "hifigan_f16.hip", "melgan.hip", "stylemelgan.hip")
-RES_SOURCES = ("gemm_bf16.hip", "gemm_bf16_8p.hip", "gemm_bf16_tn.hip", "gemm_bf16_pn.hip", "gemm_bf16_tt.hip", "attn_fused.hip", "norm_reduce.hip") + WAVE_SOURCES
+RES_SOURCES = ("gemm_bf16.hip", "gemm_bf16_8p.hip", "gemm_bf16_tn.hip", "gemm_bf16_pn.hip", "gemm_bf16_tt.hip", "attn_fused.hip", "attn_dpos.hip", "norm_reduce.hip") + WAVE_SOURCES
 RES_FLAG = ["-Rpass-analysis=kernel-resource-usage"]
 
 

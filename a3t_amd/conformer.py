@@ -661,9 +661,18 @@ class ConformerStack(StepSchedule):
         else:
             ops.relpos_softmax_bwd(probs, dpr, ds, dbd, B, H, T, scale, probs_drop=None if regen else pdrop,
                                    drop_p=adr[0] if adr else 0.0, drop_key=adr[1] if regen else 0, rowscale=rs)
+        # bf16 path, where a3t_attn_bwd_dpos takes the shape: its workspace is a scratch-ring tensor like tmp.qv (csrc/attn_dpos.hip)
+        dpos = self.bf16 and dbd.dtype == torch.bfloat16 and ops.attn_bwd_dpos_plan(B, H, T, dk) is not None
+        dpos_ws = self.ws.get(self._t("tmp.dPws"), (ops.attn_bwd_dpos_ws(B, H, T, dk),)) if dpos else None
+
         def pos_weight_grad():   # dP_h += sum_b dbd^T (q+v) -> d W_pos; only the side stream touches tmp.dP*
             if qv_ready is not None and self.side is not None:
                 qv_ready.wait_on(self.side)
+            if dpos:     # streaming product over groups of batch elements + a fold in fixed order: no atomics, no clear, no cast
+                dP16 = self.ws.get("tmp.dP16", (T, d), torch.bfloat16)
+                ops.attn_bwd_dpos(dbd, qv, dpos_ws, dP16, B, H, T, T + 1 if dview else T, zbd)
+                ops.linear_bwd_weight(dP16, pos, gr[pre + ".wpos"], compute=cmp)
+                return
             dP = self._arena_slot("bwd32", tag + ".dP", T * d).view(T, d)   # cleared once per backward (main stream)
             ops.gemm(dbd, qv, dP, T, dk, T, 1, T + 1 if dview else T, 1, d, d, batch=B * H, batch_inner=H, a_bs=zbd, b_bs=(T * d, dk),
                      c_bs=(0, dk), acc=ACC_ATOMIC, compute=cmp, a_view=dview)

@@ -450,6 +450,29 @@ def attn_bwd_ds(dctx, ctx, qkv, probs, rowscale, ds, dbd, B, H, T, scale, drop=(
                                      d // H, d, 3 * d, bsb, bsh, scale, drop[0], drop[1], 1 if signed_probs else 0, ds_bs, _stream()), "attn_bwd_ds")
 
 
+def attn_bwd_dpos_plan(B, H, T, dk):
+    """(rows per tile, row tiles, batch elements per workgroup, grid) of attn_bwd_dpos, or None where it does not take the problem
+    (host only: csrc/attn_dpos.hip, dpos_plan)."""
+    out = (ctypes.c_int * 4)()
+    if not L.load().a3t_attn_bwd_dpos_plan(int(B), int(H), int(T), int(dk), out):
+        return None
+    return tuple(out)
+
+
+def attn_bwd_dpos_ws(B, H, T, dk):
+    """fp32 workspace elements of attn_bwd_dpos (0 where the path does not take the problem)."""
+    return int(L.load().a3t_attn_bwd_dpos_ws(int(B), int(H), int(T), int(dk)))
+
+
+def attn_bwd_dpos(dbd, qv, ws, dP16, B, H, T, dbd_rs, dbd_bs, dP=None):
+    """dP16[r, h*dk + n] = bf16(sum_b sum_i dbd[b, h][i, r] qv[b*T + i, h*dk + n]): the gradient of linear_pos' output as a streaming
+    product over groups of batch elements + a fold in fixed order (no atomics).  dbd: the compact matrix (dbd_rs = T) or its view of dS
+    (dbd_rs = T + 1), (b, h) blocks dbd_bs = (per b, per h) elements apart; ws: attn_bwd_dpos_ws floats; dP: optional fp32 copy."""
+    d = qv.shape[1]
+    L.check(L.load().a3t_attn_bwd_dpos(_ptr(dbd), _ptr(qv), _ptr(ws), _ptr(dP16), _ptr(dP), B, H, T, d // H, int(dbd_rs),
+                                       int(dbd_bs[0]), int(dbd_bs[1]), _stream()), "attn_bwd_dpos")
+
+
 def mask_fill(speech, masked, mask_feature, out):
     M, C = out.shape
     L.check(L.load().a3t_mask_fill(_ptr(speech), _ptr(masked), _ptr(mask_feature), _ptr(out), _dt(out), M, C,

@@ -321,6 +321,20 @@ int a3t_attn_scale_rows(const void* x, const float* rowscale, void* y, int B, in
 int a3t_attn_bwd_ds(const void* dctx, const void* ctx, const void* v, const void* probs, const float* rowscale, void* ds,
                     void* dbd, int B, int H, int T, int dk, int64_t ldo, int64_t ldkv, int64_t dbd_bsb, int64_t dbd_bsh,
                     float scale, float drop_p, uint32_t drop_key, int signed_probs, int64_t ds_bs, void* stream);
+/* Gradient of linear_pos' output (attention.py:190-203 on its way back), summed over the batch without atomics:
+ *   dP[r][h*dk + n] = sum_b sum_i dbd[b][h][i][r] * qv[b*T + i][h*dk + n],  r < T, n < dk      (csrc/attn_dpos.hip)
+ * dbd: bf16, 2-byte aligned, element (b, h, i, r) at b*dbd_bsb + h*dbd_bsh + i*dbd_rs + r -- the stored compact matrix (dbd_rs = T)
+ * or the view of dS (a3t_attn_bwd_ds with dbd = NULL: dbd_rs = T + 1).  qv = (q + v): bf16 [B*T][H*dk], 16-byte aligned.
+ * A streaming product sums a group of batch elements per workgroup into ws[group][T][H*dk] (fp32, 16-byte aligned,
+ * a3t_attn_bwd_dpos_ws(B, H, T, dk) floats: every float of it is overwritten); a fold adds the groups in ascending order and stores
+ * dP16 (bf16 [T][H*dk], 16-byte aligned) and, when dP != NULL, the same sums in fp32: the same bits on every run.
+ * T % 8 == 0, dk % 32 == 0 (<= 192, not 160), one batch element's operand within 2 GiB; anything else: A3T_EINVAL, nothing launched.
+ * a3t_attn_bwd_dpos_plan (host only): 1 and out = {rows per tile, row tiles, batch elements per workgroup, grid} when the path takes
+ * the problem, 0 when it does not (out untouched; _ws returns 0 as well -- neither is an error code). */
+int a3t_attn_bwd_dpos(const void* dbd, const void* qv, float* ws, void* dP16, float* dP, int B, int H, int T, int dk, int64_t dbd_rs,
+                      int64_t dbd_bsb, int64_t dbd_bsh, void* stream);
+int a3t_attn_bwd_dpos_ws(int B, int H, int T, int dk);
+int a3t_attn_bwd_dpos_plan(int B, int H, int T, int dk, int* out);
 
 /* Encoder prologue (conformer/encoder.py:522-553, mlm_encoder.py:57-70). */
 int a3t_mask_fill(const float* speech, const uint8_t* masked, const float* mask_feature, void* out,
